@@ -13,12 +13,19 @@ stages over the ranks (balanced split, e.g. [4,3,3,3,3,3,3,3]) and latents move 
 send/recv on a side stream (``vdpp_amd.pipeline.PipelineStage``).
 
 The JSON line carries: metric/value (K videos / max-over-ranks wall time of the barrier-bracketed timed
-region), ``roofline`` for the dominant kernel (the implicit-GEMM MFMA kernel: algorithmic FLOPs of its
-launches in one UNet forward / their summed HIP-event durations, vs the 2.5 PFLOP/s dense fp16 peak),
-``step_roofline`` (whole UNet forward; both with ``clock_ghz_live`` = the shader clock rank 0's chip held over the timed
-region, from stream-ordered stamps of s_memtime against the 100 MHz counter), ``cpu_baseline`` (the oracle's fp32 UNet restatement timed on the
-host cores on a bounded sample, rank 0 at N=1 only) and ``cpu_simulator`` (the reference's CPU
-simulator-mode path = DummyUNet step pipeline, as re-implemented here + the C oracle).
+region), ``ms_per_step`` (milliseconds per timed video) and ``step_roofline`` (whole UNet forward: executed FLOPs / time
+per forward, vs the 2.5 PFLOP/s dense fp16 peak).  A plain run does only that: set-up, warm-up, the K timed videos, the
+line.  ``--full`` adds every secondary leg, each measured after the timed region and never inside ``value``: ``roofline``
+for the dominant kernel (the implicit-GEMM MFMA kernel: algorithmic FLOPs of its launches in one UNet forward / their
+summed HIP-event durations), ``clock_ghz_live`` in both rooflines (the shader clock rank 0's chip held over the timed
+region, from stream-ordered stamps of s_memtime against the 100 MHz counter), the frames-out leg at N=1, the
+one-video-at-a-time leg, the VAE decode / image encode legs, ``cpu_baseline`` (the oracle's fp32 UNet restatement timed on
+the host cores on a bounded sample, rank 0 at N=1 only) and ``cpu_simulator`` (the reference's CPU simulator-mode path =
+DummyUNet step pipeline, as re-implemented here + the C oracle).
+
+``--dump-outputs DIR`` writes the finished latent of the last timed video (what ``PipelineStage.run_many`` hands its
+caller) to ``DIR/final_latent.npy`` in float32.  Inputs and weights are seeded, so two builds run with the same arguments
+can be compared output for output.
 """
 
 from __future__ import annotations
@@ -382,13 +389,35 @@ def parse():
                     help="also time the pipeline WITH its last edge stage (secondary figure `frames_out`, never `value`): every "
                          "finished latent is decoded to frames by the temporal VAE on a stream of its own beside the UNet "
                          "steps, on the rank where it finishes (models/edge_stages.py::FrameEmitter; ref "
-                         "scripts/generate_video_demo.py:418).  Default at N = 1 unless --no-decode; opt-in at N > 1")
+                         "scripts/generate_video_demo.py:418).  Part of --full at N = 1 unless --no-decode; opt-in otherwise")
     ap.add_argument("--rehearse-cpu", action="store_true",
                     help="NOT a measurement: run this script's whole multi-rank path (launcher, process group, rotating "
                          "chain / ring, watchdog, all_gather_object, steady-state arithmetic, JSON line) with the simulator's "
                          "DummyUNet on CPU tensors over Gloo, so that `--gpus 8` can be rehearsed on a box without 8 GPUs")
     ap.add_argument("--seed", type=int, default=42)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary legs after the timed region (per-kernel roofline, live shader clock, "
+                         "frames-out at N = 1, one-video-at-a-time, VAE decode / image encode, CPU baseline and simulator); "
+                         "the --no-* flags above still switch single legs off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the finished latent of the last timed video to DIR/final_latent.npy (float32)")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, finished):
+    """--dump-outputs: the last timed video's finished latent, as the caller of ``run_many`` receives it, in float32.  A
+    latent over 64 MB (far beyond the benchmark's shapes) is written as a fixed evenly strided sample of its elements."""
+    import numpy as np
+
+    last = finished[-1][-1:].detach().float().cpu()      # last pipeline sample, its last video: (1, 4, F, H, W)
+    arr = last.numpy()
+    if arr.nbytes > DUMP_LIMIT_BYTES:
+        arr = arr.reshape(-1)[::-(-arr.size // (DUMP_LIMIT_BYTES // 4))]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "final_latent.npy"), arr)
 
 
 def cpu_baseline(frames_full, h, w, total_steps):
@@ -1090,7 +1119,7 @@ def main():
         # shader clock over the timed region (rank 0, real model): a ~2 us stamp of the shader-clock and 100 MHz counters at the
         # start and behind every finished sample, in stream order (sp_clock_stamp) -- `roofline.clock_ghz_live`
         stamps = None
-        if cuda and not rehearse and rank == 0:
+        if cuda and not rehearse and rank == 0 and args.full:
             try:
                 stamps = ops.ClockStamps(device, n_samples + 3)
             except Exception as exc:  # noqa: BLE001
@@ -1106,11 +1135,14 @@ def main():
         start_ev = new_event(enable_timing=True); start_ev.record()
         if stamps is not None:
             stamps.stamp()
-        stage.run_many(n_samples, input_supplier=(lambda i: supplier(warm_samples + i)) if (rank == 0 or ring) else None)
+        finished = stage.run_many(n_samples, input_supplier=(lambda i: supplier(warm_samples + i)) if (rank == 0 or ring) else None)
         stage.drain()
         dog.beat("fence after the timed region")
         fence()
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs and finished:      # the last rank holds the finished latents
+            dump_outputs(args.dump_outputs, finished)
+        del finished
         clock_live = None
         if stamps is not None:
             try:
@@ -1121,7 +1153,7 @@ def main():
             except Exception as exc:  # noqa: BLE001
                 print(f"bench.py: clock stamps unreadable ({exc!r})", file=sys.stderr, flush=True)
     frames_out = None
-    if not rehearse and not args.no_decode and (args.emit_frames or n == 1):
+    if not rehearse and not args.no_decode and (args.emit_frames or (n == 1 and args.full)):
         dog.beat("frames-out leg")
         frames_out = frames_out_leg(args, stage, supplier, device, n, rank, ring, mb, conc, fence, dog)
     dog.beat("reduction of the timings")
@@ -1188,6 +1220,7 @@ def main():
             "peak_memory_gb_per_rank": [round(m, 3) for m in peaks], "max_peak_memory_gb": round(max(peaks), 3),
             "ms_per_step": 1e3 * elapsed / steps, "higher_is_better": True, "scaling": "strong",
             "vs_baseline": None, "dtype": "f16+fp8 attention" if args.fp8_attention else "f16", "data": "synthetic",
+            "full": bool(args.full),      # secondary legs (--full) ran after the timed region
             "config": {"workload": ("DummyUNet(4,16) fp32 on CPU (rehearsal), " if rehearse else
                                     "SVD img2vid UNet (1.52B params, random init), ") +
                                    f"latent (1,4,{args.frames},{args.height},{args.width}) fp16 per video, every UNet call on "
@@ -1243,7 +1276,7 @@ def main():
             finalize_distributed()
         dog.stop()
         return
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         with torch.no_grad():
             lat = supplier(0)
             for _ in range(2):     # (profiled forwards run launch by launch, not as a graph replay: the first one
@@ -1332,7 +1365,7 @@ def main():
             out["roofline_attention"] = out.pop("roofline_attention_short_rows")
     # ---- the reference benchmark's own order, one video per UNet call and one at a time (ref src/modes/benchmark.py:101
     # batch_size=1), beside the headline so that rounds and configurations stay comparable: a short leg, never `value`
-    if rank == 0 and n == 1 and not rehearse and not args.no_batch1_leg and (mb, conc) != (1, 1):
+    if rank == 0 and n == 1 and not rehearse and args.full and not args.no_batch1_leg and (mb, conc) != (1, 1):
         with torch.no_grad():
             torch.manual_seed(args.seed)
             model.set_dummy_conditioning(1, args.frames, args.height, args.width, device, guidance_scale=args.guidance_scale)
@@ -1357,10 +1390,10 @@ def main():
                     f"micro-batches of {mb} on {conc} streams"}
     # ---- what the last stage would add per video if it also decoded (ref scripts/generate_video_demo.py:
     # 154-195: decode_latents, decode_chunk_size 14).  Outside the headline metric: the benchmark's videos are latents.
-    if rank == 0 and not args.no_decode:
+    if rank == 0 and args.full and not args.no_decode:
         out["vae_decode"] = vae_decode_leg(device, args.frames, args.height, args.width)
         out["image_encode"] = image_encode_leg(device, args.frames, args.height, args.width)
-    if rank == 0 and n == 1 and not args.no_cpu_baseline:
+    if rank == 0 and n == 1 and args.full and not args.no_cpu_baseline:
         del model, stage
         torch.cuda.empty_cache()
         out["cpu_baseline"] = cpu_baseline(args.frames, args.height, args.width, T)

@@ -217,3 +217,30 @@ def test_refused_arguments_are_not_retried():
     assert r.returncode != 0 and r.stdout.strip() == ""
     assert "not a whole number of micro-batches" in r.stderr
     assert "attempt 1" not in r.stderr
+
+
+def test_dump_outputs_are_the_last_timed_video_and_the_same_at_every_world_size(tmp_path):
+    """--dump-outputs DIR writes the finished latent of the last timed video as float32 DIR/final_latent.npy, after the
+    timed region, from the rank that holds the finished latents.  On CPU tensors (--rehearse-cpu) one rank, the 2-rank
+    ring and the 2-rank chain are fed the same seeded latents, so their dumps must be bit-identical; --steps sets the
+    timed videos and ms_per_step is the time of one of them."""
+    import numpy as np
+
+    dumps = {}
+    for n, extra in ((1, []), (2, []), (2, ["--chain"])):
+        out = tmp_path / f"n{n}{'_'.join(extra)}"
+        r = _rehearse(["--steps", "5", "--warmup", "2", "--micro-batch", "1", "--concurrent", "1", "--dump-outputs",
+                       str(out)] + extra, {}, n=n)
+        assert r.returncode == 0, r.stderr[-4000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout
+        d = json.loads(lines[0])
+        assert d["steps"] == 5 and d["warmup"] == 2 and d["full"] is False
+        assert abs(d["ms_per_step"] * d["value"] - 1e3) < 1e-6 * 1e3
+        assert sorted(os.listdir(out)) == ["final_latent.npy"]
+        dumps[(n, tuple(extra))] = np.load(out / "final_latent.npy")
+    base = dumps[(1, ())]
+    assert base.dtype == np.float32 and base.shape == (1, 4, 4, 16, 16) and np.isfinite(base).all()
+    assert np.abs(base).max() > 0
+    for key, got in dumps.items():
+        assert np.array_equal(got, base), f"world/schedule {key}: dump differs from the single-rank run"
