@@ -129,6 +129,10 @@ typedef struct sp_gemm_desc {
      cin2 a multiple of 64; runs on the 256-row ping-pong tiles (n a multiple of 256 or 320; no geglu / folded LayerNorm /
      ln_out / n_store / Euler tail / per-group weights / split-K).  NULL = off. */
   const void *a2; int64_t lda2; int cin2;
+  /* Guidance rows of the Euler tail: with euler_eps_uncond, video b of the batch mixes with
+     euler_guidance[b * euler_guidance_ld + f] (fp32 [B][euler_guidance_ld], one row of per-frame scales per video;
+     euler_guidance_ld >= euler_frames).  0 = the one row euler_guidance[f] is shared by every video. */
+  int64_t euler_guidance_ld;
 } sp_gemm_desc;
 
 int sp_gemm_f16(const sp_gemm_desc *desc, void *stream);
@@ -284,6 +288,11 @@ int sp_pack_input_f16(const void *latent, const void *image_latents, void *out, 
 int sp_euler_step_f16(const void *latent, const void *eps_cond, const void *eps_uncond,
                       int64_t ld_eps, const float *guidance /*[F] or NULL*/, void *out, float sigma,
                       float sigma_next, int b, int frames, int h, int w, void *stream);
+/* sp_euler_step_f16 with one guidance row per video: gs[b*ld_guidance + f] (guidance fp32 [B][ld_guidance],
+ * ld_guidance >= frames); ld_guidance = 0 is sp_euler_step_f16 (one row [F] shared by every video). */
+int sp_euler_step_rows_f16(const void *latent, const void *eps_cond, const void *eps_uncond,
+                           int64_t ld_eps, const float *guidance, int64_t ld_guidance, void *out, float sigma,
+                           float sigma_next, int b, int frames, int h, int w, void *stream);
 /* channel concat of two NHWC tensors (torch.cat([hidden, skip], dim=1) in the up blocks) */
 int sp_concat_channels_f16(const void *a, int ca, const void *b, int cb, void *out, int64_t rows,
                            void *stream);

@@ -344,7 +344,7 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void gemm_f16_kernel(const GemmArgs
       const int64_t b = bf / p.eul_frames;
       f16x4 u4 = {v[0], v[1], v[2], v[3]};
       float g = 1.f;
-      if (p.eul_u) { u4 = *(const f16x4 *)(p.eul_u + m * p.eul_ldu); g = p.eul_gs[f]; }
+      if (p.eul_u) { u4 = *(const f16x4 *)(p.eul_u + m * p.eul_ldu); g = p.eul_gs[b * p.eul_ldg + f]; }
 #pragma unroll
       for (int ch = 0; ch < 4; ++ch) {
         const int64_t a = ((b * 4 + ch) * p.eul_frames + f) * p.eul_hw + pix;
@@ -748,9 +748,13 @@ extern "C" int sp_gemm_f16(const sp_gemm_desc *d, void *stream) {
                (double)d->euler_sigma);
     if (d->euler_eps_uncond) SP_REQUIRE(d->euler_guidance && d->euler_ld_eps >= 4 && d->euler_ld_eps % 4 == 0,
                                         "sp_gemm_f16: Euler tail: guidance needs euler_guidance and euler_ld_eps");
+    SP_REQUIRE(d->euler_guidance_ld == 0 || d->euler_guidance_ld >= d->euler_frames,
+               "sp_gemm_f16: Euler tail: euler_guidance_ld=%lld must be 0 (one shared row) or >= frames (%d)",
+               (long long)d->euler_guidance_ld, d->euler_frames);
     const float s2 = d->euler_sigma * d->euler_sigma + 1.0f;
     a.eul_lat = (const f16 *)d->euler_latent; a.eul_out = (f16 *)d->euler_out;
     a.eul_u = (const f16 *)d->euler_eps_uncond; a.eul_gs = d->euler_guidance; a.eul_ldu = d->euler_ld_eps;
+    a.eul_ldg = d->euler_guidance_ld;
     a.eul_frames = d->euler_frames; a.eul_hw = d->euler_hw;
     a.eul_c_out = -d->euler_sigma / sqrtf(s2); a.eul_c_skip = 1.0f / s2;
     a.eul_inv_sigma = 1.0f / d->euler_sigma; a.eul_dt = d->euler_sigma_next - d->euler_sigma;

@@ -22,8 +22,9 @@ struct GemmArgs {
   const f16 *res1;
   const f16 *res2;
   // Euler tail (conv_out only): latent in / out (B,4,F,H,W) fp16, optional unconditional eps rows + per-frame guidance
+  // guidance: eul_gs[b * eul_ldg + f] (eul_ldg = 0: one row shared by every video)
   const f16 *eul_lat; f16 *eul_out; const f16 *eul_u; const float *eul_gs;
-  int64_t eul_ldu, eul_hw;
+  int64_t eul_ldu, eul_hw, eul_ldg;
   int eul_frames;
   float eul_c_out, eul_c_skip, eul_inv_sigma, eul_dt;
   const float *ln_stats;    // LayerNorm fold: fp32 [m][2] (mean, rstd), or null

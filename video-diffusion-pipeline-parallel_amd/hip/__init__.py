@@ -40,6 +40,7 @@ class GemmDesc(ctypes.Structure):
         ("w_group_rows", ctypes.c_int64), ("w_group_stride", ctypes.c_int64),
         ("gn_part", ctypes.c_void_p),
         ("a2", ctypes.c_void_p), ("lda2", ctypes.c_int64), ("cin2", ctypes.c_int),
+        ("euler_guidance_ld", ctypes.c_int64),
     ]
 
 
@@ -73,6 +74,7 @@ SIGNATURES = {
     "sp_attn_temporal_f16": (_I, [_P, _P, _P, _P, _L, _L, _L, _L, _I, _I, _L, _I, _F, _P, _P]),
     "sp_pack_input_f16": (_I, [_P, _P, _P, _F, _I, _I, _I, _I, _I, _P]),
     "sp_euler_step_f16": (_I, [_P, _P, _P, _L, _P, _P, _F, _F, _I, _I, _I, _I, _P]),
+    "sp_euler_step_rows_f16": (_I, [_P, _P, _P, _L, _P, _L, _P, _F, _F, _I, _I, _I, _I, _P]),
     "sp_concat_channels_f16": (_I, [_P, _I, _P, _I, _P, _L, _P]),
     "sp_add_rowvec_f16": (_I, [_P, _P, _P, _L, _I, _P]),
     "sp_softmax_rows_f16": (_I, [_P, _L, _L, _I, _P]),

@@ -109,6 +109,7 @@ def gemm(a, w, out, *, m, n, cin, mode=A_LINEAR, lda=None, conv=None, temporal=N
         d.euler_latent, d.euler_out = _f16(euler["latent"], "latent").data_ptr(), _f16(euler["out"], "out").data_ptr()
         d.euler_eps_uncond, d.euler_guidance = _ptr(euler.get("eps_uncond")), _ptr(euler.get("guidance"))
         d.euler_ld_eps = int(euler.get("ld_eps", 0))
+        d.euler_guidance_ld = int(euler.get("ld_guidance", 0))     # guidance [B][ld] per video; 0: one [F] row for all
         d.euler_sigma, d.euler_sigma_next = float(euler["sigma"]), float(euler["sigma_next"])
         d.euler_frames, d.euler_hw = int(euler["frames"]), int(euler["hw"])
     if workspace is not None:      # fp32 scratch: split-K (few rows, long K; too small a buffer simply disables it), or the
@@ -437,9 +438,13 @@ class ClockStamps:
         return sum(ratios) / len(ratios), sum(secs) / len(secs), len(ratios)
 
 
-def euler_step(latent, eps_cond, eps_uncond, guidance, out, *, ld_eps, sigma, sigma_next, b, frames, h, w):
-    _check(load().sp_euler_step_f16(latent.data_ptr(), eps_cond.data_ptr(), _ptr(eps_uncond), ld_eps, _ptr(guidance),
-                                    out.data_ptr(), sigma, sigma_next, b, frames, h, w, _stream()), "sp_euler_step_f16")
+def euler_step(latent, eps_cond, eps_uncond, guidance, out, *, ld_eps, sigma, sigma_next, b, frames, h, w,
+               ld_guidance=0):
+    """``ld_guidance``: ``guidance`` is fp32 [B][ld_guidance], one row of per-frame scales per video; 0 = one [F] row
+    shared by every video (``sp_euler_step_rows_f16``)."""
+    _check(load().sp_euler_step_rows_f16(latent.data_ptr(), eps_cond.data_ptr(), _ptr(eps_uncond), ld_eps, _ptr(guidance),
+                                         int(ld_guidance), out.data_ptr(), sigma, sigma_next, b, frames, h, w, _stream()),
+           "sp_euler_step_f16")
     return out
 
 

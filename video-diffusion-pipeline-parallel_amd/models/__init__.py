@@ -2,11 +2,11 @@
 
 from .dummy_unet import DummyUNet
 
-__all__ = ["DummyUNet", "StableVideoUNet"]
+__all__ = ["DummyUNet", "StableVideoUNet", "VideoConditioning"]
 
 
 def __getattr__(name):  # lazy: svd_unet pulls in the HIP binding
-    if name == "StableVideoUNet":
-        from .svd_unet import StableVideoUNet
-        return StableVideoUNet
+    if name in ("StableVideoUNet", "VideoConditioning"):
+        from . import svd_unet
+        return getattr(svd_unet, name)
     raise AttributeError(name)

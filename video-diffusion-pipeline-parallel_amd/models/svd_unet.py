@@ -20,6 +20,7 @@ from __future__ import annotations
 import math
 import os
 from collections.abc import Sequence
+from dataclasses import dataclass
 
 import torch
 import torch.nn as nn
@@ -27,6 +28,55 @@ import torch.nn as nn
 from . import euler_schedule
 from .unet_hip import SVDUNetHIP
 from .unet_spec import UNetConfig, random_state_dict
+
+
+@dataclass(frozen=True, eq=False)
+class VideoConditioning:
+    """Everything one ``StableVideoUNet.forward`` call is conditioned on (``StableVideoUNet.prepare_conditioning``).
+
+    Device tensors, prepared once and never written: ``image_embeddings`` (B,1,D) and ``image_latents`` (B,4,F,H,W)
+    fp16; ``added_time_ids`` (B,3) fp16 as the reference builds them; ``added_ids32`` their fp32 form, [3] when every
+    video has the same (fps-1, motion bucket, noise aug) triple, else [B][3]; ``guidance32`` None (no guidance), [F]
+    (one per-frame scale row for every video, ``guidance_ld`` 0) or [B][F] (one row per video, ``guidance_ld`` = F);
+    ``guidance_scale_tensor`` the same scales in fp16, (1 or B, 1, F, 1, 1);
+    ``uncond_*`` the zero conditioning of the guidance pass (None without guidance)."""
+
+    image_embeddings: torch.Tensor
+    image_latents: torch.Tensor
+    added_time_ids: torch.Tensor
+    added_ids32: torch.Tensor
+    guidance_scale: object
+    guidance32: torch.Tensor | None
+    guidance_ld: int
+    guidance_scale_tensor: torch.Tensor | None
+    uncond_embeddings: torch.Tensor | None
+    uncond_image_latents: torch.Tensor | None
+    num_frames: int
+
+    @property
+    def guided(self) -> bool:
+        return self.guidance32 is not None
+
+    @property
+    def batch(self) -> int:
+        return self.image_embeddings.shape[0]
+
+    def tensors(self) -> dict:
+        """The device tensors by field name (None where absent)."""
+        return {k: getattr(self, k) for k in ("image_embeddings", "image_latents", "added_time_ids", "added_ids32",
+                                              "guidance32", "guidance_scale_tensor", "uncond_embeddings",
+                                              "uncond_image_latents")}
+
+
+def _per_video(name: str, value, batch: int) -> list:
+    """A setting given as a scalar (every video) or as a sequence of one value per video -> list of ``batch`` values."""
+    if isinstance(value, torch.Tensor):
+        value = value.tolist() if value.dim() else value.item()
+    if isinstance(value, (list, tuple)):
+        if len(value) != batch:
+            raise ValueError(f"{name}: {len(value)} values for a batch of {batch} videos")
+        return list(value)
+    return [value] * batch
 
 
 class StableVideoUNet(nn.Module):
@@ -67,6 +117,8 @@ class StableVideoUNet(nn.Module):
         self._uncond_image_latents = None
         self._guidance_scale_tensor = None
         self._guidance32 = None
+        self._cond: VideoConditioning | None = None
+        self._graph_conds: dict = {}     # (calling stream, layout of a VideoConditioning) -> that lane's static copy
 
     # ------------------------------------------------------------------ schedule
     def _init_scheduler(self) -> None:
@@ -165,11 +217,14 @@ class StableVideoUNet(nn.Module):
         (it matters when the host is slow or the latent is small; at the benchmark shape the GPU is the bottleneck
         either way).  Graphs, their static buffers, their memory pool and the engine's per-stream scratch are all
         private to the HIP stream the caller runs on, so several videos in flight on separate streams
-        (``PipelineConfig.concurrent_samples``) never share replay state.  Conditioning changes invalidate them."""
+        (``PipelineConfig.concurrent_samples``) never share replay state.  ``set_conditioning`` invalidates them; a
+        conditioning passed per call (``forward(..., conditioning=)``) is copied into the lane's static copy of it before
+        each replay (one graph per lane, step, latent shape and conditioning layout)."""
         self._use_graphs = enabled
         if not enabled:
             self._graphs.clear()
             self._graph_lanes.clear()
+            self._graph_conds.clear()
             release = getattr(self.unet, "release_stream_state", None)
             if release is not None:
                 release()
@@ -181,6 +236,65 @@ class StableVideoUNet(nn.Module):
         return self
 
     # ------------------------------------------------------------------ conditioning
+    def prepare_conditioning(
+        self,
+        image_embeddings: torch.Tensor,
+        image_latents: torch.Tensor,
+        fps=6,
+        motion_bucket_id=127,
+        noise_aug_strength=0.02,
+        guidance_scale=None,
+        num_frames: int = 14,
+    ) -> VideoConditioning:
+        """The conditioning of one (micro-)batch of videos as an immutable object for ``forward(..., conditioning=)``.
+
+        ``fps``, ``motion_bucket_id``, ``noise_aug_strength`` and ``guidance_scale`` are each a scalar (every video) or
+        a sequence of one value per video.  Guidance of video i is ``linspace(1, g_i, num_frames)`` per frame; a batch
+        mixes no guided (g > 1) and unguided videos (ValueError), a sequence of another length than the batch is a
+        ValueError.  Videos that agree on all of them run exactly the shared-conditioning path."""
+        if image_embeddings.dim() == 2:
+            image_embeddings = image_embeddings.unsqueeze(1)
+        batch = image_embeddings.shape[0]
+        dev = self.unet.device
+        fps_v = _per_video("fps", fps, batch)
+        mb_v = _per_video("motion_bucket_id", motion_bucket_id, batch)
+        na_v = _per_video("noise_aug_strength", noise_aug_strength, batch)
+        gs_v = _per_video("guidance_scale", guidance_scale, batch)
+        guided = [g is not None and g > 1.0 for g in gs_v]
+        if any(guided) and not all(guided):
+            raise ValueError(f"guidance_scale {gs_v}: a batch cannot mix guided (> 1) and unguided videos "
+                             "(the guided ones need an unconditional pass the others do not run)")
+        rows = [[f - 1, m, a] for f, m, a in zip(fps_v, mb_v, na_v)]
+        host = torch.tensor(rows, dtype=self.dtype)
+        if bool((host == host[0]).all()):
+            # one triple for the whole batch (ref svd_unet.py:252-259 builds the rows the same way): the engine evaluates
+            # the added-time embedding once per call (M = 1); the same device work as for scalar settings
+            ids = torch.tensor(rows[:1], dtype=self.dtype, device=dev)
+            added = ids.repeat(batch, 1)
+            ids32 = ids[0].float().contiguous()
+        else:
+            added = host.to(dev)
+            ids32 = added.float().contiguous()
+        emb16 = image_embeddings.to(dev, self.dtype).contiguous()
+        lat16 = image_latents.to(dev, self.dtype).contiguous()
+        gs16 = g32 = uncond_e = uncond_l = None
+        g_ld = 0
+        if all(guided):
+            uncond_e, uncond_l = torch.zeros_like(emb16), torch.zeros_like(lat16)
+            if len(set(float(g) for g in gs_v)) == 1:
+                gs16 = torch.linspace(1.0, gs_v[0], num_frames).view(1, 1, num_frames, 1, 1).to(dev, dtype=self.dtype)
+                g32 = gs16.flatten().float().contiguous()
+            else:                                    # one row of per-frame scales per video
+                gs = torch.stack([torch.linspace(1.0, float(g), num_frames) for g in gs_v])
+                gs16 = gs.view(batch, 1, num_frames, 1, 1).to(dev, dtype=self.dtype)
+                g32 = gs16.reshape(batch, num_frames).float().contiguous()
+                g_ld = num_frames
+        return VideoConditioning(
+            image_embeddings=emb16, image_latents=lat16, added_time_ids=added, added_ids32=ids32,
+            guidance_scale=guidance_scale if not isinstance(guidance_scale, (list, torch.Tensor)) else tuple(gs_v),
+            guidance32=g32, guidance_ld=g_ld, guidance_scale_tensor=gs16, uncond_embeddings=uncond_e,
+            uncond_image_latents=uncond_l, num_frames=int(num_frames))
+
     def set_conditioning(
         self,
         image_embeddings: torch.Tensor,
@@ -191,32 +305,21 @@ class StableVideoUNet(nn.Module):
         guidance_scale: float | None = None,
         num_frames: int = 14,
     ) -> None:
-        if image_embeddings.dim() == 2:
-            image_embeddings = image_embeddings.unsqueeze(1)
-        batch = image_embeddings.shape[0]
-        dev = self.unet.device
-        ids = torch.tensor([[fps - 1, motion_bucket_id, noise_aug_strength]], dtype=self.dtype, device=dev)
-        self._added_time_ids = ids.repeat(batch, 1)
-        # every row is the same triple by construction (ref svd_unet.py:252-259 builds it the same way), so the engine
-        # evaluates the added-time embedding once per call; SVDUNetHIP.__call__ refuses rows that differ
-        self._added_ids32 = ids[0].float().contiguous()
-        self._image_embeddings = image_embeddings.to(dev, self.dtype).contiguous()
-        self._image_latents = image_latents.to(dev, self.dtype).contiguous()
+        c = self._cond = self.prepare_conditioning(image_embeddings, image_latents, fps=fps, motion_bucket_id=motion_bucket_id,
+                                                   noise_aug_strength=noise_aug_strength, guidance_scale=guidance_scale,
+                                                   num_frames=num_frames)
+        self._added_time_ids = c.added_time_ids
+        self._added_ids32 = c.added_ids32
+        self._image_embeddings = c.image_embeddings
+        self._image_latents = c.image_latents
         self._conditioning_set = True
-        self._num_frames = int(num_frames)
+        self._num_frames = c.num_frames
         self._graphs.clear()          # captured graphs hold pointers to the previous conditioning tensors
-        self._guidance_scale = guidance_scale
-        if guidance_scale is not None and guidance_scale > 1.0:
-            self._uncond_embeddings = torch.zeros_like(self._image_embeddings)
-            self._uncond_image_latents = torch.zeros_like(self._image_latents)
-            gs = torch.linspace(1.0, guidance_scale, num_frames)
-            self._guidance_scale_tensor = gs.view(1, 1, num_frames, 1, 1).to(dev, dtype=self.dtype)
-            self._guidance32 = self._guidance_scale_tensor.flatten().float().contiguous()
-        else:
-            self._uncond_embeddings = None
-            self._uncond_image_latents = None
-            self._guidance_scale_tensor = None
-            self._guidance32 = None
+        self._guidance_scale = c.guidance_scale
+        self._uncond_embeddings = c.uncond_embeddings
+        self._uncond_image_latents = c.uncond_image_latents
+        self._guidance32 = c.guidance32
+        self._guidance_scale_tensor = c.guidance_scale_tensor
 
     def set_dummy_conditioning(
         self,
@@ -246,14 +349,16 @@ class StableVideoUNet(nn.Module):
         self._uncond_image_latents = None
         self._guidance_scale_tensor = None
         self._guidance32 = None
+        self._cond = None
         self._graphs.clear()
         self._graph_lanes.clear()            # capture streams / pools are keyed by the calling stream's raw handle
+        self._graph_conds.clear()
         release = getattr(self.unet, "release_stream_state", None)
         if release is not None:
             release()
 
     # ------------------------------------------------------------------ one diffusion step
-    def _unet_pass(self, latent, image_latents, embeddings, in_scale, step, euler=None):
+    def _unet_pass(self, latent, image_latents, embeddings, in_scale, step, euler=None, added_ids32=None):
         from ..hip import ops
 
         b, _, f, h, w = latent.shape
@@ -261,53 +366,84 @@ class StableVideoUNet(nn.Module):
         ops.pack_input(latent, image_latents, rows, in_scale=in_scale, b=b, frames=f, h=h, w=w,
                        cpad=self.unet.cin_pad)
         return self.unet.forward_rows(rows, b=b, frames=f, h=h, w=w, t_value=self._t_dev[step:step + 1],
-                                      ctx16=embeddings.reshape(b, -1), added_ids32=self._added_ids32, euler=euler)
+                                      ctx16=embeddings.reshape(b, -1),
+                                      added_ids32=self._added_ids32 if added_ids32 is None else added_ids32, euler=euler)
 
     @torch.inference_mode()
-    def forward(self, latent: torch.Tensor, step: int) -> torch.Tensor:
+    def forward(self, latent: torch.Tensor, step: int, conditioning: VideoConditioning | None = None) -> torch.Tensor:
+        """One Euler step of ``latent`` (B,4,F,H,W).  ``conditioning`` (``prepare_conditioning``): what this call is
+        conditioned on; None = the model's own (``set_conditioning``)."""
         from ..hip import ops
 
-        if not self._conditioning_set:
+        cond = self._cond if conditioning is None else conditioning
+        if cond is None:
             raise RuntimeError(
                 "Conditioning not set. Call set_conditioning() or set_dummy_conditioning() before forward()."
             )
+        if not isinstance(cond, VideoConditioning):
+            raise TypeError("conditioning must be a VideoConditioning (StableVideoUNet.prepare_conditioning)")
         if not (0 <= step < len(self.timesteps)):
             raise ValueError(f"Step {step} out of range [0, {len(self.timesteps)})")
         if latent.dtype != torch.float16 or not latent.is_cuda:
             raise ValueError("latent must be a float16 tensor on the HIP device")
-        self._check_shapes(latent)
+        self._check_shapes(latent, cond)
         latent = latent.contiguous()
         if self._use_graphs:
-            return self._forward_graph(latent, step)
-        return self._forward_eager(latent, step)
+            return self._forward_graph(latent, step, conditioning)
+        return self._forward_eager(latent, step, cond)
 
-    def _check_shapes(self, latent: torch.Tensor) -> None:
+    def _check_shapes(self, latent: torch.Tensor, cond: VideoConditioning | None = None) -> None:
         """The kernels take raw pointers and the latent's (B, F, H, W): a conditioning tensor of another shape would be
         read out of bounds (the reference fails in ``torch.cat`` / on broadcast, ``svd_unet.py:385-411``)."""
+        cond = self._cond if cond is None else cond
         if latent.dim() != 5 or latent.shape[1] != 4:
             raise ValueError(f"latent must be (B, 4, F, H, W); got {tuple(latent.shape)}")
-        if tuple(self._image_latents.shape) != tuple(latent.shape):
-            raise ValueError(f"image_latents {tuple(self._image_latents.shape)} do not match the latent "
+        if tuple(cond.image_latents.shape) != tuple(latent.shape):
+            raise ValueError(f"image_latents {tuple(cond.image_latents.shape)} do not match the latent "
                              f"{tuple(latent.shape)} (set_conditioning was called for another batch / frame count / size)")
-        emb = self._image_embeddings
+        emb = cond.image_embeddings
         if emb.dim() != 3 or emb.shape[0] != latent.shape[0] or emb.shape[1] != 1 \
                 or emb.shape[2] != self.unet.cfg.cross_attention_dim:
             raise ValueError(f"image_embeddings must be (B, 1, {self.unet.cfg.cross_attention_dim}) with B = "
                              f"{latent.shape[0]}; got {tuple(emb.shape)}")
-        if self._guidance32 is not None and self._guidance32.numel() != latent.shape[2]:
-            raise ValueError(f"guidance was set for num_frames={self._guidance32.numel()}, the latent has "
-                             f"{latent.shape[2]} frames")
+        if cond.added_ids32.dim() == 2 and cond.added_ids32.shape[0] != latent.shape[0]:
+            raise ValueError(f"added time ids for {cond.added_ids32.shape[0]} videos, the latent has {latent.shape[0]}")
+        g = cond.guidance32
+        if g is not None and g.shape[-1] != latent.shape[2]:
+            raise ValueError(f"guidance was set for num_frames={g.shape[-1]}, the latent has {latent.shape[2]} frames")
+        if g is not None and g.dim() == 2 and g.shape[0] != latent.shape[0]:
+            raise ValueError(f"guidance rows for {g.shape[0]} videos, the latent has {latent.shape[0]}")
 
-    def _forward_graph(self, latent: torch.Tensor, step: int) -> torch.Tensor:
+    def _lane_conditioning(self, lane, cond: VideoConditioning):
+        """(This lane's static copy of a conditioning of ``cond``'s layout, refreshed from ``cond`` on the calling stream;
+        the layout): a graph captured on the copy reads whatever conditioning the lane's current sample has."""
+        layout = tuple((k, None if t is None else tuple(t.shape)) for k, t in cond.tensors().items()) + (cond.guidance_ld,)
+        static = self._graph_conds.get((lane, layout))
+        if static is None:
+            static = self._graph_conds[(lane, layout)] = VideoConditioning(
+                **{k: (None if t is None else t.clone()) for k, t in cond.tensors().items()},
+                guidance_scale=cond.guidance_scale, guidance_ld=cond.guidance_ld, num_frames=cond.num_frames)
+        else:
+            for k, t in cond.tensors().items():
+                if t is not None:
+                    getattr(static, k).copy_(t)
+        return static, layout
+
+    def _forward_graph(self, latent: torch.Tensor, step: int, conditioning: VideoConditioning | None = None) -> torch.Tensor:
         # Everything a replay touches is keyed by the CALLING stream (one lane of PipelineStage's interleave = one
         # stream): its own graph, static input/output, memory pool, and - because the engine keys its GroupNorm / fp8
         # scratch by the stream it is enqueued on - its own capture stream.  Two lanes replaying at once therefore
-        # share nothing but the (read-only) weights and conditioning tensors.
+        # share nothing but the (read-only) weights and conditioning tensors.  A conditioning passed per call reaches the
+        # replay through the lane's static copy of it (one per layout), written on the lane's stream before the replay.
         lane = torch.cuda.current_stream(latent.device).cuda_stream
         key = (lane, step, tuple(latent.shape))
+        cond = self._cond
+        if conditioning is not None:
+            cond, layout = self._lane_conditioning(lane, conditioning)
+            key = key + (layout,)
         entry = self._graphs.get(key)
         if entry is None:
-            self._forward_eager(latent, step)             # warm-up: lazy allocations, function attributes
+            self._forward_eager(latent, step, cond)       # warm-up: lazy allocations, function attributes
             torch.cuda.synchronize(latent.device)
             lane_state = self._graph_lanes.get(lane)
             if lane_state is None:
@@ -315,7 +451,7 @@ class StableVideoUNet(nn.Module):
             static_in = latent.clone()
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, pool=lane_state[1], stream=lane_state[0]):
-                static_out = self._forward_eager(static_in, step)
+                static_out = self._forward_eager(static_in, step, cond)
             if lane_state[1] is None:
                 lane_state[1] = graph.pool()
             entry = self._graphs[key] = (graph, static_in, static_out)
@@ -324,19 +460,21 @@ class StableVideoUNet(nn.Module):
         graph.replay()
         return static_out.clone()                          # the static buffer is overwritten by this lane's next replay
 
-    def _forward_eager(self, latent: torch.Tensor, step: int) -> torch.Tensor:
+    def _forward_eager(self, latent: torch.Tensor, step: int, cond: VideoConditioning | None = None) -> torch.Tensor:
         from ..hip import ops
 
+        cond = self._cond if cond is None else cond
         b, _, f, h, w = latent.shape
         sigma, sigma_next = self._sigma_host[step], self._sigma_host[step + 1]
         in_scale = 1.0 / math.sqrt(sigma * sigma + 1.0)
 
         eps_u = None
-        guided = self._guidance_scale is not None and self._guidance_scale > 1.0
-        if guided and self.batched_cfg:
+        ids = cond.added_ids32
+        if cond.guided and self.batched_cfg:
             both = self._unet_pass(torch.cat([latent, latent], dim=0),
-                                   torch.cat([self._uncond_image_latents, self._image_latents], dim=0),
-                                   torch.cat([self._uncond_embeddings, self._image_embeddings], dim=0), in_scale, step)
+                                   torch.cat([cond.uncond_image_latents, cond.image_latents], dim=0),
+                                   torch.cat([cond.uncond_embeddings, cond.image_embeddings], dim=0), in_scale, step,
+                                   added_ids32=ids if ids.dim() == 1 else torch.cat([ids, ids], dim=0))
             half = both.shape[0] // 2
             eps_u, eps_c = both[:half], both[half:]
         else:
@@ -344,12 +482,14 @@ class StableVideoUNet(nn.Module):
             # mix and the Euler update in its epilogue, so its eps rows never exist in HBM
             out = torch.empty_like(latent)
             tail = dict(latent=latent, out=out, sigma=sigma, sigma_next=sigma_next)
-            if guided:
-                eps_u = self._unet_pass(latent, self._uncond_image_latents, self._uncond_embeddings, in_scale, step)
-                tail.update(eps_uncond=eps_u, guidance=self._guidance32, ld_eps=eps_u.shape[1])
-            self._unet_pass(latent, self._image_latents, self._image_embeddings, in_scale, step, euler=tail)
+            if cond.guided:
+                eps_u = self._unet_pass(latent, cond.uncond_image_latents, cond.uncond_embeddings, in_scale, step,
+                                        added_ids32=ids)
+                tail.update(eps_uncond=eps_u, guidance=cond.guidance32, ld_eps=eps_u.shape[1], ld_guidance=cond.guidance_ld)
+            self._unet_pass(latent, cond.image_latents, cond.image_embeddings, in_scale, step, euler=tail, added_ids32=ids)
             return out
         out = torch.empty_like(latent)
-        ops.euler_step(latent, eps_c, eps_u, self._guidance32 if eps_u is not None else None, out,
-                       ld_eps=eps_c.shape[1], sigma=sigma, sigma_next=sigma_next, b=b, frames=f, h=h, w=w)
+        ops.euler_step(latent, eps_c, eps_u, cond.guidance32 if eps_u is not None else None, out,
+                       ld_eps=eps_c.shape[1], sigma=sigma, sigma_next=sigma_next, b=b, frames=f, h=h, w=w,
+                       ld_guidance=cond.guidance_ld)
         return out

@@ -112,7 +112,8 @@ class _Run:
     f: int
     h: int
     w: int
-    temb: torch.Tensor          # fp32 [n_temb_total] : every time_emb_proj(silu(emb)) of the net
+    temb: torch.Tensor          # fp32 [n_temb_total] : every time_emb_proj(silu(emb)) of the net; [B][n_temb_total]
+                                # when the videos of the batch have timesteps / added-time ids of their own
     ctx16: torch.Tensor         # fp16 [B][cross_dim]
     gn_ws: torch.Tensor
     sk_ws: torch.Tensor         # fp32 scratch for split-K contractions of the few-row levels (None: no such level)
@@ -507,7 +508,7 @@ class SVDUNetHIP:
         geom, _, _ = self._conv_geom(r)
         t = self._gn(r, p["n1"], x, temporal=False, silu=True, concat_sums=concat_sums)
         n1 = p["c1"].n
-        t = self._gemm(r, p["c1"], t, conv=geom, bias2=r.temb[p["te_s"]:p["te_s"] + n1], bias2_rows=r.m, gn_next=True)
+        t = self._gemm(r, p["c1"], t, conv=geom, **self._temb(r, p["te_s"], n1), gn_next=True)
         t = self._gn(r, p["n2"], t, temporal=False, silu=True)
         if p["sc"] is not None and p["c2sc"] is not None and self.fold_shortcut and r.m > self.SPLITK_MAX_ROWS \
                 and r.m % 256 == 0:
@@ -519,9 +520,17 @@ class SVDUNetHIP:
             s = self._gemm(r, p["c2"], t, conv=geom, res1=skip, r1scale=1.0, gn_next=True)
         # temporal branch + AlphaBlender: alpha*s + (1-alpha)*(s + conv2(...)) = s + (1-alpha)*conv2(...)
         t = self._gn(r, p["tn1"], s, temporal=True, silu=True)
-        t = self._gemm(r, p["tc1"], t, bias2=r.temb[p["te_t"]:p["te_t"] + p["cout"]], bias2_rows=r.m, gn_next=True)
+        t = self._gemm(r, p["tc1"], t, **self._temb(r, p["te_t"], p["cout"]), gn_next=True)
         t = self._gn(r, p["tn2"], t, temporal=True, silu=True)
         return self._gemm(r, p["tc2"], t, oscale=1.0 - p["alpha"], res1=s, r1scale=1.0, out=out, gn_next=gn_next)
+
+    @staticmethod
+    def _temb(r: _Run, off: int, n: int) -> dict:
+        """The time-embedding projection of one resnet as the contraction's ``bias2``: one row for every output row when
+        the batch shares its embedding, else one row per video (its rows at the current level)."""
+        if r.temb.dim() == 1:
+            return dict(bias2=r.temb[off:off + n], bias2_rows=r.m)
+        return dict(bias2=r.temb[:, off:off + n], bias2_rows=r.f * r.hw, ldb2=r.temb.shape[1])
 
     def _cross_vec(self, r: _Run, x):
         """to_out(to_v(ctx)) + b_out for the single context token -> fp32 [B][C] (computed by _small_gemvs)."""
@@ -648,7 +657,10 @@ class SVDUNetHIP:
     # ------------------------------------------------------------------ forward
     def forward_rows(self, x_rows, *, b, frames, h, w, t_value, ctx16, added_ids32, euler=None):
         """x_rows: fp16 [B*F*H*W][cin_pad] (see ``sp_pack_input_f16``); ``t_value``: fp32 device tensor [1]
-        (continuous timestep); ``ctx16``: fp16 [B][cross_dim]; ``added_ids32``: fp32 device [3].
+        (continuous timestep) or [B] (one per video); ``ctx16``: fp16 [B][cross_dim]; ``added_ids32``: fp32 device [3]
+        or [B][3] (one (fps-1, motion bucket, noise aug) triple per video).  A [1] timestep with [3] ids is shared by
+        the whole batch: the embedding MLPs run once (M = 1).  Otherwise they run with B rows and every resnet's
+        time-embedding row is picked per video.
         Returns eps rows fp16 [B*F*H*W][out_channels].  With ``euler`` (dict: latent, out, sigma, sigma_next and
         optionally eps_uncond + guidance + ld_eps) the last convolution's epilogue applies the guidance mix and the
         Euler update itself (ref svd_unet.py:410-439): ``euler["out"]`` receives the new latent, the
@@ -677,19 +689,27 @@ class SVDUNetHIP:
         if sk_bytes and (sk_ws is None or sk_ws.numel() < sk_bytes):
             sk_ws = self._sk_ws[skey] = torch.empty(sk_bytes, dtype=torch.uint8, device=dev)
 
-        # ---- embeddings (M = 1 GEMVs)
-        hid = torch.empty((1, 2 * temb_dim), dtype=torch.float16, device=dev)
-        tsin = torch.empty((1, c0), dtype=torch.float16, device=dev)
-        ops.sinusoid(t_value, tsin, 1, c0)
-        ops.gemv(tsin, self.te1.w, self.te1.bias, n=temb_dim, k=c0, y16=hid, ldy=2 * temb_dim, silu_out=True)
-        asin = torch.empty((1, cfg.projection_class_embeddings_input_dim), dtype=torch.float16, device=dev)
-        ops.sinusoid(added_ids32, asin, 3, cfg.addition_time_embed_dim)
-        ops.gemv(asin, self.ae1.w, self.ae1.bias, n=temb_dim, k=asin.shape[1], y16=hid[:, temb_dim:],
+        # ---- embeddings: M = 1 GEMVs when the batch shares timestep and ids, else one row per video
+        nt, nids = t_value.numel(), added_ids32.numel()
+        if nt not in (1, b) or nids not in (3, 3 * b):
+            raise ValueError(f"t_value must hold 1 or B = {b} values and added_ids32 3 or 3*B; got {nt} and {nids}")
+        rows = 1 if nt == 1 and nids == 3 else b
+        if rows > 1:
+            t_value = t_value.reshape(-1).expand(b).contiguous()
+            added_ids32 = added_ids32.reshape(-1, 3).expand(b, 3).contiguous()
+        hid = torch.empty((rows, 2 * temb_dim), dtype=torch.float16, device=dev)
+        tsin = torch.empty((rows, c0), dtype=torch.float16, device=dev)
+        ops.sinusoid(t_value, tsin, rows, c0)
+        ops.gemv(tsin, self.te1.w, self.te1.bias, n=temb_dim, k=c0, rows=rows, y16=hid, ldy=2 * temb_dim, silu_out=True)
+        asin = torch.empty((rows, cfg.projection_class_embeddings_input_dim), dtype=torch.float16, device=dev)
+        ops.sinusoid(added_ids32, asin, 3 * rows, cfg.addition_time_embed_dim)
+        ops.gemv(asin, self.ae1.w, self.ae1.bias, n=temb_dim, k=asin.shape[1], rows=rows, y16=hid[:, temb_dim:],
                  ldy=2 * temb_dim, silu_out=True)
-        emb16 = torch.empty((1, temb_dim), dtype=torch.float16, device=dev)
-        ops.gemv(hid, self.emb2_w, self.emb2_b, n=temb_dim, k=2 * temb_dim, y16=emb16)
-        temb = torch.empty(self.temb_w.shape[0], dtype=torch.float32, device=dev)
-        ops.gemv(emb16, self.temb_w, self.temb_b, n=self.temb_w.shape[0], k=temb_dim, y32=temb, silu_in=True)
+        emb16 = torch.empty((rows, temb_dim), dtype=torch.float16, device=dev)
+        ops.gemv(hid, self.emb2_w, self.emb2_b, n=temb_dim, k=2 * temb_dim, rows=rows, y16=emb16)
+        n_temb = self.temb_w.shape[0]
+        temb = torch.empty((n_temb,) if rows == 1 else (rows, n_temb), dtype=torch.float32, device=dev)
+        ops.gemv(emb16, self.temb_w, self.temb_b, n=n_temb, k=temb_dim, rows=rows, y32=temb, silu_in=True)
 
         r = _Run(b=b, f=frames, h=h, w=w, temb=temb, ctx16=ctx16, gn_ws=gn_ws, sk_ws=sk_ws,
                  frame_ids=torch.arange(frames, dtype=torch.float32, device=dev))
@@ -769,28 +789,36 @@ class SVDUNetHIP:
         return self._gemm(r, self.conv_out, x, conv=geom)
 
     # diffusers-style call (sample (B,F,8,H,W)) – used by parity tests and as a drop-in `unet`
-    def __call__(self, sample, timestep, encoder_hidden_states, added_time_ids, return_dict=False):
+    def __call__(self, sample, timestep, encoder_hidden_states, added_time_ids, return_dict=False, per_video=False):
+        """``per_video=True``: a (B,) timestep and (B, 3) ``added_time_ids`` may differ from video to video (as diffusers'
+        ``UNetSpatioTemporalConditionModel`` takes them).  Without it the call takes ONE timestep and ONE triple and
+        refuses rows that differ."""
         b, f, c, h, w = sample.shape
         dev = self.device
         rows = torch.zeros((b * f * h * w, self.cin_pad), dtype=torch.float16, device=dev)
         rows[:, :c] = sample.to(dev, torch.float16).permute(0, 1, 3, 4, 2).reshape(-1, c)
-        # ONE timestep and ONE (fps-1, motion bucket, noise aug) triple per call: the embedding MLPs run once and their
-        # result is shared by every video of the batch (what the reference adapter feeds, svd_unet.py:252-259,389-392:
-        # a scalar timestep and `added_time_ids.repeat(batch, 1)`).  Per-video values would be silently ignored -> refuse.
+        # By default ONE timestep and ONE (fps-1, motion bucket, noise aug) triple per call: the embedding MLPs run once and
+        # their result is shared by every video of the batch (what the reference adapter feeds, svd_unet.py:252-259,389-392:
+        # a scalar timestep and `added_time_ids.repeat(batch, 1)`).  Per-video values without per_video=True -> refuse.
         t = torch.as_tensor(timestep, dtype=torch.float32).reshape(-1)
-        if t.numel() not in (1, b) or (t.numel() > 1 and bool((t != t[0]).any())):
-            raise ValueError("SVDUNetHIP takes one timestep per call (a scalar, or B equal values)")
+        t_differ = t.numel() > 1 and bool((t != t[0]).any())
+        if t.numel() not in (1, b) or (t_differ and not per_video):
+            raise ValueError("SVDUNetHIP takes one timestep per call (a scalar, or B equal values; per_video=True for "
+                             "one per video)")
         ids = added_time_ids.to(torch.float32).reshape(-1, 3) if added_time_ids.numel() % 3 == 0 else None
         if ids is None or ids.shape[0] not in (1, b):
             raise ValueError(f"added_time_ids must be (B, 3) or (1, 3); got {tuple(added_time_ids.shape)}")
-        if ids.shape[0] > 1 and bool((ids != ids[0]).any()):
+        ids_differ = ids.shape[0] > 1 and bool((ids != ids[0]).any())
+        if ids_differ and not per_video:
             raise ValueError("SVDUNetHIP shares the added-time embedding across the batch: the rows of added_time_ids "
-                             "differ (run videos with different fps / motion bucket / noise augmentation in separate calls)")
+                             "differ (run videos with different fps / motion bucket / noise augmentation in separate calls, "
+                             "or pass per_video=True)")
         if encoder_hidden_states.shape[0] != b or encoder_hidden_states[0].numel() != self.cfg.cross_attention_dim:
             raise ValueError(f"encoder_hidden_states must be (B, 1, {self.cfg.cross_attention_dim}) with B = {b}; got "
                              f"{tuple(encoder_hidden_states.shape)}")
-        eps = self.forward_rows(rows, b=b, frames=f, h=h, w=w, t_value=t[:1].to(dev),
+        eps = self.forward_rows(rows, b=b, frames=f, h=h, w=w,
+                                t_value=(t if t_differ else t[:1]).to(dev).contiguous(),
                                 ctx16=encoder_hidden_states.to(dev, torch.float16).reshape(b, -1).contiguous(),
-                                added_ids32=ids[0].to(dev).contiguous())
+                                added_ids32=(ids if ids_differ else ids[0]).to(dev).contiguous())
         out = eps.reshape(b, f, h, w, -1).permute(0, 1, 4, 2, 3).contiguous()
         return (out,)

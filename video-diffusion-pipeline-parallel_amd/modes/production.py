@@ -30,6 +30,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--motion-bucket-id", type=int, default=127)
     p.add_argument("--noise-aug-strength", type=float, default=0.02)
     p.add_argument("--guidance-scale", type=float, default=None)
+    p.add_argument("--sample-motion-buckets", type=int, nargs="+", default=None, metavar="B",
+                   help="per-sample conditioning: sample i gets its own dummy image conditioning (seeded by seed + i) "
+                        "with motion bucket B[i %% len(B)]")
     p.add_argument("--model-id", type=str, default="stabilityai/stable-video-diffusion-img2vid-xt")
     p.add_argument("--random-init", action="store_true")
     p.add_argument("--balanced", action="store_true")
@@ -67,12 +70,26 @@ def main(argv=None) -> None:
         torch.manual_seed(args.seed + i)
         return torch.randn(shape, device=device, dtype=torch.float16) * model.init_noise_sigma
 
+    conditioning_supplier = None
+    if args.sample_motion_buckets:
+        buckets = list(args.sample_motion_buckets)
+
+        def conditioning_supplier(i: int):
+            # made on every rank that steps sample i, identically (own generator: the latent supplier's seeding is untouched)
+            g = torch.Generator(device=device).manual_seed(args.seed + i)
+            emb = torch.randn((1, 1, model.unet.cfg.cross_attention_dim), generator=g, device=device, dtype=torch.float16)
+            img = torch.randn(shape, generator=g, device=device, dtype=torch.float16)
+            return model.prepare_conditioning(emb, img, fps=args.fps, motion_bucket_id=buckets[i % len(buckets)],
+                                              noise_aug_strength=args.noise_aug_strength,
+                                              guidance_scale=args.guidance_scale, num_frames=args.latent_frames)
+
     try:
         with torch.no_grad():
             outs = run_pipeline_latents(model, total_steps=args.total_steps,
                                         timesteps=list(range(args.total_steps - 1, -1, -1)), world_size=world,
                                         rank=rank, latent_spec=spec, num_samples=args.num_samples,
-                                        input_supplier=supplier if rank == 0 else None, balanced=args.balanced)
+                                        input_supplier=supplier if rank == 0 else None, balanced=args.balanced,
+                                        conditioning_supplier=conditioning_supplier)
         if outs:
             torch.cuda.synchronize(device)
             for i, o in enumerate(outs):

@@ -1,6 +1,7 @@
 """Step assignment + stage executor (mirror of ``/root/reference/src/pipeline/__init__.py:1-11``)."""
 
 from .pipeline import (
+    ConditioningSupplier,
     InputSupplier,
     LatentSpec,
     PipelineConfig,
@@ -20,6 +21,7 @@ __all__ = [
     "PipelineStage",
     "PipelineConfig",
     "InputSupplier",
+    "ConditioningSupplier",
     "run_single_latent",
     "run_pipeline_latents",
 ]

@@ -39,10 +39,18 @@ sample index (``assign_steps_rotating``), so no stage is a permanent bottleneck.
 the chain of stages into a ring: sample ``i`` starts on rank ``i mod N`` and visits ranks ``i, i+1, ...`` (mod N) for
 stages ``0 .. N-1``, so every rank computes from the first moment (no pipeline fill or drain bubble) and every rank
 runs every stage once per N samples (perfectly balanced for any split); see ``PipelineStage._run_many_ring``.
+
+Per-sample conditioning (extension): ``run_many(..., conditioning_supplier=f)`` calls ``f(sample_idx)`` on every rank
+that steps sample ``i``, once, before that sample's first local step there, and runs its steps as
+``model(latent, step, conditioning=f(i))``.  The conditioning is produced where it is used and never sent: the
+hand-off messages are exactly those of a run without a supplier (an extra message would change the per-pair order that
+RCCL relies on, see ``models/edge_stages.py::FrameEmitter``), so ``f`` must be given on every rank and be deterministic
+in ``sample_idx``.
 """
 
 from __future__ import annotations
 
+import inspect
 import logging
 import os
 import time
@@ -93,6 +101,7 @@ class PipelineConfig:
 
 
 InputSupplier = Callable[[int], torch.Tensor]
+ConditioningSupplier = Callable[[int], object]
 
 
 class _NullCtx:
@@ -276,8 +285,28 @@ class PipelineStage:
             raise RuntimeError("Local timestep slice length mismatch with step range.")
         return owned
 
-    def _run_local_steps(self, latent: torch.Tensor, sample_idx: int | None = None) -> torch.Tensor:
+    def _check_conditioning_model(self) -> None:
+        """A conditioning supplier needs a model whose forward takes ``conditioning=`` (checked before any hand-off)."""
+        fn = getattr(self.model, "forward", self.model)
+        try:
+            params = inspect.signature(fn).parameters
+        except (TypeError, ValueError):
+            params = {}
+        if "conditioning" not in params and not any(p.kind == p.VAR_KEYWORD for p in params.values()):
+            raise ValueError(f"conditioning_supplier given, but {type(self.model).__name__}.forward takes no "
+                             "`conditioning` argument")
+
+    def _step(self, latent: torch.Tensor, step, conditioning=None, supplied: bool = False) -> torch.Tensor:
+        # without a supplier the model is called exactly as the reference calls it (the timestep VALUE, ref :95)
+        if supplied:
+            return self.model(latent, step, conditioning=conditioning)
+        return self.model(latent, step)
+
+    def _run_local_steps(self, latent: torch.Tensor, sample_idx: int | None = None,
+                         conditioning_supplier: ConditioningSupplier | None = None) -> torch.Tensor:
         owned = self._owned_timesteps(sample_idx)
+        supplied = conditioning_supplier is not None and len(owned) > 0
+        cond = conditioning_supplier(sample_idx) if supplied else None
 
         verbose = self.logger.isEnabledFor(logging.INFO)
         for pos, step in enumerate(owned):
@@ -285,7 +314,7 @@ class PipelineStage:
                     and self._more_samples_expected and self._link.posted == 0 and not self._link.post_after_send):
                 self._link.post_recv()      # next sample's receive: resident no earlier than this last step
             began = time.time()
-            latent = self.model(latent, step)  # the timestep VALUE is the argument (ref :95)
+            latent = self._step(latent, step, cond, supplied)  # the timestep VALUE is the argument (ref :95)
             if verbose:
                 self._log(f"step {step} completed in {(time.time() - began) * 1000.0:.2f} ms")
         return latent
@@ -304,17 +333,23 @@ class PipelineStage:
         num_samples: int,
         *,
         input_supplier: InputSupplier | None = None,
+        conditioning_supplier: ConditioningSupplier | None = None,
     ) -> list[torch.Tensor] | None:
+        """``conditioning_supplier(sample_idx)``: what sample ``sample_idx``'s steps pass as ``model(..., conditioning=)``
+        (see the module docstring); every rank must give one, deterministic in ``sample_idx``.  None: ``model(latent,
+        step)``."""
         if num_samples <= 0:
             raise ValueError("num_samples must be positive for pipeline execution")
+        if conditioning_supplier is not None:
+            self._check_conditioning_model()
         if self.config.ring and self.config.world_size > 1:
-            return self._run_many_ring(num_samples, input_supplier)
+            return self._run_many_ring(num_samples, input_supplier, conditioning_supplier)
         first_rank = self.config.rank == 0
         if first_rank and input_supplier is None:
             raise ValueError("rank 0 requires an input_supplier when processing multiple samples")
 
         if self.config.concurrent_samples > 1 and self.config.latent_spec.device.type == "cuda":
-            return self._run_many_interleaved(num_samples, input_supplier)
+            return self._run_many_interleaved(num_samples, input_supplier, conditioning_supplier)
 
         finished: list[torch.Tensor] = []
         for sample_idx in range(num_samples):
@@ -322,13 +357,15 @@ class PipelineStage:
             result = self._process_single_latent(
                 input_supplier(sample_idx) if first_rank else None,
                 sample_idx=sample_idx,
+                conditioning_supplier=conditioning_supplier,
             )
             if result is not None:
                 finished.append(result)
         self._more_samples_expected = False
         return finished or None
 
-    def _run_many_interleaved(self, num_samples: int, input_supplier) -> list[torch.Tensor] | None:
+    def _run_many_interleaved(self, num_samples: int, input_supplier,
+                              conditioning_supplier=None) -> list[torch.Tensor] | None:
         """``concurrent_samples`` latents at a time, one HIP stream each, their UNet steps issued round-robin.
 
         A single video leaves CUs idle (tail rounds of tiles, HBM-bound norm kernels next to MFMA-bound GEMMs);
@@ -360,6 +397,11 @@ class PipelineStage:
                         self._more_samples_expected = False
                         latents.append(self._recv_latent())
             owned = [self._owned_timesteps(idx) for idx in group]
+            supplied = [conditioning_supplier is not None and len(o) > 0 for o in owned]
+            conds = []
+            for j, idx in enumerate(group):
+                with torch.cuda.stream(self._streams[j]):      # made on the lane that reads it
+                    conds.append(conditioning_supplier(idx) if supplied[j] else None)
             rounds = max(len(o) for o in owned)
             for k in range(rounds):
                 if k == rounds - 1 and not first and self._link is not None and not self._link.post_after_send:
@@ -369,7 +411,7 @@ class PipelineStage:
                 for j in range(len(group)):
                     if k < len(owned[j]):
                         with torch.cuda.stream(self._streams[j]):
-                            latents[j] = self.model(latents[j], owned[j][k])
+                            latents[j] = self._step(latents[j], owned[j][k], conds[j], supplied[j])
             for j in range(len(group)):
                 with torch.cuda.stream(self._streams[j]):
                     if last:
@@ -383,6 +425,7 @@ class PipelineStage:
                 if last:
                     latents[j].record_stream(main)
                     main.wait_stream(self._streams[j])
+            del conds                                   # the group's samples have left this rank
             if not first and self._link is not None and self._link.post_after_send:
                 with torch.cuda.stream(self._streams[0]):
                     for _ in range(following):
@@ -393,7 +436,7 @@ class PipelineStage:
             self._log(f"samples {group[0]}..{group[-1]} issued on {len(group)} streams")
         return finished or None
 
-    def _run_many_ring(self, num_samples: int, input_supplier) -> list[torch.Tensor] | None:
+    def _run_many_ring(self, num_samples: int, input_supplier, conditioning_supplier=None) -> list[torch.Tensor] | None:
         """Ring schedule (extension).  Samples are taken in batches of N = world_size; in slot ``s`` of a batch this
         rank runs stage ``s`` (the ``s``-th range of the balanced split) of the sample whose home rank is
         ``(rank - s) mod N``, then hands it to rank+1 and receives its slot ``s+1`` sample from rank-1.  In every slot
@@ -493,10 +536,16 @@ class PipelineStage:
                 steps = list(cfg.timesteps[starts[s]: starts[s] + sizes[s]])
                 if len(steps) != sizes[s]:
                     raise RuntimeError("Local timestep slice length mismatch with step range.")
+                supplied = conditioning_supplier is not None and len(steps) > 0
+                conds = {}
+                for j in live:                                    # the slot's samples, conditioned on this rank
+                    with on(j):
+                        conds[j] = conditioning_supplier(vid[j]) if supplied else None
                 for step in steps:                                # round-robin over the interleaved samples
                     for j in live:
                         with on(j):
-                            cur[j] = self.model(cur[j], step)
+                            cur[j] = self._step(cur[j], step, conds[j], supplied)
+                del conds                                         # they leave this rank after the slot
                 if s == n - 1:
                     for j in live:
                         finished[vid[j]] = cur.pop(j)
@@ -549,7 +598,7 @@ class PipelineStage:
         return [have[i] for i in range(num_samples)] if r == last else None
 
     def _process_single_latent(
-        self, input_latent: torch.Tensor | None, sample_idx: int | None
+        self, input_latent: torch.Tensor | None, sample_idx: int | None, conditioning_supplier=None
     ) -> torch.Tensor | None:
         label = "" if sample_idx is None else f"sample {sample_idx} "
         cfg = self.config
@@ -565,7 +614,7 @@ class PipelineStage:
             latent = self._recv_latent()
             self._log(f"{label}received latent")
 
-        latent = self._run_local_steps(latent, sample_idx)
+        latent = self._run_local_steps(latent, sample_idx, conditioning_supplier)
 
         if cfg.rank == cfg.world_size - 1:
             self._log(f"{label}final rank completed")
@@ -650,9 +699,11 @@ def run_pipeline_latents(
     input_supplier: InputSupplier | None,
     logger: logging.Logger | None = None,
     balanced: bool = False,
+    conditioning_supplier: ConditioningSupplier | None = None,
 ) -> list[torch.Tensor] | None:
+    """``conditioning_supplier``: see ``PipelineStage.run_many`` (given on every rank, or on none)."""
     stage = _make_stage(model, total_steps=total_steps, timesteps=timesteps, world_size=world_size,
                         rank=rank, latent_spec=latent_spec, logger=logger, balanced=balanced)
-    out = stage.run_many(num_samples, input_supplier=input_supplier)
+    out = stage.run_many(num_samples, input_supplier=input_supplier, conditioning_supplier=conditioning_supplier)
     stage.drain()
     return out
