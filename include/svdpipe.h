@@ -53,7 +53,7 @@ enum { SP_A_LINEAR = 0, SP_A_CONV3X3 = 1, SP_A_TEMPORAL3 = 2 };
 typedef struct sp_gemm_desc {
   /* A operand */
   const void *a;        /* fp16 [rows_in][lda] */
-  int64_t lda;          /* elements between consecutive A rows (>= cin) */
+  int64_t lda;          /* elements between consecutive A rows (>= cin, a multiple of 8) */
   int mode;             /* SP_A_* */
   int cin;              /* channels per tap (multiple of 64); K = taps*cin */
   /* geometry for SP_A_CONV3X3: input images [n_img][hin][win], output [n_img][hout][wout];
@@ -69,19 +69,26 @@ typedef struct sp_gemm_desc {
      (bias applies before gelu; oscale/res are applied to the product) */
   const float *bias;    /* [n] or NULL */
   const float *bias2;   /* [nb][ldb2] or NULL */
-  int64_t bias2_rows;   /* rows of D sharing one bias2 row (e.g. frames*H*W of a batch item) */
-  int64_t ldb2;         /* floats between bias2 rows (0 = n) */
-  const void *res1; int64_t ldr1; float r1scale;   /* fp16 [m][ldr1] or NULL */
-  const void *res2; int64_t ldr2; float r2scale;
+  int64_t bias2_rows;   /* rows of D sharing one bias2 row (e.g. frames*H*W of a batch item); 0 = one row for all m */
+  int64_t ldb2;         /* floats between bias2 rows: 0 (= n), or >= n and a multiple of 4 */
+  const void *res1; int64_t ldr1; float r1scale;   /* fp16 [m][ldr1] or NULL; ldr1 >= stored columns, a multiple of 8 */
+  const void *res2; int64_t ldr2; float r2scale;   /* the same */
   float oscale;
-  int geglu;
-  int n_store;          /* number of leading output columns actually stored (<= Nout); 0 = all */
-  void *d; int64_t ldd; /* fp16 [m][ldd] */
+  int geglu;            /* needs n a multiple of 128 */
+  int n_store;          /* number of leading output columns actually stored (0 <= n_store <= Nout); 0 = all */
+  void *d; int64_t ldd; /* fp16 [m][ldd]; ldd >= stored columns (n_store, or Nout), a multiple of 8 -- with 0 < n_store < 8
+                           any such pitch (conv_out stores rows of 4) */
   const void *zero_page;
+  /* Every rule of this descriptor is checked before anything is launched (SP_EINVAL, sp_last_error() names the field):
+     a, w, d, zero_page non-NULL; m, n > 0; the multiples and minimum row pitches above; SP_A_CONV3X3: stride 1 or 2,
+     positive geometry, hout / wout = ((hin / win, doubled with upsample2x) + 2 - 3) / stride + 1, m == n_img*hout*wout;
+     SP_A_TEMPORAL3: frames, hw > 0, m a multiple of frames*hw.  Buffers are not known to the library: a, w, d, res1, res2 and
+     a2 must be 16-byte aligned (d with 0 < n_store < 8: 2-byte), bias / bias2 / ln_colsum 16-byte aligned. */
   /* LayerNorm folded into this contraction (SP_A_LINEAR only, bias2 must be NULL): with W pre-multiplied by the norm's
      gamma, LN(x).W^T + b = rstd[m]*(x.W'^T - mean[m]*ln_colsum[n]) + bias[n], so the normalised tensor is never
      written: ln_stats = fp32 [m][2] (mean, rstd) from sp_ln_stats_f16, ln_colsum[n] = sum_k W'[n][k] (of the fp16
-     values), bias[n] = W.beta + b.  NULL = no fold. */
+     values), bias[n] = W.beta + b.  NULL = no fold; ln_stats and ln_colsum come together (one without the other is
+     refused). */
   const float *ln_stats;
   const float *ln_colsum;
   /* Guidance mix + Euler update folded into the epilogue of the UNet's last convolution (conv_out: n = 64 padded
@@ -89,7 +96,10 @@ typedef struct sp_gemm_desc {
      storing eps rows in d, row m = (b, f, pixel) updates the four latent channels
        eps = euler_eps_uncond ? u + g[f]*(eps - u) (evaluated in fp16 like the reference) : eps
        x0 = eps*(-sigma/sqrt(sigma^2+1)) + x/(sigma^2+1);  x' = x + (x - x0)/sigma*(sigma_next - sigma)   (fp32)
-     with x read from euler_latent and x' written to euler_out, both fp16 (B,4,F,H,W); d is not written. */
+     with x read from euler_latent and x' written to euler_out, both fp16 (B,4,F,H,W); d is not written.
+     Needs euler_latent, n == 64, n_store == 4, no geglu, no residuals, oscale == 1, euler_frames, euler_hw > 0, m a multiple
+     of euler_frames*euler_hw, euler_sigma > 0; with euler_eps_uncond also euler_guidance and euler_ld_eps >= 4, a multiple
+     of 4. */
   const void *euler_latent; void *euler_out;
   const void *euler_eps_uncond; int64_t euler_ld_eps;   /* fp16 [m][euler_ld_eps] eps rows of the unconditional pass, or NULL */
   const float *euler_guidance;                         /* fp32 [frames] per-frame guidance scale (with euler_eps_uncond) */
@@ -110,8 +120,11 @@ typedef struct sp_gemm_desc {
   /* Per-row-group weights (SP_A_LINEAR only): with w_group_rows > 0, output rows [g*w_group_rows, (g+1)*w_group_rows)
      are multiplied with the weight matrix at w + g*w_group_stride halves instead of w (what a GroupNorm folded into the
      linear layer behind it needs: one scaled copy of the weights per frame, sp_groupnorm_fold_linear_f16; combine with a
-     bias2 row per group).  w_group_rows must be a multiple of 128 (no tile may straddle two groups); the call runs on the
-     ping-pong kernels (no split-K).  0 = one weight matrix for every row. */
+     bias2 row per group).  w_group_rows must be a multiple of 128 AND of the height of the tiles the call runs on (no
+     tile may straddle two groups): a multiple of 256 with gn_part (256-row tiles), of 256 or 192 with ln_out, and where it
+     is a multiple of neither 256 nor 192 (128-row tiles) n must be a multiple of 256.  w_group_stride > 0, a multiple of 8;
+     n a multiple of 256 or 320; no geglu / folded LayerNorm / Euler tail; the call runs on the ping-pong kernels (no
+     split-K).  0 = one weight matrix for every row. */
   int64_t w_group_rows; int64_t w_group_stride;
   /* GroupNorm statistics of the NEXT norm out of this contraction's epilogue (round 5): gn_part = fp32
      [m/256][2][n][2] -- for every 256-row tile, each of its two 128-row halves and every output column, (sum, sum of
@@ -120,14 +133,15 @@ typedef struct sp_gemm_desc {
      sp_groupnorm_tile_sums_f16 folds them into the (mean, rstd) of any instance that is a whole number of tiles and
      normalises d without a statistics pass over it.  Needs m a multiple of 256, n a multiple of 256 or 320, no geglu /
      folded LayerNorm / ln_out / n_store / Euler tail; the call runs on the 256-row ping-pong tiles.  Sums
-     are folded in a fixed order (bit-reproducible).  NULL = off. */
+     are folded in a fixed order (bit-reproducible).  16-byte aligned.  NULL = off. */
   float *gn_part;
   /* Extra LINEAR tap (round 5): behind the taps of `mode` the contraction runs on over cin2 channels of a SECOND tensor a2
      (fp16 [m][lda2], row i for output row i), multiplied with weight columns [taps*cin, taps*cin + cin2): w is then
      [n][taps*cin + cin2].  A resnet's 1x1 shortcut convolution folded into its second 3x3 convolution
      (conv2(h) + conv_shortcut(x) = one contraction with bias = b2 + b_sc): the skip tensor is neither written nor read.
      cin2 a multiple of 64; runs on the 256-row ping-pong tiles (n a multiple of 256 or 320; no geglu / folded LayerNorm /
-     ln_out / n_store / Euler tail / per-group weights / split-K).  NULL = off. */
+     ln_out / n_store / Euler tail / per-group weights / split-K; together with gn_part only without residuals).  lda2 >=
+     cin2, a multiple of 8.  NULL = off. */
   const void *a2; int64_t lda2; int cin2;
   /* Guidance rows of the Euler tail: with euler_eps_uncond, video b of the batch mixes with
      euler_guidance[b * euler_guidance_ld + f] (fp32 [B][euler_guidance_ld], one row of per-frame scales per video;
@@ -150,7 +164,9 @@ const char *sp_gemm_last_kernel(void);
  * shapes that family supports; everything else keeps the automatic choice.  Process-wide, not thread-safe: set it
  * before the calls it should affect.  route 0 = automatic (default), 1 = small tiles only, 2 = ping-pong large tiles
  * (bm in {0,128,192,256}, bn in {0,256,320}; 0 = automatic), 3 = persistent-stream tiles (bm in {0,192,256},
- * bn in {0,256}), 4 = split-K whenever a workspace is given (also for short K). */
+ * bn in {0,256}), 4 = split-K whenever a workspace is given (also for short K).
+ * gn_part, a2, ln_out and w_group_rows override a forced route: those calls run on the ping-pong tiles their comments name,
+ * whatever route is set. */
 int sp_gemm_set_route(int route, int bm, int bn);
 
 /* y[n] = act_out( W[n][:] . act_in(x) + b[n] ), M = 1.  Replaces the nn.Linear GEMVs of the

@@ -1,0 +1,204 @@
+"""Randomised cross-check of sp_gemm_f16 over the WHOLE descriptor (tests/gemm_model.py draws it, legal draws only): every
+leading dimension with slack, operands as column slices whose slack is NaN, temporal batches, every option in combination, on
+every forced route.  Per draw:
+
+* every output the call owns (d, ln_out, gn_part, euler_out, workspace) lies inside a sentinel-filled buffer: guard rows,
+  guard columns between the stored columns and ldd, guard words behind the side outputs; with the Euler tail d is untouched;
+* no NaN (the slack of A, residuals, bias2, a2, the weight groups) reaches an output;
+* d against the fp64 reference by the global relative L2 error AND by the worst 64 x 64 block, both at the fuzz tolerance of
+  3e-3 (fp16 storage, fp32 accumulation; tools/fuzz_gemm.py) -- an exact kernel with fp16 stores reads <= 3.4e-4 on both
+  (tests/test_gemm_descriptor_cpu.py::test_generator_coverage_and_rounding_floor);
+* side outputs with the tolerances of their dedicated tests in tests/test_kernels_gpu.py: ln_out as the (mean, rstd) of the
+  STORED row (atol 2e-4 / rtol 2e-4, test_gemm_output_row_layernorm_statistics), gn_part against the reference's fp32-side
+  sums (2e-3 / 3e-3 of the largest, test_groupnorm_statistics_from_the_producing_contraction) or, with residuals, against
+  the sums of the stored values (1e-5), the Euler tail at l2 1e-3 / max 2e-3 (2e-3 / 4e-3 with guidance,
+  test_pack_input_and_euler);
+* the call repeated into fresh buffers is bit-identical (fixed-order sums).
+
+A failing draw is replayed alone with ``tools/fuzz_gemm.py --descriptor ROUTE BM INDEX``."""
+import ctypes
+import os
+import sys
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import gemm_model as M  # noqa: E402
+
+DEV = "cuda"
+GUARD = 3
+SENTINEL, WS_SENTINEL = 7.0, 123.0
+
+
+def family(route, bm):
+    """Prefix of sp_gemm_last_kernel() for the kernel family a forced route pins (route 3 pins the persistent kernels, whose
+    256- or 192-row tile is the dispatcher's pick; bm 128 / -192 pin their 128 x 320 / 256 x 192 tiles)."""
+    if route == 1:
+        return "gemm_f16_kernel"
+    if route == 2:
+        return f"gemm_pp_kernel<{bm},"
+    if route == 3:
+        return {128: "gemm_ps_kernel<128, 320", -192: "gemm_ps_kernel<256, 192"}.get(bm, "gemm_ps_kernel<")
+    return ""
+
+
+def _upload(bufs, views):
+    dev, ptr = {}, {}
+    for k, b in bufs.items():
+        dev[k] = b.to(DEV)
+        same = views[k].untyped_storage().data_ptr() == b.untyped_storage().data_ptr()
+        ptr[k] = dev[k].data_ptr() + ((views[k].data_ptr() - b.data_ptr()) if same else 0)
+    return dev, ptr
+
+
+def _outputs(d, lib):
+    """Fresh sentinel-filled output buffers and the pointers into them."""
+    m, ldd, off = d["m"], d["ldd"], d["_off"]["d"]
+    out = {"d": torch.full(((m + 2 * GUARD) * ldd + 64,), SENTINEL, dtype=torch.float16, device=DEV)}
+    ptr = {"d": out["d"].data_ptr() + 2 * (GUARD * ldd + off)}
+    if d["ln_out"]:
+        out["ln_out"] = torch.full((m * 2 + 64,), SENTINEL, dtype=torch.float32, device=DEV)
+    if d["gn_part"]:
+        out["gn_part"] = torch.full((m // 256 * 2 * d["n"] * 2 + 64,), SENTINEL, dtype=torch.float32, device=DEV)
+    if d["euler_out"]:
+        out["euler_out"] = torch.full((m * 4 + 64,), SENTINEL, dtype=torch.float16, device=DEV)
+    if d["workspace"]:
+        out["workspace"] = torch.full((d["workspace_bytes"] // 4 + 64,), WS_SENTINEL, dtype=torch.float32, device=DEV)
+    for k in ("ln_out", "gn_part", "euler_out", "workspace"):
+        if k in out:
+            ptr[k] = out[k].data_ptr()
+    return out, ptr
+
+
+def run_draw(d, lib, zero_page):
+    """Runs one legal draw twice and checks everything listed in the module docstring; returns (global, worst block, kernel)."""
+    d = dict(d)
+    assert M.legal(d) == (True, None)
+    bufs, views = M.make_tensors(d)
+    ref = M.reference(d, views)
+    if d["workspace"]:                               # what a caller sizes it with (split-K slabs), at least the ln_out sums
+        need = int(lib.sp_gemm_workspace_bytes(ctypes.byref(M.to_struct(d))))
+        d["workspace_bytes"] = max(d["workspace_bytes"], need)
+    dev, in_ptr = _upload(bufs, views)
+    in_ptr["zero_page"] = zero_page.data_ptr()
+    what = {k: v for k, v in d.items() if v and not k.startswith("_") and k not in M.POINTERS}
+    what["options"] = sorted(M.options_of(d))
+    assert all(k in in_ptr or k in ("d", "ln_out", "gn_part", "euler_out", "workspace") for k in M.POINTERS if d[k]), \
+        "every pointer of the descriptor must address a real buffer"
+    runs = []
+    for _ in range(2):
+        out, out_ptr = _outputs(d, lib)
+        rc = lib.sp_gemm_f16(ctypes.byref(M.to_struct(d, {**in_ptr, **out_ptr})), torch.cuda.current_stream().cuda_stream)
+        assert rc == 0, f"{lib.sp_last_error().decode()}: {what}"
+        kernel = lib.sp_gemm_last_kernel().decode()
+        torch.cuda.synchronize()
+        runs.append({k: v.cpu() for k, v in out.items()})
+    got, again = runs
+    for k in got:
+        if k != "workspace":
+            assert torch.equal(got[k].view(torch.int16 if got[k].dtype == torch.float16 else torch.int32),
+                               again[k].view(torch.int16 if got[k].dtype == torch.float16 else torch.int32)), \
+                f"{k} differs between two identical calls ({kernel}): {what}"
+    m, ldd, off, st = d["m"], d["ldd"], d["_off"]["d"], M.stored(d)
+    # ---- guards
+    buf = got["d"][:(m + 2 * GUARD) * ldd].reshape(m + 2 * GUARD, ldd).float()
+    assert torch.all(got["d"][(m + 2 * GUARD) * ldd:] == SENTINEL), f"d: words behind the buffer written ({kernel}): {what}"
+    assert torch.all(buf[:GUARD] == SENTINEL) and torch.all(buf[GUARD + m:] == SENTINEL), f"d: guard rows written ({kernel}): {what}"
+    rows = buf[GUARD:GUARD + m]
+    if d["euler_out"]:
+        assert torch.all(rows == SENTINEL), f"the Euler tail wrote d ({kernel}): {what}"
+    else:
+        assert torch.all(rows[:, :off] == SENTINEL) and torch.all(rows[:, off + st:] == SENTINEL), \
+            f"d: columns outside the {st} stored ones written ({kernel}): {what}"
+    sizes = dict(ln_out=m * 2, gn_part=m // 256 * 2 * d["n"] * 2, euler_out=m * 4)
+    for k, size in sizes.items():
+        if k in got:
+            assert torch.all(got[k][size:] == SENTINEL), f"{k}: words behind the buffer written ({kernel}): {what}"
+            assert torch.isfinite(got[k][:size].float()).all(), f"{k}: NaN / inf ({kernel}): {what}"
+    if "workspace" in got:
+        assert torch.all(got["workspace"][d["workspace_bytes"] // 4:] == WS_SENTINEL), f"workspace overrun ({kernel}): {what}"
+    # ---- d
+    e = (0.0, 0.0)
+    stored = rows[:, off:off + st]
+    if not d["euler_out"]:
+        assert torch.isfinite(stored).all(), f"NaN / inf in d: a slack column or a neighbouring row was read ({kernel}): {what}"
+        e = M.errors(stored, ref["d"])
+        assert e[0] <= M.TOL and e[1] <= M.TOL, f"global rel_l2={e[0]:.3e} worst 64x64 block={e[1]:.3e} ({kernel}): {what}"
+    # ---- side outputs
+    if d["ln_out"]:
+        want = M.row_stats(stored.half(), d["ln_out_eps"]).float()
+        have = got["ln_out"][:m * 2].reshape(m, 2)
+        assert torch.allclose(have[:, 0], want[:, 0], rtol=0, atol=2e-4) and torch.allclose(have[:, 1], want[:, 1], rtol=2e-4), \
+            f"ln_out: mean off by {float((have[:, 0] - want[:, 0]).abs().max()):.2e}, rstd by (rel) " \
+            f"{float(((have[:, 1] - want[:, 1]) / want[:, 1]).abs().max()):.2e} ({kernel}): {what}"
+    if d["gn_part"]:
+        have = got["gn_part"][:sizes["gn_part"]].double().reshape(m // 256, 2, d["n"], 2)
+        if d["res1"] or d["res2"]:
+            v = stored.double().reshape(m // 128, 128, d["n"])
+            want = M.half_tile_sums(stored)
+            tol_s, tol_q = 1e-5 * float(v.abs().sum(1).max()), 1e-5 * float((v * v).sum(1).max())
+        else:
+            want = ref["gn_part"]
+            tol_s, tol_q = 2e-3 * float(want[..., 0].abs().max() + 128.0 * 0.02), 3e-3 * float(want[..., 1].abs().max())
+        es, eq = float((have[..., 0] - want[..., 0]).abs().max()), float((have[..., 1] - want[..., 1]).abs().max())
+        assert es <= tol_s and eq <= tol_q, f"gn_part: sums off by {es:.3e} (allowed {tol_s:.3e}), squares by {eq:.3e} ({tol_q:.3e}) ({kernel}): {what}"
+    if d["euler_out"]:
+        want = ref["euler_out"].reshape(-1)
+        have = got["euler_out"][:m * 4].double()
+        l2 = float((have - want).norm() / want.norm())
+        mx = float((have - want).abs().max() / want.abs().max())
+        lim = (2e-3, 4e-3) if d["euler_eps_uncond"] else (1e-3, 2e-3)
+        assert l2 <= lim[0] and mx <= lim[1], f"Euler tail: rel_l2={l2:.3e} max_rel={mx:.3e} ({kernel}): {what}"
+    return e[0], e[1], kernel
+
+
+@pytest.mark.parametrize("route,bm", M.ROUTES)
+def test_gemm_descriptor_fuzz(route, bm):
+    from vdpp_amd.hip import ops
+    lib = ops.load()
+    zero_page = ops.zero_page(torch.device(DEV))
+    draws = M.route_draws(route, bm)
+    worst_g = worst_b = 0.0
+    kernels = []
+    with (ops.gemm_route(3, bm=256, bn=192) if bm == -192 else ops.gemm_route(route, bm=bm)):
+        for i, d in enumerate(draws):
+            try:
+                g, b, kernel = run_draw(d, lib, zero_page)
+            except AssertionError as err:
+                raise AssertionError(f"route ({route}, {bm}) draw {i}: {err}") from None
+            worst_g, worst_b = max(worst_g, g), max(worst_b, b)
+            kernels.append(kernel)
+            # options that a forced route cannot serve run where the header says they run
+            if d["gn_part"] or d["a2"]:
+                assert kernel.startswith("gemm_pp_kernel<256,"), (i, kernel)
+            elif d["ln_out"] or d["w_group_rows"]:
+                assert kernel.startswith("gemm_pp_kernel<"), (i, kernel)
+    print(f"descriptor fuzz route ({route}, {bm}): {len(draws)} draws, worst global rel_l2 {worst_g:.2e}, worst 64x64 block {worst_b:.2e}")
+    own = [k for k in kernels if k.startswith(family(route, bm)) and (route != 4 or "splitk_reduce_kernel" in k)]
+    assert len(own) >= 5, f"route ({route}, {bm}): its own family ran {len(own)} times: {sorted(set(kernels))}"
+    assert any(k.startswith("gemm_pp_kernel<256,") for k, d in zip(kernels, draws) if d["gn_part"] or d["a2"]), \
+        "no draw of this route took the option-forced 256-row ping-pong tiles"
+
+
+# Draws of the seeded run above that were wrong when this file was written: GEGLU together with bias2 rows on the small-tile
+# kernels (gemm_f16_kernel's GEGLU epilogue dropped bias2: rel_l2 0.72 - 0.79), kept by name and run on every family.
+GEGLU_BIAS2_DRAWS = [((0, 0), 0), ((1, 0), 9), ((4, 0), 12)]
+
+
+@pytest.mark.parametrize("route,bm", [(0, 0), (1, 0), (2, 256), (2, 192), (2, 128), (3, 256), (4, 0)])
+def test_geglu_with_bias2_rows_regression(route, bm):
+    from vdpp_amd.hip import ops
+    lib = ops.load()
+    zero_page = ops.zero_page(torch.device(DEV))
+    cases = [M.route_draws(*r)[i] for r, i in GEGLU_BIAS2_DRAWS]
+    big = M.blank()                # and many rows of a linear layer (what the persistent kernels take), one bias2 row per 1,000
+    big.update({p: M.FAKE[p] for p in ("a", "w", "d", "zero_page", "bias", "bias2")})
+    big.update(mode=M.LINEAR, m=5000, n=512, cin=320, lda=328, geglu=1, ldd=264, bias2_rows=1000, ldb2=516,
+               _off={"a": 8, "d": 8, "bias2": 4}, _seed=31, _broken=None)
+    with ops.gemm_route(route, bm=bm):
+        for d in cases + [big]:
+            assert d["geglu"] and d["bias2"] and M.legal(d) == (True, None)
+            run_draw(d, lib, zero_page)

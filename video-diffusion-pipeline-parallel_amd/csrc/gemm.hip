@@ -315,6 +315,12 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void gemm_f16_kernel(const GemmArgs
             hv = (acc[i][j] - st.x * ch) * st.y + bh;
             gv = (acc[i + 1][j] - st.x * cg) * st.y + bg;
           }
+          if (p.bias2) {          // (value and gate rows each take their own bias2 columns, like bias)
+            const int64_t m = (int64_t)tile_m * BM + ml;
+            const float *b2 = p.bias2 + (m < p.m ? m / p.bias2_rows : 0) * p.ldb2 + n;
+            hv += *(const f32x4 *)b2;
+            gv += *(const f32x4 *)(b2 + 16);
+          }
           f16x4 h;
 #pragma unroll
           for (int r = 0; r < 4; ++r) h[r] = (f16)(p.oscale * hv[r] * gelu_f(gv[r]));
@@ -533,11 +539,9 @@ int dispatch(GemmArgs &a, const sp_gemm_desc *d, hipStream_t s) {
   }
 
   if (a.w_group_rows) {                       // ping-pong kernels only (the others walk one weight matrix)
-    const int bn = ok320 ? 320 : 256;
-    int bm = 0;
-    const int bms[3] = {256, 192, 128};
-    for (int i = 0; i < 3 && !bm; ++i)
-      if (group_ok(bms[i]) && !(bms[i] == 128 && bn != 256)) bm = bms[i];
+    int bn = ok320 ? 320 : 256;
+    int bm = group_ok(256) ? 256 : group_ok(192) ? 192 : 0;
+    if (!bm && group_ok(128) && ok256) { bm = 128; bn = 256; }      // 128-row tiles exist 256 columns wide only
     SP_REQUIRE(bm, "sp_gemm_f16: w_group_rows=%lld fits no tile height for n=%d", (long long)a.w_group_rows, d->n);
     return launch_pp(a, bm, bn, s);
   }
@@ -697,7 +701,16 @@ extern "C" int sp_gemm_f16(const sp_gemm_desc *d, void *stream) {
   SP_REQUIRE(d->n % 64 == 0, "sp_gemm_f16: n=%d must be a multiple of 64", d->n);
   SP_REQUIRE(d->mode >= SP_A_LINEAR && d->mode <= SP_A_TEMPORAL3, "sp_gemm_f16: bad mode %d", d->mode);
   SP_REQUIRE(d->lda >= d->cin && d->lda % 8 == 0, "sp_gemm_f16: lda=%lld invalid", (long long)d->lda);
-  SP_REQUIRE(d->ldd % 8 == 0 || d->n_store > 0, "sp_gemm_f16: ldd must be a multiple of 8");
+  // stored columns per row: every row pitch that addresses them must cover them (a smaller one makes rows overlap and the
+  // last rows reach past the caller's buffer)
+  const int nout_cols = d->geglu ? d->n / 2 : d->n;
+  SP_REQUIRE(d->n_store >= 0 && d->n_store <= nout_cols, "sp_gemm_f16: n_store=%d must be 0 (all) or 1 ... %d output columns",
+             d->n_store, nout_cols);
+  const int stored_cols = d->n_store > 0 ? d->n_store : nout_cols;
+  // (rows of fewer than 8 stored halves are written element by element: any pitch; everything else takes 16-byte stores)
+  SP_REQUIRE(d->ldd >= stored_cols && (d->ldd % 8 == 0 || (d->n_store > 0 && d->n_store < 8)),
+             "sp_gemm_f16: ldd=%lld must be >= the %d stored columns and a multiple of 8 (any pitch with 0 < n_store < 8)",
+             (long long)d->ldd, stored_cols);
   GemmArgs a{};
 #ifdef SP_GEMM_EXPERIMENTS
   { const char *e = getenv("SP_GEMM_DBG"); a.dbg = e ? atoi(e) : 0; }   // ablation builds only (make exp)
@@ -725,6 +738,10 @@ extern "C" int sp_gemm_f16(const sp_gemm_desc *d, void *stream) {
                "sp_gemm_f16: per-row-group weights need SP_A_LINEAR, no geglu / Euler tail / folded LayerNorm (ln_stats), n a "
                "multiple of 256 or 320, w_group_rows a positive multiple of 128 (got %lld) and w_group_stride a positive multiple "
                "of 8 (got %lld)", (long long)d->w_group_rows, (long long)d->w_group_stride);
+    // gn_part pins the 256-row tiles: a group of 128 or 384 rows would be straddled by one of them
+    SP_REQUIRE(!d->gn_part || d->w_group_rows % 256 == 0,
+               "sp_gemm_f16: with gn_part (256-row tiles) w_group_rows must be a multiple of 256 (got %lld)",
+               (long long)d->w_group_rows);
     a.w_group_rows = d->w_group_rows; a.w_group_stride = d->w_group_stride;
   }
   if (d->ln_out) {
@@ -761,7 +778,8 @@ extern "C" int sp_gemm_f16(const sp_gemm_desc *d, void *stream) {
   }
   if (d->ln_stats)
     SP_REQUIRE(d->ln_colsum && d->mode == SP_A_LINEAR && !d->bias2,
-               "sp_gemm_f16: a folded LayerNorm needs ln_colsum, SP_A_LINEAR and no bias2");
+               "sp_gemm_f16: a folded LayerNorm (ln_stats) needs ln_colsum, SP_A_LINEAR and no bias2");
+  SP_REQUIRE(!d->ln_colsum || d->ln_stats, "sp_gemm_f16: ln_colsum without ln_stats (the fold needs both)");
   a.zero = (const char *)d->zero_page;
   a.lda = d->lda; a.ldr1 = d->ldr1; a.ldr2 = d->ldr2; a.ldd = d->ldd;
   a.mode = d->mode; a.cin = d->cin;
@@ -784,15 +802,21 @@ extern "C" int sp_gemm_f16(const sp_gemm_desc *d, void *stream) {
   a.geglu = d->geglu; a.n_store = d->n_store;
   a.bias2_rows = d->bias2_rows > 0 ? d->bias2_rows : d->m;
   a.ldb2 = d->ldb2 > 0 ? d->ldb2 : d->n;
-  if (d->res1) SP_REQUIRE(d->ldr1 % 8 == 0, "sp_gemm_f16: ldr1 must be a multiple of 8");
-  if (d->res2) SP_REQUIRE(d->ldr2 % 8 == 0, "sp_gemm_f16: ldr2 must be a multiple of 8");
+  if (d->bias2)
+    SP_REQUIRE(d->bias2_rows >= 0 && (d->ldb2 == 0 || (d->ldb2 >= d->n && d->ldb2 % 4 == 0)),
+               "sp_gemm_f16: bias2 needs bias2_rows=%lld >= 0 and ldb2=%lld 0 or a multiple of 4 that is >= n (%d)",
+               (long long)d->bias2_rows, (long long)d->ldb2, d->n);
+  if (d->res1) SP_REQUIRE(d->ldr1 % 8 == 0 && d->ldr1 >= stored_cols,
+                          "sp_gemm_f16: ldr1=%lld must be a multiple of 8 and >= the %d stored columns", (long long)d->ldr1, stored_cols);
+  if (d->res2) SP_REQUIRE(d->ldr2 % 8 == 0 && d->ldr2 >= stored_cols,
+                          "sp_gemm_f16: ldr2=%lld must be a multiple of 8 and >= the %d stored columns", (long long)d->ldr2, stored_cols);
   if (d->mode == SP_A_CONV3X3) {
     SP_REQUIRE(d->stride == 1 || d->stride == 2, "sp_gemm_f16: stride must be 1 or 2");
     SP_REQUIRE(d->n_img > 0 && d->hin > 0 && d->win > 0 && d->hout > 0 && d->wout > 0,
-               "sp_gemm_f16: conv geometry must be positive");
+               "sp_gemm_f16: conv geometry (n_img, hin, win, hout, wout) must be positive");
     const int hv = d->hin << (d->upsample2x ? 1 : 0), wv = d->win << (d->upsample2x ? 1 : 0);
     SP_REQUIRE(d->hout == (hv + 2 - 3) / d->stride + 1 && d->wout == (wv + 2 - 3) / d->stride + 1,
-               "sp_gemm_f16: conv output %dx%d inconsistent with input %dx%d stride %d", d->hout,
+               "sp_gemm_f16: conv output hout x wout = %dx%d inconsistent with input %dx%d stride %d", d->hout,
                d->wout, hv, wv, d->stride);
     SP_REQUIRE((int64_t)d->n_img * d->hout * d->wout == d->m, "sp_gemm_f16: m != n_img*hout*wout");
     a.n_img = d->n_img; a.hin = d->hin; a.win = d->win; a.hout = d->hout; a.wout = d->wout;
@@ -803,7 +827,7 @@ extern "C" int sp_gemm_f16(const sp_gemm_desc *d, void *stream) {
                (long long)d->hw);
     a.frames = d->frames; a.hw = d->hw;
   }
-  if (d->geglu) SP_REQUIRE(d->n % 128 == 0, "sp_gemm_f16: geglu needs n %% 128 == 0");
+  if (d->geglu) SP_REQUIRE(d->n % 128 == 0, "sp_gemm_f16: geglu needs n %% 128 == 0 (n=%d)", d->n);
   hipStream_t s = (hipStream_t)stream;
   return dispatch(a, d, s);
 }
