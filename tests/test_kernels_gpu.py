@@ -635,7 +635,7 @@ def test_gemm_with_folded_layernorm(m, c, n, geglu, route):
     runs on the UN-normalised rows with gamma-scaled weights and applies rstd*(acc - mean*colsum) + (W.beta + b)
     in its epilogue.  Every kernel family, rows with a large common offset; vs torch layer_norm -> linear (-> GEGLU)."""
     ops = _ops()
-    from vdpp_amd.models.unet_hip import _Dense
+    from vdpp_amd.models.common import _Dense
     g = torch.Generator().manual_seed(m + n)
     x = h(torch.randn(m, c, generator=g) * 1.7 + 3.0 * torch.randn(m, 1, generator=g))
     gamma = 1.0 + 0.3 * torch.randn(c, generator=g); beta = 0.5 * torch.randn(c, generator=g)
@@ -699,7 +699,7 @@ def test_gemm_split_k(case):
         xa = h(torch.randn(m, cin, generator=g) + 2.0); wl = h(torch.randn(n, cin, generator=g) / math.sqrt(cin))
         a = xa.half().to(DEV)
         if case == "ln_geglu_forced":
-            from vdpp_amd.models.unet_hip import _Dense
+            from vdpp_amd.models.common import _Dense
             gamma = 1.0 + 0.3 * torch.randn(cin, generator=g); beta = 0.5 * torch.randn(cin, generator=g)
             bl = torch.randn(n, generator=g)
             layer = _Dense.fold_layernorm(wl, bl, gamma, beta, DEV, eps=1e-5, geglu=True)

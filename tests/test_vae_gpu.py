@@ -129,6 +129,7 @@ def test_mid_block_attention_with_logits_beyond_fp16():
     (scripts/generate_video_demo.py:171-175).  With fp32 logits (round 5) the block matches an fp64 evaluation to 2e-2;
     the fp16-score composition (VDPP_VAE_FP16_SCORES=1 / fp32_scores=False) can only saturate and must be visibly wrong
     on the same input, which is what makes this a test of the new path."""
+    from vdpp_amd.models.common import _Act
     from vdpp_amd.models.vae_hip import TemporalDecoderHIP, VAEDecoderConfig, random_state_dict
     cfg = VAEDecoderConfig.tiny(64)
     sd = random_state_dict(cfg, seed=5)
@@ -142,9 +143,9 @@ def test_mid_block_attention_with_logits_beyond_fp16():
         p[name].w = (p[name].w.float() * f).half()
         p[name].bias = p[name].bias * f
     assert dec.fp32_scores
-    got32 = dec._run_attn(p, x.to(DEV), n_img, hw).float().cpu()
+    got32 = dec._run_attn(p, _Act(x.to(DEV)), n_img, hw).t.float().cpu()
     dec.fp32_scores = False
-    got16 = dec._run_attn(p, x.to(DEV), n_img, hw).float().cpu()
+    got16 = dec._run_attn(p, _Act(x.to(DEV)), n_img, hw).t.float().cpu()
     dec.fp32_scores = True
     # fp64 reference of the same block on the same fp16-rounded weights
     xn = F.group_norm(x.double().reshape(n_img, hw, c).permute(0, 2, 1), cfg.norm_groups,

@@ -23,8 +23,9 @@ from dataclasses import dataclass
 import torch
 
 from ..hip import ops
+from . import common
 from . import weights as W
-from .unet_hip import _Dense, _Norm, _f32
+from .common import _Dense, _Norm
 
 
 @dataclass
@@ -56,10 +57,7 @@ class CLIPVisionHIP:
 
     def __init__(self, spec: CLIPVisionSpec, state_dict: dict, device):
         self.spec = spec
-        self.device = dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("CLIPVisionHIP runs on an MI355X HIP device only (no CPU fallback)")
-        ops.load()  # fail loudly now if the extension is missing
+        self.device = dev = common.hip_device(device, "CLIPVisionHIP")
         c, heads = spec.hidden_size, spec.num_attention_heads
         if c % 64 or spec.intermediate_size % 64 or c % heads or (c // heads) % 8 or c // heads > 128:
             raise ValueError("unsupported widths: hidden/intermediate multiples of 64, head width a multiple of 8 <= 128")

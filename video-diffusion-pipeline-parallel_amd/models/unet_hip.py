@@ -29,80 +29,16 @@ Fusions baked into the kernel calls:
 
 from __future__ import annotations
 
-import math
 import os
 from dataclasses import dataclass
 
 import torch
 
 from ..hip import ops
+from . import common
 from . import weights as W
+from .common import _Act, _Dense, _Norm, _f32
 from .unet_spec import UNetConfig, up_block_plan
-
-
-def _version(t):
-    """In-place-write counter of a tensor (inference tensors keep none: -1)."""
-    try:
-        return t._version
-    except RuntimeError:
-        return -1
-
-
-def _f32(t, device):
-    return t.detach().to(device=device, dtype=torch.float32).contiguous()
-
-
-class _Dense:
-    """One contraction: packed fp16 weight ``[N][K]`` + fp32 bias, and how its A operand is gathered."""
-
-    def __init__(self, w16, bias32, *, cin, mode=ops.A_LINEAR, n_true=None, geglu=False, colsum=None, ln_eps=None):
-        self.w, self.bias, self.cin, self.mode = w16, bias32, cin, mode
-        self.n = w16.shape[0]
-        self.n_true = n_true if n_true is not None else (self.n // 2 if geglu else self.n)
-        self.geglu = geglu
-        self.colsum, self.ln_eps = colsum, ln_eps          # set when a LayerNorm is folded into this contraction
-
-    @staticmethod
-    def fold_layernorm(w, b, norm_w, norm_b, dev, *, eps, geglu=False):
-        """``LN(x) @ W^T + b`` as a contraction on the un-normalised x: ``rstd*(x @ (W*gamma)^T - mean*colsum) + (W @ beta
-        + b)`` with ``colsum[n] = sum_k (W*gamma)[n][k]`` taken over the fp16 values the kernel multiplies with."""
-        w32, g32, be32 = w.to(dev).float(), norm_w.to(dev).float(), norm_b.to(dev).float()
-        bias = w32 @ be32 + (b.to(dev).float() if b is not None else 0.0)
-        wg = (w32 * g32[None, :])
-        if geglu:
-            wg, bias = W.interleave_geglu(wg, bias)
-        wg16 = wg.to(torch.float16).contiguous()
-        return _Dense(wg16, bias.float().contiguous(), cin=wg16.shape[1], geglu=geglu,
-                      colsum=wg16.float().sum(dim=1).contiguous(), ln_eps=eps)
-
-    @staticmethod
-    def linear(sd, p, dev, bias=True):
-        w = W.pack_linear(sd[p + ".weight"]).to(dev)
-        return _Dense(w, _f32(sd[p + ".bias"], dev) if bias else None, cin=w.shape[1])
-
-    @staticmethod
-    def conv3x3(sd, p, dev):
-        w = sd[p + ".weight"]
-        cout, cin = w.shape[:2]
-        npad, cpad = W.round_up(cout, 64), W.round_up(cin, 64)
-        b = torch.zeros(npad, dtype=torch.float32, device=dev)
-        b[:cout] = sd[p + ".bias"].to(dev).float()
-        return _Dense(W.pack_conv3x3(w.to(dev), cpad, npad), b, cin=cpad, mode=ops.A_CONV3X3, n_true=cout)
-
-    @staticmethod
-    def tconv(sd, p, dev):
-        w = sd[p + ".weight"]
-        return _Dense(W.pack_tconv3(w.to(dev)), _f32(sd[p + ".bias"], dev), cin=w.shape[1], mode=ops.A_TEMPORAL3)
-
-    @staticmethod
-    def geglu_proj(sd, p, dev):
-        wi, bi = W.interleave_geglu(sd[p + ".weight"].to(dev), sd[p + ".bias"].to(dev))
-        return _Dense(wi, bi, cin=wi.shape[1], geglu=True)
-
-
-class _Norm:
-    def __init__(self, sd, p, dev, eps):
-        self.g, self.b, self.eps = _f32(sd[p + ".weight"], dev), _f32(sd[p + ".bias"], dev), eps
 
 
 @dataclass
@@ -128,6 +64,40 @@ class _Run:
     @property
     def m(self):
         return self.b * self.f * self.h * self.w
+
+
+class _Skips:
+    """The up path's concatenation buffers.  No torch.cat (diffusers' up blocks concatenate the running tensor with a skip
+    in front of every resnet): the buffer [rows][Cx + Cskip] an up resnet reads is allocated when its skip is PRODUCED in
+    the down path; the skip's producer writes the right-hand columns in place, and the up path's producer of the running
+    tensor (mid block, previous resnet / transformer / upsampler) writes the left-hand columns.  Until then the down path
+    keeps working on the skip through its strided view.  Each producer's column sums (``_Act.gn_part``) are noted beside
+    its half: where both left them, the popped buffer carries the pair for the up resnet's first norm."""
+
+    def __init__(self, buf, cx):
+        self.buf, self.cx, self.cats = buf, cx, []   # cx: Cx in the order the up path consumes; cats: as the down path produces
+
+    def right_dest(self, rows, cskip):
+        cx = self.cx[len(self.cx) - 1 - len(self.cats)]
+        self.cats.append(_Act(self.buf(rows, cx + cskip), c_a=cx))
+        return self.cats[-1].t[:, cx:]
+
+    def right(self, a: _Act):
+        self.cats[-1].gn_part_b = a.gn_part
+        return a
+
+    def left_dest(self):
+        """Left-hand columns of the buffer the next up resnet reads (None: no more)."""
+        return self.cats[-1].t[:, :self.cats[-1].c_a] if self.cats else None
+
+    def left(self, a: _Act):
+        if self.cats:
+            self.cats[-1].gn_part = a.gn_part
+        return a
+
+    def pop(self) -> _Act:
+        cat = self.cats.pop()
+        return cat if cat.gn_part is not None and cat.gn_part_b is not None else _Act(cat.t)
 
 
 class SVDUNetHIP:
@@ -167,10 +137,7 @@ class SVDUNetHIP:
         # LayerNorm row statistics from the producing contraction's epilogue also for rows of three / four column tiles
         # (1,280 channels at the 576-token level)
         self.ln_out_wide = os.environ.get("VDPP_LN_OUT_WIDE", "1") != "0"
-        self.device = dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("SVDUNetHIP runs on an MI355X HIP device only (no CPU fallback)")
-        ops.load()  # fail loudly now if the extension is missing
+        self.device = dev = common.hip_device(device, "SVDUNetHIP")
         sd = state_dict
         self._temb_w, self._temb_b, self._temb_n = [], [], 0
         self._xf_all = []
@@ -380,14 +347,15 @@ class SVDUNetHIP:
     def _buf(self, rows, c):
         return torch.empty((rows, c), dtype=torch.float16, device=self.device)
 
-    def _gemm(self, r: _Run, layer: _Dense, a, *, m=None, conv=None, **kw):
+    def _gemm(self, r: _Run, layer: _Dense, a, *, m=None, conv=None, ln_next=None, ln_out=None, **kw) -> _Act:
+        """One contraction on the plain tensor ``a``; returns its output with the statistics the epilogue left.
+        ``ln_next``: the contraction that will consume this output through a folded LayerNorm.  Where one tile spans a
+        whole output row (256 / 320 channels: level 0) the epilogue leaves that LayerNorm's (mean, rstd) in the returned
+        record and _ln_stats takes them from there instead of reading the tensor again (512 / 640 channels, level 1: two
+        tiles per row, their sums meet in a 16-byte-per-row scratch).  ``ln_out``: the caller has decided that already
+        and the statistics go there (_ff_pair: a chunk's rows of the whole tensor's statistics)."""
         m = r.m if m is None else m
         out = kw.pop("out", None)
-        # ``ln_next``: the contraction that will consume this output through a folded LayerNorm.  Where one tile spans a
-        # whole output row (256 / 320 channels: level 0) the epilogue leaves that LayerNorm's (mean, rstd) beside the
-        # output and _ln_stats finds them there instead of reading the tensor again (512 / 640 channels, level 1: two tiles
-        # per row, their sums meet in a 16-byte-per-row scratch).
-        ln_next = kw.pop("ln_next", None)
         # ``w_groups`` = (w_f [instances][n][c] fp16, bias_f [instances][n] fp32, rows per instance): a GroupNorm folded
         # into this linear layer (ops.groupnorm_fold_linear) -- every instance's rows meet their own scaled weights
         w_groups = kw.pop("w_groups", None)
@@ -396,10 +364,9 @@ class SVDUNetHIP:
             weight, bias = w_groups[0], None
             kw.update(bias2=w_groups[1], bias2_rows=w_groups[2], w_group_rows=w_groups[2],
                       w_group_stride=w_groups[0].shape[1] * w_groups[0].shape[2])
-        st = None
         ws = r.sk_ws if m <= self.SPLITK_MAX_ROWS else None
         # ``gn_next``: this output goes straight into a GroupNorm (no residual in between): where the tiles allow it the
-        # epilogue leaves per-tile column sums beside the output and _gn folds them instead of reading the tensor again
+        # epilogue leaves per-tile column sums in the returned record and _gn folds them instead of reading the tensor again
         gn_part = None
         if kw.pop("gn_next", False) and self.gn_from_epilogue and m % 256 == 0 and layer.n == layer.n_true \
                 and not layer.geglu and (layer.n % 320 == 0 or layer.n % 256 == 0) and r.hw % 256 == 0 \
@@ -407,9 +374,10 @@ class SVDUNetHIP:
                 and (self.gn_epilogue_residual or (kw.get("res1") is None and kw.get("res2") is None)):
             gn_part = torch.empty((m // 256, 2, layer.n, 2), dtype=torch.float32, device=self.device)
             kw.update(gn_part=gn_part)
-        st_buf = kw.pop("ln_out_buf", None)             # caller-provided rows of a larger statistics tensor (_ff_pair chunks)
-        if ln_next is not None and self._ln_out_ok(layer, m) and "euler" not in kw:
-            st = st_buf if st_buf is not None else torch.empty((m, 2), dtype=torch.float32, device=self.device)
+        st = ln_out
+        if st is None and ln_next is not None and self._ln_out_ok(layer, m) and "euler" not in kw:
+            st = torch.empty((m, 2), dtype=torch.float32, device=self.device)
+        if st is not None:
             kw.update(ln_out=st, ln_out_eps=ln_next.ln_eps)
             tiles = layer.n_true // (320 if layer.n_true % 320 == 0 else 256)
             ws = torch.empty((m, 2 * tiles), dtype=torch.float32, device=self.device) if tiles > 1 else None
@@ -429,13 +397,7 @@ class SVDUNetHIP:
         ops.gemm(a, weight, out, m=m, n=layer.n, cin=layer.cin, mode=layer.mode, conv=conv, temporal=temporal,
                  bias=bias, geglu=layer.geglu, n_store=n_store, ldd=out.stride(0), lda=a.stride(0),
                  ln_colsum=layer.colsum, workspace=ws, **kw)
-        if gn_part is not None:
-            out._gn_tile_sums = (gn_part, out.data_ptr(), _version(out), tuple(out.shape))
-        if st is not None and st_buf is None:
-            # valid for exactly this tensor object in exactly this state (checked in _ln_stats): a view, a slice or an
-            # in-place write after the contraction silently falls back to the statistics pass
-            out._row_ln_stats = (st, ln_next.ln_eps, out.data_ptr(), _version(out), tuple(out.shape))
-        return out
+        return _Act(out, gn_part=gn_part, ln_stats=st, ln_eps=ln_next.ln_eps if st is not None else None)
 
     def _ln_out_ok(self, layer: _Dense, m: int) -> bool:
         """Can this contraction's epilogue leave the next LayerNorm's row statistics?  A row = one or two column tiles at
@@ -446,53 +408,31 @@ class SVDUNetHIP:
         return layer.n_true in (256, 320, 512, 640) or (self.ln_out_wide and layer.n_true in (768, 960, 1024, 1280)
                                                         and m > self.SPLITK_MAX_ROWS)
 
-    def _ln_stats(self, layer: _Dense, x, **kw):
-        """(mean, rstd) per row of x for the LayerNorm folded into ``layer``."""
-        have = getattr(x, "_row_ln_stats", None)
-        if (have is not None and not kw and have[1] == layer.ln_eps and have[2] == x.data_ptr() and have[3] == _version(x)
-                and have[4] == tuple(x.shape)):
-            return have[0]                                # left there by the contraction that produced x
+    def _ln_stats(self, layer: _Dense, x: _Act):
+        """(mean, rstd) per row of x for the LayerNorm folded into ``layer``: left by x's producer, or a pass over x."""
+        if x.ln_stats is not None and x.ln_eps == layer.ln_eps:
+            return x.ln_stats
+        return self._ln_pass(layer, x.t)
+
+    def _ln_pass(self, layer: _Dense, x, **kw):
         st = torch.empty((x.shape[0], 2), dtype=torch.float32, device=self.device)
         ops.ln_stats(x, st, rows=x.shape[0], c=x.shape[1], eps=layer.ln_eps, **kw)
         return st
 
-    @staticmethod
-    def _tile_sums(x, rows):
-        """The per-tile column sums the contraction that produced x left beside it (``_gemm(gn_next=True)``), if they are
-        for exactly this tensor in this state and an instance of ``rows`` rows is whole 256-row tiles; else None."""
-        have = getattr(x, "_gn_tile_sums", None)
-        if (have is not None and have[1] == x.data_ptr() and have[2] == _version(x) and have[3] == tuple(x.shape)
-                and rows % 256 == 0):
-            return have[0]
-        return None
-
-    def _gn(self, r: _Run, norm: _Norm, x, *, temporal: bool, silu: bool, concat_sums=None):
-        """``concat_sums`` = (sums of the left columns, sums of the right columns): x is a concatenation buffer whose two
-        halves were written by two contractions that both left their column sums (an up block's first norm)."""
-        c = x.shape[1]
+    def _gn(self, r: _Run, norm: _Norm, a: _Act, *, temporal: bool, silu: bool):
+        """GroupNorm of ``a`` -> plain tensor.  Where a's producer left its column sums (for a concatenation buffer: both
+        producers, an up block's first norm) and an instance is whole 256-row tiles, they replace the statistics pass."""
+        x, c, groups = a.t, a.t.shape[1], self.cfg.norm_groups
         inst, rows = (r.b, r.f * r.hw) if temporal else (r.b * r.f, r.hw)
         y = self._buf(x.shape[0], c)
-        if concat_sums is not None and concat_sums[0] is not None and concat_sums[1] is not None and rows % 256 == 0:
-            (pa, _pa, _va, sa), (pb, _pb, _vb, sb) = concat_sums
-            if (sa[0] == x.shape[0] == sb[0] and sa[1] + sb[1] == c and x.stride(0) == c and _pa == x.data_ptr()
-                    and _pb == x.data_ptr() + 2 * sa[1] and _va == _version(x) == _vb):
-                stats = torch.empty((inst, self.cfg.norm_groups, 2), dtype=torch.float32, device=self.device)
-                ops.groupnorm_tile_sums(x, pa, norm.g, norm.b, y, instances=inst, rows=rows, c=c, groups=self.cfg.norm_groups,
-                                        eps=norm.eps, silu=silu, stats=stats, ldx=c, part_b=pb, c_a=sa[1])
-                return y
-        part = self._tile_sums(x, rows)
-        if part is not None:
-            stats = torch.empty((inst, self.cfg.norm_groups, 2), dtype=torch.float32, device=self.device)
-            ops.groupnorm_tile_sums(x, part, norm.g, norm.b, y, instances=inst, rows=rows, c=c,
-                                    groups=self.cfg.norm_groups, eps=norm.eps, silu=silu, stats=stats, ldx=x.stride(0))
+        if a.gn_part is not None and rows % 256 == 0:
+            stats = torch.empty((inst, groups, 2), dtype=torch.float32, device=self.device)
+            cat = dict(part_b=a.gn_part_b, c_a=a.c_a) if a.gn_part_b is not None else {}
+            ops.groupnorm_tile_sums(x, a.gn_part, norm.g, norm.b, y, instances=inst, rows=rows, c=c, groups=groups,
+                                    eps=norm.eps, silu=silu, stats=stats, ldx=x.stride(0), **cat)
             return y
-        ops.groupnorm(x, norm.g, norm.b, y, instances=inst, rows=rows, c=c, groups=self.cfg.norm_groups,
+        ops.groupnorm(x, norm.g, norm.b, y, instances=inst, rows=rows, c=c, groups=groups,
                       eps=norm.eps, silu=silu, ws=r.gn_ws, ldx=x.stride(0))
-        return y
-
-    def _ln(self, norm: _Norm, x, **kw):
-        y = self._buf(*x.shape)
-        ops.layernorm(x, norm.g, norm.b, y, rows=x.shape[0], c=x.shape[1], eps=norm.eps, **kw)
         return y
 
     def _conv_geom(self, r: _Run, stride=1, ups=0):
@@ -501,28 +441,28 @@ class SVDUNetHIP:
         return (r.b * r.f, r.h, r.w, ho, wo, stride, ups), ho, wo
 
     # ------------------------------------------------------------------ blocks
-    def _run_resblock(self, r: _Run, p, x, out=None, gn_next=False, concat_sums=None):
-        """``out``: where the block's result goes (a half of a concatenation buffer), default a fresh tensor.
-        ``gn_next``: the result goes straight into a GroupNorm (a transformer's entry norm, ``conv_norm_out``): ask the last
-        contraction for the column sums."""
+    def _run_resblock(self, r: _Run, p, x: _Act, out=None, gn_next=False) -> _Act:
+        """``x``: the block's input (an up block's: the concatenation buffer).  ``out``: where the block's result goes (a
+        half of a concatenation buffer), default a fresh tensor.  ``gn_next``: the result goes straight into a GroupNorm (a
+        transformer's entry norm, ``conv_norm_out``): ask the last contraction for the column sums."""
         geom, _, _ = self._conv_geom(r)
-        t = self._gn(r, p["n1"], x, temporal=False, silu=True, concat_sums=concat_sums)
-        n1 = p["c1"].n
-        t = self._gemm(r, p["c1"], t, conv=geom, **self._temb(r, p["te_s"], n1), gn_next=True)
+        t = self._gn(r, p["n1"], x, temporal=False, silu=True)
+        t = self._gemm(r, p["c1"], t, conv=geom, **self._temb(r, p["te_s"], p["c1"].n), gn_next=True)
         t = self._gn(r, p["n2"], t, temporal=False, silu=True)
+        x = x.t
         if p["sc"] is not None and p["c2sc"] is not None and self.fold_shortcut and r.m > self.SPLITK_MAX_ROWS \
                 and r.m % 256 == 0:
             # the shortcut convolution rides in conv2's K loop (sp_gemm_desc.a2): no skip tensor, and no residual in front of
             # the temporal block's first norm (its column sums then come straight from the accumulators)
             s = self._gemm(r, p["c2sc"], t, conv=geom, a2=x, cin2=p["c2sc"].cin2, lda2=x.stride(0), gn_next=True)
         else:
-            skip = x if p["sc"] is None else self._gemm(r, p["sc"], x)
+            skip = x if p["sc"] is None else self._gemm(r, p["sc"], x).t
             s = self._gemm(r, p["c2"], t, conv=geom, res1=skip, r1scale=1.0, gn_next=True)
         # temporal branch + AlphaBlender: alpha*s + (1-alpha)*(s + conv2(...)) = s + (1-alpha)*conv2(...)
         t = self._gn(r, p["tn1"], s, temporal=True, silu=True)
         t = self._gemm(r, p["tc1"], t, **self._temb(r, p["te_t"], p["cout"]), gn_next=True)
         t = self._gn(r, p["tn2"], t, temporal=True, silu=True)
-        return self._gemm(r, p["tc2"], t, oscale=1.0 - p["alpha"], res1=s, r1scale=1.0, out=out, gn_next=gn_next)
+        return self._gemm(r, p["tc2"], t, oscale=1.0 - p["alpha"], res1=s.t, r1scale=1.0, out=out, gn_next=gn_next)
 
     @staticmethod
     def _temb(r: _Run, off: int, n: int) -> dict:
@@ -537,11 +477,11 @@ class SVDUNetHIP:
         c, g = x["grp"]
         return r.cross[c][g]
 
-    def _self_attn(self, r: _Run, att, xvec, resid, *, temporal: bool, **epi):
+    def _self_attn(self, r: _Run, att, xvec, resid: _Act, *, temporal: bool, **epi) -> _Act:
         """LayerNorm (folded into the fused Q/K/V projection) -> self-attention -> output projection + residual."""
         c = att["out"].n
         heads = c // 64
-        qkv = self._gemm(r, att["qkv"], resid, ln_stats=self._ln_stats(att["qkv"], resid))
+        qkv = self._gemm(r, att["qkv"], resid.t, ln_stats=self._ln_stats(att["qkv"], resid)).t
         o = self._buf(r.m, c)
         q, k, v = qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:]
         if temporal:
@@ -567,26 +507,25 @@ class SVDUNetHIP:
             ops.attn_spatial(q, k, v, o, ldq=3 * c, ldk=3 * c, ldv=3 * c, ldo=c, batch=r.b * r.f, seq=r.hw,
                              heads=heads)
         # self-attn out-proj + residual, with the (token independent) cross-attention result as extra bias
-        return self._gemm(r, att["out"], o, bias2=self._cross_vec(r, xvec), bias2_rows=r.f * r.hw, res1=resid,
+        return self._gemm(r, att["out"], o, bias2=self._cross_vec(r, xvec), bias2_rows=r.f * r.hw, res1=resid.t,
                           r1scale=1.0, **epi)
 
     # GroupNorm -> proj_in fold: the per-frame weight copies must stay small next to the pass they replace
     GN_FOLD_MAX_WEIGHT_BYTES = 64 << 20
 
-    def _proj_in(self, r: _Run, p, x):
+    def _proj_in(self, r: _Run, p, a: _Act) -> _Act:
         """``proj_in(norm(x))`` of a transformer.  The GroupNorm has no activation and feeds a linear layer, so where a
         frame's rows are whole tiles (the 9,216- and 2,304-token levels) it is folded into per-frame weights
         (``sp_groupnorm_fold_linear_f16``): one statistics pass over x instead of a statistics pass, an apply pass and the
         normalised tensor's round trip through HBM.  Elsewhere: GroupNorm kernel + plain contraction."""
-        c, inst = p["c"], r.b * r.f
+        x, c, inst = a.t, p["c"], r.b * r.f
         if (self.fold_groupnorm and r.hw % 256 == 0 and (c % 256 == 0 or c % 320 == 0)          # whole ping-pong tiles
                 and inst * c * c * 2 <= self.GN_FOLD_MAX_WEIGHT_BYTES):
             w_f = torch.empty((inst, c, c), dtype=torch.float16, device=self.device)
             b_f = torch.empty((inst, c), dtype=torch.float32, device=self.device)
-            part = self._tile_sums(x, r.hw)
-            if part is not None:       # the resnet's last contraction left the column sums: no statistics pass over x
+            if a.gn_part is not None:  # the resnet's last contraction left the column sums: no statistics pass over x
                 stats = torch.empty((inst, self.cfg.norm_groups, 2), dtype=torch.float32, device=self.device)
-                ops.groupnorm_fold_linear_tile_sums(part, p["norm"].g, p["norm"].b, p["pin"].w, p["pin"].bias, w_f, b_f,
+                ops.groupnorm_fold_linear_tile_sums(a.gn_part, p["norm"].g, p["norm"].b, p["pin"].w, p["pin"].bias, w_f, b_f,
                                                     instances=inst, rows=r.hw, c=c, groups=self.cfg.norm_groups,
                                                     eps=p["norm"].eps, n=c, stats=stats)
             else:
@@ -594,7 +533,7 @@ class SVDUNetHIP:
                                           rows=r.hw, c=c, groups=self.cfg.norm_groups, eps=p["norm"].eps, n=c, ws=r.gn_ws,
                                           ldx=x.stride(0))
             return self._gemm(r, p["pin"], x, ln_next=p["s_attn"]["qkv"], w_groups=(w_f, b_f, r.hw))
-        t = self._gn(r, p["norm"], x, temporal=False, silu=False)
+        t = self._gn(r, p["norm"], a, temporal=False, silu=False)
         return self._gemm(r, p["pin"], t, ln_next=p["s_attn"]["qkv"])
 
     # GEGLU feed-forward pairs in row chunks (VDPP_FF_CHUNK_MB, default 0 = whole tensor): the hidden activation of a
@@ -604,55 +543,55 @@ class SVDUNetHIP:
     FF_CHUNK_BYTES = int(os.environ.get("VDPP_FF_CHUNK_MB", "0")) << 20
     FF_CHUNK_ROUND = None            # tests: rows a chunk is rounded to (default: one full round of FF2 workgroups)
 
-    def _ff_pair(self, r: _Run, ff1: _Dense, ff2: _Dense, x, st, **epi):
-        """``ff2(geglu(ff1(LN(x))))`` with ff2's epilogue arguments ``epi`` (residuals are row-sliced along)."""
+    def _ff_pair(self, r: _Run, ff1: _Dense, ff2: _Dense, x, st, *, ln_next=None, **epi) -> _Act:
+        """``ff2(geglu(ff1(LN(x))))`` on the plain tensor ``x`` with row statistics ``st``; ``epi``: ff2's epilogue
+        arguments (residuals are row-sliced along), ``ln_next`` as in _gemm."""
         m, hid = x.shape[0], ff1.n_true
         budget = self.FF_CHUNK_BYTES
         if not budget or m * hid * 2 <= budget:
-            g = self._gemm(r, ff1, x, ln_stats=st)
-            return self._gemm(r, ff2, g, **epi)
+            g = self._gemm(r, ff1, x, ln_stats=st).t
+            return self._gemm(r, ff2, g, ln_next=ln_next, **epi)
         tiles_n = max(1, ff2.n // 320 if ff2.n % 320 == 0 else ff2.n // 256)
         rows_round = self.FF_CHUNK_ROUND or 256 * max(1, 256 // tiles_n)   # rows of one full round of FF2 workgroups
         rows = max(rows_round, (budget // (hid * 2)) // rows_round * rows_round)
+        spans = [(r0, min(m, r0 + rows)) for r0 in range(0, m, rows)]
         out = epi.pop("out", None)
         if out is None:
             out = self._buf(m, ff2.n_true)
-        ln_next = epi.pop("ln_next", None)
+        # the next LayerNorm's statistics: every chunk leaves those of its rows, or (a chunk's row count rules it out) none
+        # does and the consumer runs its pass
         st_next = None
-        if ln_next is not None and self._ln_out_ok(ff2, m):
+        if ln_next is not None and all(self._ln_out_ok(ff2, r1 - r0) for r0, r1 in spans):
             st_next = torch.empty((m, 2), dtype=torch.float32, device=self.device)
-        for r0 in range(0, m, rows):
-            r1 = min(m, r0 + rows)
+        for r0, r1 in spans:
             kw = {k: (v[r0:r1] if k in ("res1", "res2") and v is not None else v) for k, v in epi.items()}
             if st_next is not None:
-                kw.update(ln_next=ln_next, ln_out_buf=st_next[r0:r1])
-            g = self._gemm(r, ff1, x[r0:r1], m=r1 - r0, ln_stats=st[r0:r1])
+                kw.update(ln_next=ln_next, ln_out=st_next[r0:r1])
+            g = self._gemm(r, ff1, x[r0:r1], m=r1 - r0, ln_stats=st[r0:r1]).t
             self._gemm(r, ff2, g, m=r1 - r0, out=out[r0:r1], **kw)
             del g
-        if st_next is not None:
-            out._row_ln_stats = (st_next, ln_next.ln_eps, out.data_ptr(), _version(out), tuple(out.shape))
-        return out
+        return _Act(out, ln_stats=st_next, ln_eps=ln_next.ln_eps if st_next is not None else None)
 
-    def _run_transformer(self, r: _Run, p, x, out=None, gn_next=False):
+    def _run_transformer(self, r: _Run, p, x: _Act, out=None, gn_next=False) -> _Act:
         c, a = p["c"], p["alpha"]
         hs = self._proj_in(r, p, x)
         # --- spatial block
         hs1 = self._self_attn(r, p["s_attn"], p["s_x"], hs, temporal=False, ln_next=p["s_ff1"])
-        hs_s = self._ff_pair(r, p["s_ff1"], p["s_ff2"], hs1, self._ln_stats(p["s_ff1"], hs1), res1=hs1, r1scale=1.0)
+        hs_s = self._ff_pair(r, p["s_ff1"], p["s_ff2"], hs1.t, self._ln_stats(p["s_ff1"], hs1), res1=hs1.t, r1scale=1.0).t
         # --- frame positional embedding (B*F rows)
         pe = r.pos[c][p["pos_idx"]]
         if r.b > 1:
             pe = pe.repeat(r.b, 1)
         # --- temporal block on hmix = hs_s + pe[frame]
         hmix = self._buf(r.m, c)
-        st = self._ln_stats(p["t_fi1"], hs_s, addvec=pe, addvec_rows=r.hw, sum_out=hmix)   # also writes hmix = hs_s + pe
+        st = self._ln_pass(p["t_fi1"], hs_s, addvec=pe, addvec_rows=r.hw, sum_out=hmix)    # also writes hmix = hs_s + pe
         ht = self._ff_pair(r, p["t_fi1"], p["t_fi2"], hmix, st, res1=hmix, r1scale=1.0, ln_next=p["t_attn"]["qkv"])
         del hmix, st
         ht1 = self._self_attn(r, p["t_attn"], p["t_x"], ht, temporal=True, ln_next=p["t_ff1"])
         # temporal out = ff(..)+ht1 ; blend = a*hs_s + (1-a)*temporal out   (folded into the epilogue)
-        mix = self._ff_pair(r, p["t_ff1"], p["t_ff2"], ht1, self._ln_stats(p["t_ff1"], ht1), oscale=1.0 - a, res1=ht1,
-                            r1scale=1.0 - a, res2=hs_s, r2scale=a)
-        return self._gemm(r, p["pout"], mix, res1=x, r1scale=1.0, out=out, gn_next=gn_next)
+        mix = self._ff_pair(r, p["t_ff1"], p["t_ff2"], ht1.t, self._ln_stats(p["t_ff1"], ht1), oscale=1.0 - a, res1=ht1.t,
+                            r1scale=1.0 - a, res2=hs_s, r2scale=a).t
+        return self._gemm(r, p["pout"], mix, res1=x.t, r1scale=1.0, out=out, gn_next=gn_next)
 
     # ------------------------------------------------------------------ forward
     def forward_rows(self, x_rows, *, b, frames, h, w, t_value, ctx16, added_ids32, euler=None):
@@ -715,78 +654,53 @@ class SVDUNetHIP:
                  frame_ids=torch.arange(frames, dtype=torch.float32, device=dev))
         self._small_gemvs(r)
 
-        # No torch.cat (diffusers' up blocks concatenate the running tensor with a skip in front of every resnet): the
-        # buffer [rows][Cx + Cskip] an up resnet reads is allocated when its skip is PRODUCED in the down path; the skip's
-        # producer writes the right-hand columns in place, and the up path's producer of the running tensor (mid block,
-        # previous resnet / transformer / upsampler) writes the left-hand columns.  Until then the down path keeps
-        # working on the skip through its strided view.
-        cx_pop = [p["cx"] for res, _, _ in self.up for p in res]           # in the order the up path consumes skips
-        cats = []                                                          # in the order the down path produces them
-        cat_sums = []                                                      # per buffer: column sums of its [left, right] halves
-
-        def skip_dest(rows, cskip):
-            cx = cx_pop[len(cx_pop) - 1 - len(cats)]
-            cats.append(self._buf(rows, cx + cskip))
-            cat_sums.append([None, None])
-            return cats[-1][:, cx:]
-
-        def note_skip(t):                      # the skip's producer may have left its column sums beside the view it wrote
-            cat_sums[-1][1] = getattr(t, "_gn_tile_sums", None)
-            return t
-
-        def note_x(t):                         # ... and so may the producer of the running tensor's half
-            if cats and t is not None:
-                cat_sums[-1][0] = getattr(t, "_gn_tile_sums", None)
-            return t
-
+        skips = _Skips(self._buf, [p["cx"] for res, _, _ in self.up for p in res])
         geom, _, _ = self._conv_geom(r)
-        x = note_skip(self._gemm(r, self.conv_in, x_rows, conv=geom, out=skip_dest(r.m, self.conv_in.n_true), gn_next=True))
+        x = skips.right(self._gemm(r, self.conv_in, x_rows, conv=geom, out=skips.right_dest(r.m, self.conv_in.n_true),
+                                   gn_next=True))
         for res, att, ds in self.down:
             for j, p in enumerate(res):
                 if att:
                     x = self._run_resblock(r, p, x, gn_next=True)          # -> the transformer's entry norm
                     # -> the next resnet's norm1, and (as a skip) the first norm of an up resnet
-                    x = note_skip(self._run_transformer(r, att[j], x, out=skip_dest(r.m, p["cout"]), gn_next=True))
+                    x = skips.right(self._run_transformer(r, att[j], x, out=skips.right_dest(r.m, p["cout"]), gn_next=True))
                 else:
-                    x = note_skip(self._run_resblock(r, p, x, out=skip_dest(r.m, p["cout"]), gn_next=True))
+                    x = skips.right(self._run_resblock(r, p, x, out=skips.right_dest(r.m, p["cout"]), gn_next=True))
             if ds is not None:
                 geom, ho, wo = self._conv_geom(r, stride=2)
                 m_out = r.b * r.f * ho * wo
                 r.h, r.w = ho, wo                    # (the output's level decides whether its frames are whole tiles)
-                x = note_skip(self._gemm(r, ds, x, m=m_out, conv=geom, out=skip_dest(m_out, ds.n_true), gn_next=True))
-        if len(cats) != len(cx_pop):
+                x = skips.right(self._gemm(r, ds, x.t, m=m_out, conv=geom, out=skips.right_dest(m_out, ds.n_true),
+                                           gn_next=True))
+        if len(skips.cats) != len(skips.cx):
             raise RuntimeError("skip bookkeeping out of step with the up blocks")
-
-        def x_dest():                          # left-hand columns of the buffer the next up resnet reads (None: no more)
-            return cats[-1][:, :cx_pop[len(cx_pop) - len(cats)]] if cats else None
 
         x = self._run_resblock(r, self.mid[0], x)
         x = self._run_transformer(r, self.mid[1], x)
-        note_x(self._run_resblock(r, self.mid[2], x, out=x_dest(), gn_next=True))
+        skips.left(self._run_resblock(r, self.mid[2], x, out=skips.left_dest(), gn_next=True))
         for res, att, us in self.up:
             for j, p in enumerate(res):
-                cat = cats.pop()               # both halves are in place
-                sums = cat_sums.pop()          # ... and, where both producers left them, the column sums of both
+                cat = skips.pop()              # both halves are in place
                 last = j == len(res) - 1 and us is not None
                 if att:
-                    x = self._run_resblock(r, p, cat, gn_next=True, concat_sums=sums)   # -> the transformer's entry norm
+                    x = self._run_resblock(r, p, cat, gn_next=True)                     # -> the transformer's entry norm
                     # -> the left half of the next up resnet's input, or conv_norm_out at the very end
-                    x = note_x(self._run_transformer(r, att[j], x, out=None if last else x_dest(), gn_next=not last))
+                    x = skips.left(self._run_transformer(r, att[j], x, out=None if last else skips.left_dest(),
+                                                         gn_next=not last))
                 else:
-                    x = note_x(self._run_resblock(r, p, cat, out=None if last else x_dest(), gn_next=not last,
-                                                  concat_sums=sums))
+                    x = skips.left(self._run_resblock(r, p, cat, out=None if last else skips.left_dest(), gn_next=not last))
                 del cat
             if us is not None:
                 geom, ho, wo = self._conv_geom(r, ups=1)
                 m_up = r.b * r.f * ho * wo
                 r.h, r.w = ho, wo                    # (the output's level decides whether its frames are whole tiles)
-                x = note_x(self._gemm(r, us, x, m=m_up, conv=geom, out=x_dest(), gn_next=True))
+                x = skips.left(self._gemm(r, us, x.t, m=m_up, conv=geom, out=skips.left_dest(), gn_next=True))
         x = self._gn(r, self.norm_out, x, temporal=False, silu=True)
         geom, _, _ = self._conv_geom(r)
         if euler is not None:
             self._gemm(r, self.conv_out, x, conv=geom, euler=dict(euler, frames=r.f, hw=r.hw))
             return None
-        return self._gemm(r, self.conv_out, x, conv=geom)
+        return self._gemm(r, self.conv_out, x, conv=geom).t
 
     # diffusers-style call (sample (B,F,8,H,W)) – used by parity tests and as a drop-in `unet`
     def __call__(self, sample, timestep, encoder_hidden_states, added_time_ids, return_dict=False, per_video=False):

@@ -36,7 +36,8 @@ from typing import Iterator, Sequence
 import torch
 
 from ..hip import ops
-from .unet_hip import _Dense, _Norm, _f32
+from . import common
+from .common import _Act, _Dense, _Norm, _f32
 
 
 @dataclass
@@ -192,10 +193,7 @@ class _VAEKernels:
 
     def _init_common(self, cfg, device):
         self.cfg = cfg
-        self.device = dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError(f"{type(self).__name__} runs on an MI355X HIP device only (no CPU fallback)")
-        ops.load()  # fail loudly now if the extension is missing
+        self.device = dev = common.hip_device(device, type(self).__name__)
         if any(v % 64 for v in cfg.block_out_channels):
             raise ValueError("block_out_channels must be multiples of 64 (MFMA K-steps)")
         self._ws = {}
@@ -215,11 +213,11 @@ class _VAEKernels:
     def _buf(self, rows, c):
         return torch.empty((rows, c), dtype=torch.float16, device=self.device)
 
-    def _gemm(self, layer: _Dense, a, m, *, conv=None, temporal=None, gn_rows=0, **kw):
-        """``gn_rows`` > 0: the output goes straight into a GroupNorm whose instances are multiples of that many rows (a
-        frame): where the tiles allow it (256- / 320-wide column tiles, whole 256-row tiles per frame) the epilogue leaves
-        per-tile column sums beside the output and ``_gn`` folds them instead of reading the tensor again (round 5,
-        ``sp_gemm_desc.gn_part``; the 128-channel level has no such tiles)."""
+    def _gemm(self, layer: _Dense, a, m, *, conv=None, temporal=None, gn_rows=0, **kw) -> _Act:
+        """One contraction on the plain tensor ``a``.  ``gn_rows`` > 0: the output goes straight into a GroupNorm whose
+        instances are multiples of that many rows (a frame): where the tiles allow it (256- / 320-wide column tiles, whole
+        256-row tiles per frame) the epilogue leaves per-tile column sums in the returned record and ``_gn`` folds them
+        instead of reading the tensor again (round 5, ``sp_gemm_desc.gn_part``; the 128-channel level has no such tiles)."""
         out = kw.pop("out", None)
         if out is None:
             out = self._buf(m, layer.n_true)
@@ -231,17 +229,15 @@ class _VAEKernels:
             kw.update(gn_part=part)
         ops.gemm(a, layer.w, out, m=m, n=layer.n, cin=layer.cin, mode=layer.mode, conv=conv, temporal=temporal,
                  bias=layer.bias, n_store=n_store, ldd=layer.n_true, lda=a.shape[1], **kw)
-        if part is not None:
-            out._gn_tile_sums = (part, out.data_ptr(), tuple(out.shape))
-        return out
+        return _Act(out, gn_part=part)
 
-    def _gn(self, norm: _Norm, x, inst, rows, silu):
-        c = x.shape[1]
-        have = getattr(x, "_gn_tile_sums", None)
-        if have is not None and have[1] == x.data_ptr() and have[2] == tuple(x.shape) and rows % 256 == 0:
+    def _gn(self, norm: _Norm, a: _Act, inst, rows, silu):
+        """GroupNorm of ``a`` -> plain tensor; the column sums a's producer left replace the statistics pass."""
+        x, c = a.t, a.t.shape[1]
+        if a.gn_part is not None and rows % 256 == 0:
             y = self._buf(x.shape[0], c)
             stats = torch.empty((inst, self.cfg.norm_groups, 2), dtype=torch.float32, device=self.device)
-            ops.groupnorm_tile_sums(x, have[0], norm.g, norm.b, y, instances=inst, rows=rows, c=c, groups=self.cfg.norm_groups,
+            ops.groupnorm_tile_sums(x, a.gn_part, norm.g, norm.b, y, instances=inst, rows=rows, c=c, groups=self.cfg.norm_groups,
                                     eps=norm.eps, silu=silu, stats=stats)
             return y
         need = ops.groupnorm_ws_bytes(inst, rows, c, self.cfg.norm_groups)
@@ -254,14 +250,14 @@ class _VAEKernels:
                       silu=silu, ws=ws)
         return y
 
-    def _run_attn(self, p, x, n_img, hw):
+    def _run_attn(self, p, x: _Act, n_img, hw) -> _Act:
         """diffusers ``Attention(heads=1, dim_head=C, norm_num_groups=32, residual_connection=True)`` per image."""
         c, m = p["c"], n_img * hw
         if hw % 64:
             raise ValueError(f"mid-block attention: H*W = {hw} tokens per image must be a multiple of 64")
         t = self._gn(p["norm"], x, n_img, hw, False)
-        q = self._gemm(p["q"], t, m)
-        k = self._gemm(p["k"], t, m)
+        q = self._gemm(p["q"], t, m).t
+        k = self._gemm(p["k"], t, m).t
         o = self._buf(m, c)
         vt = self._buf(c, hw)
         scale = 1.0 / math.sqrt(c)
@@ -289,7 +285,7 @@ class _VAEKernels:
                 ops.gemm(scores, vt, o[r], m=hw, n=c, cin=hw, bias=p["bv"])                # O = P V + b_v
             del scores
         del vt, q, k, t
-        return self._gemm(p["out"], o, m, res1=x, r1scale=1.0, gn_rows=hw)
+        return self._gemm(p["out"], o, m, res1=x.t, r1scale=1.0, gn_rows=hw)
 
 
 class TemporalDecoderHIP(_VAEKernels):
@@ -337,7 +333,7 @@ class TemporalDecoderHIP(_VAEKernels):
                     tn2=_Norm(sd, t + ".norm2", dev, 1e-5), tc2=_Dense.tconv(sd, t + ".conv2", dev))
 
     # ------------------------------------------------------------------ blocks
-    def _run_res(self, p, x, b, f, h, w, gn_next=True):
+    def _run_res(self, p, x: _Act, b, f, h, w, gn_next=True) -> _Act:
         """SpatioTemporalResBlock(temb_channels=None): ResnetBlock2D per frame, TemporalResnetBlock over the frames,
         blended by the (switched) AlphaBlender."""
         hw, m = h * w, b * f * h * w
@@ -345,14 +341,14 @@ class TemporalDecoderHIP(_VAEKernels):
         t = self._gn(p["n1"], x, b * f, hw, True)
         t = self._gemm(p["c1"], t, m, conv=geom, gn_rows=hw)
         t = self._gn(p["n2"], t, b * f, hw, True)
-        skip = x if p["sc"] is None else self._gemm(p["sc"], x, m)
-        s = self._gemm(p["c2"], t, m, conv=geom, res1=skip, r1scale=1.0, gn_rows=hw)
+        skip = x if p["sc"] is None else self._gemm(p["sc"], x.t, m)
+        s = self._gemm(p["c2"], t, m, conv=geom, res1=skip.t, r1scale=1.0, gn_rows=hw)
         del t, skip
         t = self._gn(p["tn1"], s, b, f * hw, True)
         t = self._gemm(p["tc1"], t, m, temporal=(f, hw), gn_rows=hw)
         t = self._gn(p["tn2"], t, b, f * hw, True)
         # (1-sig)*s + sig*(s + conv2(t)) = s + sig*conv2(t)
-        return self._gemm(p["tc2"], t, m, temporal=(f, hw), oscale=p["temporal_weight"], res1=s, r1scale=1.0,
+        return self._gemm(p["tc2"], t, m, temporal=(f, hw), oscale=p["temporal_weight"], res1=s.t, r1scale=1.0,
                           gn_rows=hw if gn_next else 0)
 
     # ------------------------------------------------------------------ public
@@ -374,10 +370,10 @@ class TemporalDecoderHIP(_VAEKernels):
                 # (a level's last resnet feeds the upsampling convolution: no norm behind it)
                 x = self._run_res(p, x, b, f, h, w, gn_next=not (us is not None and j == len(res) - 1))
             if us is not None:
-                x = self._gemm(us, x, n * 4 * h * w, conv=(n, h, w, 2 * h, 2 * w, 1, 1), gn_rows=4 * h * w)
+                x = self._gemm(us, x.t, n * 4 * h * w, conv=(n, h, w, 2 * h, 2 * w, 1, 1), gn_rows=4 * h * w)
                 h, w = 2 * h, 2 * w
         x = self._gn(self.norm_out, x, n, h * w, True)
-        x = self._gemm(self.conv_out, x, n * h * w, conv=(n, h, w, h, w, 1, 0))
+        x = self._gemm(self.conv_out, x, n * h * w, conv=(n, h, w, h, w, 1, 0)).t
         ops.vae_frames_out(x, self.tco_w, self.tco_b, dst, batch=b, frames=f, h=h, w=w, flat0=flat0,
                            frames_per_item=frames_per_item, strides=dst_strides)
 
@@ -481,13 +477,13 @@ class ImageEncoderHIP(_VAEKernels):
                     n2=_Norm(sd, p + ".norm2", dev, 1e-6), c2=_Dense.conv3x3(sd, p + ".conv2", dev),
                     sc=_Dense.linear(sd, p + ".conv_shortcut", dev) if cin != cout else None)
 
-    def _run_res2d(self, p, x, n, h, w):
+    def _run_res2d(self, p, x: _Act, n, h, w) -> _Act:
         m, geom = n * h * w, (n, h, w, h, w, 1, 0)
         t = self._gn(p["n1"], x, n, h * w, True)
         t = self._gemm(p["c1"], t, m, conv=geom)
         t = self._gn(p["n2"], t, n, h * w, True)
-        skip = x if p["sc"] is None else self._gemm(p["sc"], x, m)
-        return self._gemm(p["c2"], t, m, conv=geom, res1=skip, r1scale=1.0)
+        skip = x if p["sc"] is None else self._gemm(p["sc"], x.t, m)
+        return self._gemm(p["c2"], t, m, conv=geom, res1=skip.t, r1scale=1.0)
 
     def encode_image_latents(self, image, num_frames: int):
         """image: fp16 (B, 3, H, W) in [-1, 1], noise augmentation already added (ref :126-136).  Returns the
@@ -510,13 +506,13 @@ class ImageEncoderHIP(_VAEKernels):
             for p in res:
                 x = self._run_res2d(p, x, n, h, w)
             if ds is not None:
-                x = self._gemm(ds, x, n * (h // 2) * (w // 2), conv=(n, h, w, h // 2, w // 2, 2, 0))
+                x = self._gemm(ds, x.t, n * (h // 2) * (w // 2), conv=(n, h, w, h // 2, w // 2, 2, 0))
                 h, w = h // 2, w // 2
         x = self._run_res2d(self.mid[0], x, n, h, w)
         x = self._run_attn(self.mid[1], x, n, h * w)
         x = self._run_res2d(self.mid[2], x, n, h, w)
         x = self._gn(self.norm_out, x, n, h * w, True)
-        x = self._gemm(self.conv_out, x, n * h * w, conv=(n, h, w, h, w, 1, 0))
+        x = self._gemm(self.conv_out, x, n * h * w, conv=(n, h, w, h, w, 1, 0)).t
         out = torch.empty((n, self.cfg.latent_channels, num_frames, h, w), dtype=torch.float16, device=self.device)
         ops.vae_latent_out(x, out, batch=n, channels=self.cfg.latent_channels, frames=num_frames, h=h, w=w, flip=True)
         return out
