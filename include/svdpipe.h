@@ -349,6 +349,12 @@ int sp_vae_pack_latent_f16(const void *latent, void *rows, float scale, int64_t 
 int sp_vae_frames_out_f16(const void *rows, int64_t ld, const float *weight, const float *bias, void *out,
                           int out_fp32, int batch, int frames, int h, int w, int64_t flat0, int F, int64_t sb,
                           int64_t sc, int64_t sf, void *stream);
+/* The same time_conv_out values as 8-bit frames: each fp32 value goes through the arithmetic of sp_frames_to_u8 (below) and
+ * is stored at out[((flat0 + i)*h*w + p)*3 + c] for entry i of the call, pixel p, channel c -- a dense (B*F, H, W, 3) uint8
+ * tensor, a quarter of the fp32 video's bytes.  Byte for byte what sp_frames_to_u8 makes of sp_vae_frames_out_f16(out_fp32 = 1):
+ * both kernels share one device function for the value and one for the level. */
+int sp_vae_frames_out_u8(const void *rows, int64_t ld, const float *weight, const float *bias, void *out, int batch,
+                         int frames, int h, int w, int64_t flat0, void *stream);
 
 /* Encoder half (vae.encode(image).latent_dist.mode(), generate_video_demo.py:139-148).  flip != 0 mirrors the image in
  * both axes between the tensor and the rows (pixel (y,x) <-> row (H-1-y)*W + (W-1-x)): the engine runs the encoder on
@@ -376,6 +382,31 @@ int sp_attn_small_f16(const void *q, const void *k, const void *v, void *o, int6
 /* y = gelu(x) elementwise over n fp16 values (n a multiple of 8): exact erf form (hidden_act "gelu"), or
  * x*sigmoid(1.702 x) when quick != 0 ("quick_gelu"). */
 int sp_gelu_f16(const void *x, void *y, int64_t n, int quick, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Image in, 8-bit frames out: the host-side image handling of /root/reference/scripts/generate_video_demo.py on the device
+ * (load_and_preprocess_image :71-89, the CLIPImageProcessor / ToTensor / Normalize of encode_image :108-126, and the
+ * uint8 conversion of save_video :198-209).  Images are uint8 RGB, interleaved [h][w][3]; row pitches are in BYTES and may be
+ * any value >= 3*w (no alignment is assumed), so a crop is a pointer into a larger image plus that image's pitch.
+ * ------------------------------------------------------------------------------------------- */
+enum { SP_FILTER_BICUBIC = 0 /* a = -0.5, support 2 */, SP_FILTER_LANCZOS3 = 1 /* support 3 */ };
+/* Pillow's antialiased separable resize (Image.resize with BICUBIC / LANCZOS): the horizontal pass writes src_h x dst_w
+ * pixels to `tmp`, the vertical pass reads them; a pass whose size does not change is a copy.  Per axis, with scale =
+ * in/out, fs = max(scale, 1), support = S*fs: output i has centre = (i + 0.5)*scale and taps k in [max(0, int(centre -
+ * support + 0.5)), min(in, int(centre + support + 0.5))) weighted filter((k - centre + 0.5)/fs), normalised by the sum of
+ * the taps kept; the result is floor(v + 0.5) clipped to [0, 255] and is stored as uint8 between the passes as well.
+ * Geometry in fp64, weights and sums in fp32: within one level of Pillow (whose weights are 22-bit fixed point).
+ * tmp: >= sp_image_resample_tmp_bytes(src_h, dst_w) = src_h*dst_w*3 bytes, owned by the caller. */
+size_t sp_image_resample_tmp_bytes(int src_h, int dst_w);
+int sp_image_resample_u8(const void *src, int64_t src_pitch, int src_h, int src_w, void *dst, int64_t dst_pitch, int dst_h,
+                         int dst_w, int filter, void *tmp, size_t tmp_bytes, void *stream);
+/* uint8 [h][w][3] -> fp16 planar (3, h, w): out[c][y][x] = fp16((float(v)/255.0f - mean[c]) / std[c]).  torchvision's
+ * ToTensor + Normalize([0.5], [0.5]) (the VAE's input) and the rescale + normalize of the CLIPImageProcessor. */
+int sp_image_to_tensor_f16(const void *src, int64_t src_pitch, int h, int w, void *out, float mean0, float mean1, float mean2,
+                           float std0, float std1, float std2, void *stream);
+/* video (B, 3, F, H, W) fp16 (is_fp32 == 0) or fp32 -> uint8 (B, F, H, W, 3): v = ((x + 1.0f)/2.0f)*255.0f in fp32, clamped to
+ * [0, 255] and truncated, as ((frames + 1) / 2 * 255).clamp(0, 255).to(torch.uint8) does; a NaN gives 0. */
+int sp_frames_to_u8(const void *frames, int is_fp32, void *out, int batch, int frames_n, int h, int w, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Measurement aid (bench.py `roofline.clock_ghz_live`; the reference has no counterpart -- its benchmark reads no clocks,

@@ -82,6 +82,14 @@ __device__ __forceinline__ f32x2 gelu2_f(f32x2 v) {
   return __builtin_elementwise_fma(av, e, v * 0.5f);
 }
 
+// A frame value in [-1, 1] as an 8-bit level, the reference's ((x + 1) / 2 * 255).clamp(0, 255).to(torch.uint8)
+// (/root/reference/scripts/generate_video_demo.py:205): fp32, truncated; +-inf clamp, a NaN gives 0 (fmaxf drops it).
+// The one definition sp_frames_to_u8 and sp_vae_frames_out_u8 share.
+__device__ __forceinline__ unsigned char frame_level_u8(float x) {
+  const float v = ((x + 1.0f) / 2.0f) * 255.0f;
+  return (unsigned char)(int)fminf(fmaxf(v, 0.0f), 255.0f);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

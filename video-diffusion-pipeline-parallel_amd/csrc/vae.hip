@@ -9,6 +9,8 @@
 //   pack_latent_kernel  : a chunk of latent frames / scaling_factor -> channels-last rows (the decoder's input).
 //   frames_out_kernel   : time_conv_out -- Conv3d(3 -> 3, kernel (3,1,1), zero padding in time) -- on the channels-last
 //                         rows conv_out wrote, stored straight into the video tensor the caller returns.  HBM-bound.
+//   frames_out_u8_kernel: the same values stored as interleaved 8-bit frames (what save_video makes of the fp32 tensor,
+//                         generate_video_demo.py:205), a quarter of the bytes.
 #include "common.h"
 
 namespace {
@@ -136,16 +138,13 @@ __global__ void pack_latent_kernel(const f16 *__restrict__ lat, f16 *__restrict_
   for (int c = 8; c < cpad; c += 8) *(f16x8 *)(o + c) = z;
 }
 
-// one thread per (frame, pixel): out[g][co][p] = b[co] + sum_{tap, ci} w[co][ci][tap] * in[f + tap - 1][p][ci]
-template <typename OUT>
-__global__ void frames_out_kernel(const f16 *__restrict__ rows, int64_t ld, const float *__restrict__ w,
-                                  const float *__restrict__ b, OUT *__restrict__ out, int frames, int64_t hw,
-                                  int64_t total, int64_t flat0, int F, int64_t sb, int64_t sc, int64_t sf) {
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total) return;
-  const int64_t p = idx % hw, bf = idx / hw;
-  const int f = (int)(bf % frames);
-  float acc[3] = {b[0], b[1], b[2]};
+// time_conv_out of one (frame, pixel): acc[co] = b[co] + sum_{tap, ci} w[co][ci][tap] * in[f + tap - 1][p][ci], fp32.  idx is the
+// row of `rows` (chunk-relative (frame, pixel)), f its frame within the chunk's item.  The one statement of the value both
+// frames_out kernels store.
+__device__ __forceinline__ void time_conv_out_px(const f16 *__restrict__ rows, int64_t ld, const float *__restrict__ w,
+                                                 const float *__restrict__ b, int64_t idx, int f, int frames, int64_t hw,
+                                                 float (&acc)[3]) {
+  acc[0] = b[0]; acc[1] = b[1]; acc[2] = b[2];
 #pragma unroll
   for (int tap = 0; tap < 3; ++tap) {
     const int ff = f + tap - 1;
@@ -156,10 +155,53 @@ __global__ void frames_out_kernel(const f16 *__restrict__ rows, int64_t ld, cons
 #pragma unroll
       for (int ci = 0; ci < 3; ++ci) acc[co] = fmaf(w[(co * 3 + ci) * 3 + tap], (float)v[ci], acc[co]);
   }
+}
+
+// one thread per (frame, pixel)
+template <typename OUT>
+__global__ void frames_out_kernel(const f16 *__restrict__ rows, int64_t ld, const float *__restrict__ w,
+                                  const float *__restrict__ b, OUT *__restrict__ out, int frames, int64_t hw,
+                                  int64_t total, int64_t flat0, int F, int64_t sb, int64_t sc, int64_t sf) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const int64_t p = idx % hw, bf = idx / hw;
+  float acc[3];
+  time_conv_out_px(rows, ld, w, b, idx, (int)(bf % frames), frames, hw, acc);
   const int64_t g = flat0 + bf;
   OUT *dst = out + (g / F) * sb + (g % F) * sf + p;
 #pragma unroll
   for (int co = 0; co < 3; ++co) dst[co * sc] = (OUT)acc[co];
+}
+
+// The same values as 8-bit levels (frame_level_u8), interleaved: out[((flat0 + bf)*hw + p)*3 + c], dense (B*F, H, W, 3).
+// One thread per PX consecutive pixels of a frame; PX = 4 (hw % 4 == 0, out 4-byte aligned) stores 12 packed bytes.
+template <int PX>
+__global__ void frames_out_u8_kernel(const f16 *__restrict__ rows, int64_t ld, const float *__restrict__ w,
+                                     const float *__restrict__ b, unsigned char *__restrict__ out, int frames, int64_t hw,
+                                     int64_t total, int64_t flat0) {
+  const int64_t idx = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * PX;
+  if (idx >= total) return;
+  const int f = (int)((idx / hw) % frames);
+  unsigned char v[3 * PX];
+#pragma unroll
+  for (int e = 0; e < PX; ++e) {
+    float acc[3];
+    time_conv_out_px(rows, ld, w, b, idx + e, f, frames, hw, acc);
+#pragma unroll
+    for (int co = 0; co < 3; ++co) v[3 * e + co] = frame_level_u8(acc[co]);
+  }
+  unsigned char *dst = out + (flat0 * hw + idx) * 3;
+  if (PX == 4) {
+    typedef unsigned int u32x3 __attribute__((ext_vector_type(3)));
+    u32x3 o;
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+      o[d] = (unsigned)v[4 * d] | ((unsigned)v[4 * d + 1] << 8) | ((unsigned)v[4 * d + 2] << 16) | ((unsigned)v[4 * d + 3] << 24);
+    *(u32x3 *)dst = o;
+  } else {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) dst[c] = v[c];
+  }
 }
 
 // Encoder ends.  `flip`: rows hold the image mirrored in both axes (pixel (y, x) at row (H-1-y)*W + (W-1-x)); see
@@ -271,6 +313,27 @@ extern "C" int sp_vae_frames_out_f16(const void *rows, int64_t ld, const float *
     hipLaunchKernelGGL(frames_out_kernel<f16>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        (const f16 *)rows, ld, weight, bias, (f16 *)out, frames, hw, total, flat0, F, sb, sc, sf);
   SP_CHECK_LAUNCH("sp_vae_frames_out_f16");
+  return SP_OK;
+}
+
+extern "C" int sp_vae_frames_out_u8(const void *rows, int64_t ld, const float *weight, const float *bias, void *out, int batch,
+                                    int frames, int h, int w, int64_t flat0, void *stream) {
+  SP_REQUIRE(rows && weight && bias && out, "sp_vae_frames_out_u8: null pointer");
+  SP_REQUIRE(batch > 0 && frames > 0 && h > 0 && w > 0 && ld >= 4 && ld % 4 == 0,
+             "sp_vae_frames_out_u8: bad shape (ld=%lld must be a multiple of 4, >= 4)", (long long)ld);
+  SP_REQUIRE(flat0 >= 0, "sp_vae_frames_out_u8: flat0 must not be negative");
+  const int64_t hw = (int64_t)h * w, total = (int64_t)batch * frames * hw;
+  SP_REQUIRE((total + 255) / 256 <= 0x7fffffff, "sp_vae_frames_out_u8: too many pixels");
+  const bool vec = hw % 4 == 0 && (uintptr_t)out % 4 == 0;
+  const dim3 grid((unsigned)(((vec ? total / 4 : total) + 255) / 256));
+  SP_CLEAR_STALE_ERROR();
+  if (vec)
+    hipLaunchKernelGGL(frames_out_u8_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, (const f16 *)rows, ld, weight, bias,
+                       (unsigned char *)out, frames, hw, total, flat0);
+  else
+    hipLaunchKernelGGL(frames_out_u8_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, (const f16 *)rows, ld, weight, bias,
+                       (unsigned char *)out, frames, hw, total, flat0);
+  SP_CHECK_LAUNCH("sp_vae_frames_out_u8");
   return SP_OK;
 }
 

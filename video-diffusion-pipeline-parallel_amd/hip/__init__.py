@@ -82,11 +82,16 @@ SIGNATURES = {
     "sp_softmax_rows_f32": (_I, [_P, _L, _P, _L, _L, _I, _F, _P]),
     "sp_vae_pack_latent_f16": (_I, [_P, _P, _F, _L, _I, _I, _L, _L, _L, _I, _I, _I, _P]),
     "sp_vae_frames_out_f16": (_I, [_P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _L, _I, _L, _L, _L, _P]),
+    "sp_vae_frames_out_u8": (_I, [_P, _L, _P, _P, _P, _I, _I, _I, _I, _L, _P]),
     "sp_vae_image_pack_f16": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "sp_vae_latent_out_f16": (_I, [_P, _L, _P, _I, _I, _I, _I, _I, _I, _P]),
     "sp_patchify_f16": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "sp_attn_small_f16": (_I, [_P, _P, _P, _P, _L, _L, _L, _L, _I, _I, _I, _I, _F, _P]),
     "sp_gelu_f16": (_I, [_P, _P, _L, _I, _P]),
+    "sp_image_resample_tmp_bytes": (_Z, [_I, _I]),
+    "sp_image_resample_u8": (_I, [_P, _L, _I, _I, _P, _L, _I, _I, _I, _P, _Z, _P]),
+    "sp_image_to_tensor_f16": (_I, [_P, _L, _I, _I, _P, _F, _F, _F, _F, _F, _F, _P]),
+    "sp_frames_to_u8": (_I, [_P, _I, _P, _I, _I, _I, _I, _P]),
     "sp_clock_stamp": (_I, [_P, _I, _P]),
     "sp_dummy_unet_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _I, _I, _I, _I, _I, _I, _P]),
 }

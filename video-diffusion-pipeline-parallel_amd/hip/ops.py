@@ -372,6 +372,19 @@ def vae_frames_out(rows, weight, bias, out, *, batch, frames, h, w, flat0, frame
     return out
 
 
+def vae_frames_out_u8(rows, weight, bias, out, *, batch, frames, h, w, flat0):
+    """time_conv_out of a decoder call stored as 8-bit frames: ``out`` is the dense (B*F, H, W, 3) uint8 video (any leading
+    shape), the call writes entries flat0 .. flat0 + batch*frames - 1."""
+    if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous():
+        raise TypeError("vae_frames_out_u8: out must be a contiguous uint8 tensor on a HIP device")
+    if (flat0 + batch * frames) * h * w * 3 > out.numel():
+        raise ValueError("vae_frames_out_u8: the call's entries do not fit in out")
+    with _Timed("vae_frames_out", 0.0, batch * frames * h * w * (2.0 * rows.shape[1] + 3)):
+        _check(load().sp_vae_frames_out_u8(_f16(rows, "rows").data_ptr(), rows.shape[1], weight.data_ptr(), bias.data_ptr(),
+                                           out.data_ptr(), batch, frames, h, w, flat0, _stream()), "sp_vae_frames_out_u8")
+    return out
+
+
 def vae_image_pack(image, rows, *, batch, h, w, cpad, flip):
     _check(load().sp_vae_image_pack_f16(_f16(image, "image").data_ptr(), _f16(rows, "rows").data_ptr(), batch, h, w, cpad,
                                         int(flip), _stream()), "sp_vae_image_pack_f16")
@@ -400,6 +413,64 @@ def attn_small(q, k, v, o, *, ldq, ldk, ldv, ldo, batch, seq, heads, head_dim, s
 def gelu(x, y, *, quick=False):
     _check(load().sp_gelu_f16(_f16(x, "x").data_ptr(), _f16(y, "y").data_ptr(), x.numel(), int(quick), _stream()), "sp_gelu_f16")
     return y
+
+
+FILTER_BICUBIC, FILTER_LANCZOS3 = 0, 1
+
+
+def _image_u8(t: torch.Tensor, name: str) -> torch.Tensor:
+    """Interleaved uint8 RGB (h, w, 3) on the device; rows may be any pitch >= 3*w bytes (a crop is a slice)."""
+    if t.dtype != torch.uint8 or not t.is_cuda or t.dim() != 3 or t.shape[2] != 3:
+        raise TypeError(f"{name} must be a uint8 (h, w, 3) tensor on a HIP device")
+    if t.stride(2) != 1 or (t.shape[1] > 1 and t.stride(1) != 3) or (t.shape[0] > 1 and t.stride(0) < 3 * t.shape[1]):
+        raise ValueError(f"{name} must hold interleaved pixels in rows (strides (pitch, 3, 1)); got {tuple(t.stride())}")
+    return t
+
+
+def _pitch(t: torch.Tensor) -> int:
+    return t.stride(0) if t.shape[0] > 1 else 3 * t.shape[1]      # (the stride of a dimension of one is arbitrary)
+
+
+def image_resample_tmp_bytes(src_h: int, dst_w: int) -> int:
+    return int(load().sp_image_resample_tmp_bytes(src_h, dst_w))
+
+
+def image_resample_u8(src, dst, tmp, *, filter):
+    """Pillow's antialiased resize of ``src`` (h, w, 3) into ``dst`` (h', w', 3), both uint8 and possibly slices of larger
+    images; ``tmp``: uint8 scratch of at least ``image_resample_tmp_bytes(h, w')`` bytes."""
+    _image_u8(src, "src"), _image_u8(dst, "dst")
+    if tmp.dtype != torch.uint8 or not tmp.is_cuda or not tmp.is_contiguous():
+        raise TypeError("image_resample_u8: tmp must be a contiguous uint8 tensor on a HIP device")
+    _check(load().sp_image_resample_u8(src.data_ptr(), _pitch(src), src.shape[0], src.shape[1], dst.data_ptr(), _pitch(dst),
+                                       dst.shape[0], dst.shape[1], int(filter), tmp.data_ptr(), tmp.numel(), _stream()),
+           "sp_image_resample_u8")
+    return dst
+
+
+def image_to_tensor(src, out, *, mean, std):
+    """uint8 (h, w, 3) -> fp16 planar (3, h, w) = (v/255 - mean[c]) / std[c]; ``src`` may be a slice of a larger image."""
+    _image_u8(src, "src")
+    h, w = src.shape[0], src.shape[1]
+    if not out.is_contiguous() or out.numel() != 3 * h * w:
+        raise ValueError("image_to_tensor: out must be a contiguous tensor of 3*h*w values")
+    m, s = [float(v) for v in mean], [float(v) for v in std]
+    _check(load().sp_image_to_tensor_f16(src.data_ptr(), _pitch(src), h, w, _f16(out, "out").data_ptr(), m[0], m[1], m[2],
+                                         s[0], s[1], s[2], _stream()), "sp_image_to_tensor_f16")
+    return out
+
+
+def frames_to_u8(frames, out):
+    """(B, 3, F, H, W) fp16 / fp32 -> uint8 (B, F, H, W, 3): ((x + 1) / 2 * 255).clamp(0, 255), truncated; NaN gives 0."""
+    if frames.dtype not in (torch.float16, torch.float32) or not frames.is_cuda or not frames.is_contiguous():
+        raise TypeError("frames_to_u8: frames must be a contiguous float16 or float32 tensor on a HIP device")
+    if frames.dim() != 5 or frames.shape[1] != 3:
+        raise ValueError(f"frames_to_u8: frames must be (B, 3, F, H, W); got {tuple(frames.shape)}")
+    b, _, f, h, w = frames.shape
+    if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or tuple(out.shape) != (b, f, h, w, 3):
+        raise TypeError(f"frames_to_u8: out must be a contiguous uint8 tensor of shape {(b, f, h, w, 3)} on a HIP device")
+    _check(load().sp_frames_to_u8(frames.data_ptr(), int(frames.dtype == torch.float32), out.data_ptr(), b, f, h, w, _stream()),
+           "sp_frames_to_u8")
+    return out
 
 
 class ClockStamps:

@@ -52,6 +52,61 @@ class CLIPVisionSpec:
                               cfg.image_size, cfg.patch_size, cfg.projection_dim, cfg.layer_norm_eps, cfg.hidden_act)
 
 
+    @staticmethod
+    def tiny(projection_dim: int = 128) -> "CLIPVisionSpec":
+        """A 56-pixel, three-layer encoder (the shape of tests/golden/clip_tiny.npz) projecting to the cross-attention
+        width of ``UNetConfig.tiny``: quick end-to-end runs with random weights."""
+        return CLIPVisionSpec(128, 512, 3, 2, 56, 14, projection_dim, 1e-5, "quick_gelu")
+
+
+def param_inventory(spec: CLIPVisionSpec):
+    """(name, shape, fan) of ``CLIPVisionModelWithProjection`` (transformers naming); fan > 0: weight/bias of a layer with
+    that fan-in, 0: norm scale, -1: norm bias, -3: embedding table."""
+    c, v = spec.hidden_size, "vision_model."
+
+    def lin(p, cin, cout, bias=True):
+        yield p + ".weight", (cout, cin), cin
+        if bias:
+            yield p + ".bias", (cout,), cin
+
+    def norm(p):
+        yield p + ".weight", (c,), 0
+        yield p + ".bias", (c,), -1
+
+    e = v + "embeddings"
+    yield e + ".class_embedding", (c,), -3
+    yield e + ".patch_embedding.weight", (c, 3, spec.patch_size, spec.patch_size), 3 * spec.patch_size ** 2
+    yield e + ".position_embedding.weight", ((spec.image_size // spec.patch_size) ** 2 + 1, c), -3
+    yield from norm(v + "pre_layrnorm")
+    for i in range(spec.num_hidden_layers):
+        p = f"{v}encoder.layers.{i}"
+        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            yield from lin(f"{p}.self_attn.{n}", c, c)
+        yield from norm(p + ".layer_norm1")
+        yield from lin(p + ".mlp.fc1", c, spec.intermediate_size)
+        yield from lin(p + ".mlp.fc2", spec.intermediate_size, c)
+        yield from norm(p + ".layer_norm2")
+    yield from norm(v + "post_layernorm")
+    yield from lin("visual_projection", c, spec.projection_dim, bias=False)
+
+
+def random_state_dict(spec: CLIPVisionSpec, seed: int = 0, device="cpu", dtype=torch.float16) -> dict:
+    """Random weights of the exact architecture (``nn.Linear`` default ranges, norm scale ~1, embeddings ~0.02)."""
+    gen = torch.Generator(device=device).manual_seed(seed)
+    sd = {}
+    for name, shape, fan in param_inventory(spec):
+        if fan > 0:
+            t = (torch.rand(shape, generator=gen, device=device) * 2 - 1) / math.sqrt(fan)
+        elif fan == 0:
+            t = 1.0 + 0.1 * (torch.rand(shape, generator=gen, device=device) - 0.5)
+        elif fan == -1:
+            t = 0.1 * (torch.rand(shape, generator=gen, device=device) - 0.5)
+        else:
+            t = 0.02 * torch.randn(shape, generator=gen, device=device)
+        sd[name] = t.to(dtype)
+    return sd
+
+
 class CLIPVisionHIP:
     """``CLIPVisionModelWithProjection.forward(pixel_values).image_embeds`` on a HIP device."""
 

@@ -4,6 +4,9 @@ the last rank (``:154-195``), on the HIP engines of ``clip_hip.py`` / ``vae_hip.
 
 Same argument meaning and return values as the script's functions, minus what is host-side image handling there: the
 ``CLIPImageProcessor`` output (``pixel_values``) and the normalised image tensor are arguments instead of a PIL image.
+``encode_image_u8`` takes the picture itself (uint8 pixels) and makes those two tensors on the device
+(``image_io.ImageFrontEnd``); ``decode_latents_uint8`` / ``FrameEmitter(output="uint8")`` end in the 8-bit frames the
+script's ``save_video`` writes.
 """
 
 from __future__ import annotations
@@ -86,11 +89,30 @@ def encode_image(pixel_values: torch.Tensor, image_tensor: torch.Tensor, image_e
     return emb, latents
 
 
+def encode_image_u8(image_u8, front_end, image_encoder: CLIPVisionHIP, vae_encoder: ImageEncoderHIP, num_frames: int,
+                    noise: torch.Tensor | None = None, noise_aug_strength: float = 0.0) -> tuple[torch.Tensor, torch.Tensor]:
+    """``encode_image`` from the picture itself: ``image_u8`` (H, W, 3) uint8 of any size goes through ``front_end`` (an
+    ``image_io.ImageFrontEnd``: the reference's cover-resize and crop, then the CLIP processor and ``ToTensor`` /
+    ``Normalize`` on the cropped picture), the two tensors it returns through ``encode_image``.  ``noise``: as there,
+    shaped like the image tensor (1, 3, height, width)."""
+    pixel_values, image_tensor, _ = front_end(image_u8)
+    return encode_image(pixel_values, image_tensor, image_encoder, vae_encoder, num_frames, noise=noise,
+                        noise_aug_strength=noise_aug_strength)
+
+
 def decode_latents(latents: torch.Tensor, vae: TemporalDecoderHIP, num_frames: int,
                    decode_chunk_size: int = 14) -> torch.Tensor:
     """(B, 4, F, H, W) latents -> (B, 3, F, 8H, 8W) fp32 frames (ref ``:154-195``)."""
     return vae.decode_latents(latents.to(vae.device, torch.float16).contiguous(), num_frames,
                               decode_chunk_size=decode_chunk_size)
+
+
+def decode_latents_uint8(latents: torch.Tensor, vae: TemporalDecoderHIP, num_frames: int,
+                         decode_chunk_size: int = 14) -> torch.Tensor:
+    """(B, 4, F, H, W) latents -> (B, F, 8H, 8W, 3) uint8 frames: ``decode_latents`` and the conversion of ``save_video``
+    (ref ``:205``) in one, without the fp32 video in between."""
+    return vae.decode_latents_uint8(latents.to(vae.device, torch.float16).contiguous(), num_frames,
+                                    decode_chunk_size=decode_chunk_size)
 
 
 class FrameEmitter:
@@ -118,14 +140,22 @@ class FrameEmitter:
         emitter = FrameEmitter(decoder, stage, num_frames)            # every rank
         stage.run_many(K, input_supplier=...); stage.drain()
         frames = emitter.finish(K)                                    # {sample index: (B,3,F,8H,8W) fp32} decoded HERE
+
+    ``output="uint8"`` keeps (B,F,8H,8W,3) uint8 frames instead (``decode_latents_uint8``): a quarter of the bytes per
+    kept sample, ready for ``image_io.save_frames``.
     """
 
     def __init__(self, decoder: TemporalDecoderHIP, stage, num_frames: int, *, decode_chunk_size: int = 14,
-                 spread: bool = True, keep: str = "all", check_finite: bool = False) -> None:
+                 spread: bool = True, keep: str = "all", check_finite: bool = False, output: str = "float32") -> None:
         from ..pipeline.step_assignment import ring_finish_rank
 
         if keep not in ("all", "last", "none"):
             raise ValueError("keep must be 'all', 'last' or 'none'")
+        if output not in ("float32", "uint8"):
+            raise ValueError("output must be 'float32' or 'uint8'")
+        if check_finite and output == "uint8":
+            raise ValueError("check_finite needs output='float32' (an 8-bit level cannot show a non-finite value)")
+        self.output = output
         self.decoder, self.stage, self.num_frames = decoder, stage, num_frames
         self.chunk, self.keep, self.check_finite = decode_chunk_size, keep, check_finite
         cfg = stage.config
@@ -158,7 +188,8 @@ class FrameEmitter:
         latent.record_stream(self.stream)
         with torch.cuda.stream(self.stream):
             self.stream.wait_event(ready)
-            out = self.decoder.decode_latents(latent.contiguous(), self.num_frames, decode_chunk_size=self.chunk)
+            decode = self.decoder.decode_latents_uint8 if self.output == "uint8" else self.decoder.decode_latents
+            out = decode(latent.contiguous(), self.num_frames, decode_chunk_size=self.chunk)
         self.stats["decoded"] += 1
         if self.keep == "all":
             self.frames[idx] = out

@@ -355,7 +355,8 @@ class TemporalDecoderHIP(_VAEKernels):
     def _decode_chunk(self, src, src_strides, dst, dst_strides, *, flat0, n, frames_per_item, batch, frames, h, w,
                       scale):
         """Entries flat0 .. flat0+n-1 of the flattened (batch, frame) list of ``src`` -> the same entries of ``dst``;
-        the temporal layers treat them as ``batch`` items of ``frames`` frames (n = batch * frames)."""
+        the temporal layers treat them as ``batch`` items of ``frames`` frames (n = batch * frames).
+        ``dst_strides`` None: ``dst`` is the dense uint8 (B*F, 8H, 8W, 3) video (``sp_vae_frames_out_u8``)."""
         rows = self._buf(n * h * w, self.conv_in.cin)
         ops.vae_pack_latent(src, rows, scale=scale, flat0=flat0, n=n, frames_per_item=frames_per_item,
                             strides=src_strides, h=h, w=w, cpad=self.conv_in.cin)
@@ -374,8 +375,11 @@ class TemporalDecoderHIP(_VAEKernels):
                 h, w = 2 * h, 2 * w
         x = self._gn(self.norm_out, x, n, h * w, True)
         x = self._gemm(self.conv_out, x, n * h * w, conv=(n, h, w, h, w, 1, 0)).t
-        ops.vae_frames_out(x, self.tco_w, self.tco_b, dst, batch=b, frames=f, h=h, w=w, flat0=flat0,
-                           frames_per_item=frames_per_item, strides=dst_strides)
+        if dst_strides is None:
+            ops.vae_frames_out_u8(x, self.tco_w, self.tco_b, dst, batch=b, frames=f, h=h, w=w, flat0=flat0)
+        else:
+            ops.vae_frames_out(x, self.tco_w, self.tco_b, dst, batch=b, frames=f, h=h, w=w, flat0=flat0,
+                               frames_per_item=frames_per_item, strides=dst_strides)
 
     def decode(self, z, num_frames: int):
         """``vae.decode(z, num_frames).sample`` (ref generate_video_demo.py:181): z (B*F, 4, H, W) fp16, already divided
@@ -402,20 +406,11 @@ class TemporalDecoderHIP(_VAEKernels):
         (``force_upcast``, ref :171-175, because activations of the TRAINED decoder can leave fp16's range); with the flag
         the frames are checked (one device synchronisation) and a non-finite value raises ``FloatingPointError`` naming
         the first bad frame instead of being returned as a picture."""
-        if latents.dim() != 5 or latents.shape[1] != self.cfg.latent_channels or latents.shape[2] != num_frames:
-            raise ValueError(f"decode_latents expects (B, {self.cfg.latent_channels}, F, H, W) with F = num_frames; "
-                             f"got {tuple(latents.shape)}")
-        if decode_chunk_size <= 0:
-            raise ValueError("decode_chunk_size must be positive")
-        if latents.dtype != torch.float16 or latents.device != self.device or not latents.is_contiguous():
-            raise TypeError("decode_latents expects a contiguous float16 tensor on this decoder's device")
+        self._check_latents(latents, num_frames, decode_chunk_size)
         b, c, f, h, w = latents.shape
         out = torch.empty((b, 3, f, 8 * h, 8 * w), dtype=torch.float32, device=self.device)
-        hw, ohw = h * w, 64 * h * w
-        for i in range(0, b * f, decode_chunk_size):
-            n = min(decode_chunk_size, b * f - i)
-            self._decode_chunk(latents, (c * f * hw, f * hw, hw), out, (3 * f * ohw, f * ohw, ohw), flat0=i, n=n,
-                               frames_per_item=f, batch=1, frames=n, h=h, w=w, scale=1.0 / self.cfg.scaling_factor)
+        ohw = 64 * h * w
+        self._decode_chunks(latents, out, (3 * f * ohw, f * ohw, ohw), decode_chunk_size)
         if check_finite:
             bad = (~torch.isfinite(out)).flatten(3).any(-1).any(1)                       # (B, F)
             if bool(bad.any()):
@@ -423,6 +418,35 @@ class TemporalDecoderHIP(_VAEKernels):
                 raise FloatingPointError(f"decode_latents: non-finite values in video {bi}, frame {fi}: an activation left "
                                          f"fp16's range (the reference runs this VAE in fp32, force_upcast)")
         return out
+
+    def decode_latents_uint8(self, latents, num_frames: int, decode_chunk_size: int = 14):
+        """``decode_latents`` ending in the 8-bit frames the reference's ``save_video`` writes
+        (``/root/reference/scripts/generate_video_demo.py:205``): latents (B, 4, F, H, W) fp16 -> (B, F, 8H, 8W, 3) uint8,
+        byte for byte ``image_io.frames_to_uint8(decode_latents(...))`` -- the same decoder calls over the same chunks,
+        the last kernel storing levels instead of fp32 values, so the fp32 video (four times the bytes) never exists."""
+        self._check_latents(latents, num_frames, decode_chunk_size)
+        b, _, f, h, w = latents.shape
+        out = torch.empty((b, f, 8 * h, 8 * w, 3), dtype=torch.uint8, device=self.device)
+        self._decode_chunks(latents, out, None, decode_chunk_size)
+        return out
+
+    def _check_latents(self, latents, num_frames, decode_chunk_size):
+        if latents.dim() != 5 or latents.shape[1] != self.cfg.latent_channels or latents.shape[2] != num_frames:
+            raise ValueError(f"decode_latents expects (B, {self.cfg.latent_channels}, F, H, W) with F = num_frames; "
+                             f"got {tuple(latents.shape)}")
+        if decode_chunk_size <= 0:
+            raise ValueError("decode_chunk_size must be positive")
+        if latents.dtype != torch.float16 or latents.device != self.device or not latents.is_contiguous():
+            raise TypeError("decode_latents expects a contiguous float16 tensor on this decoder's device")
+
+    def _decode_chunks(self, latents, out, out_strides, decode_chunk_size):
+        """The reference's chunk walk over the flattened (B, F) list (ref :178-184), one decoder call per chunk."""
+        b, c, f, h, w = latents.shape
+        hw = h * w
+        for i in range(0, b * f, decode_chunk_size):
+            n = min(decode_chunk_size, b * f - i)
+            self._decode_chunk(latents, (c * f * hw, f * hw, hw), out, out_strides, flat0=i, n=n,
+                               frames_per_item=f, batch=1, frames=n, h=h, w=w, scale=1.0 / self.cfg.scaling_factor)
 
 
 class ImageEncoderHIP(_VAEKernels):

@@ -1,0 +1,168 @@
+"""Generate mode: a picture file in, the frames of a video out.
+
+Counterpart of the ``main()`` of the reference's demo (``/root/reference/scripts/generate_video_demo.py:225-466``; same
+flags where it has them, ``--output`` names the file instead of a directory of time-stamped names).  ``--model-id`` must be
+a LOCAL checkpoint directory in the hub layout; ``--random-init`` runs the exact architecture with synthetic weights
+(``--tiny``: the narrow test configuration).  Runs on one GPU as it is, or under torchrun as a step pipeline:
+
+    python -m vdpp_amd.modes.generate --random-init --input-image in.png --output out.gif
+
+Every rank builds the conditioning from the file itself -- the image kernels, CLIP and the VAE encoder are deterministic
+and the augmentation noise comes from a seeded CPU generator, so nothing is broadcast (the reference encodes on every rank
+as well, ref ``:250-300``).  The steps go through ``run_pipeline_latents`` as in ``production.py``; the rank that ends up
+with the finished latents decodes them to 8-bit frames (``decode_latents_uint8``) and writes them (``image_io.save_frames``:
+``.gif``, ``.npy``, a ``%03d.png`` pattern or a directory of PNGs).
+"""
+
+from __future__ import annotations
+
+import argparse
+import logging
+import os
+import tempfile
+
+import torch
+
+from ..distributed import finalize_distributed, init_distributed, resolve_backend
+from ..pipeline import LatentSpec, run_pipeline_latents
+
+LOGGER = logging.getLogger(__name__)
+
+
+def parse_args(argv=None) -> argparse.Namespace:
+    p = argparse.ArgumentParser(description="Generate video frames from an image (SVD step pipeline)")
+    p.add_argument("--input-image", type=str, required=True, help="picture file (anything Pillow decodes)")
+    p.add_argument("--output", type=str, required=True, help=".gif, .npy, a %%03d.png pattern or a directory for PNG frames")
+    p.add_argument("--height", type=int, default=576)
+    p.add_argument("--width", type=int, default=1024)
+    p.add_argument("--num-frames", type=int, default=14)
+    p.add_argument("--total-steps", type=int, default=25)
+    p.add_argument("--fps", type=int, default=7)
+    p.add_argument("--motion-bucket-id", type=int, default=127)
+    p.add_argument("--noise-aug-strength", type=float, default=0.02)
+    p.add_argument("--guidance-scale", type=float, default=3.0, help="CFG guidance scale (1.0 disables CFG)")
+    p.add_argument("--num-samples", type=int, default=1, help="videos to generate (seed, seed+1, ...)")
+    p.add_argument("--seed", type=int, default=42)
+    p.add_argument("--model-id", type=str, default=None, help="LOCAL checkpoint directory in the hub layout")
+    p.add_argument("--random-init", action="store_true")
+    p.add_argument("--tiny", action="store_true", help="with --random-init: the narrow test configuration")
+    p.add_argument("--decode-chunk-size", type=int, default=14)
+    p.add_argument("--balanced", action="store_true")
+    p.add_argument("--backend", type=str, default="auto", choices=["auto", "gloo", "nccl"])
+    p.add_argument("--init-method", type=str, default=None)
+    p.add_argument("--log-level", type=str, default="INFO")
+    args = p.parse_args(argv)
+    if args.random_init == bool(args.model_id):
+        p.error("give exactly one of --model-id <local dir> and --random-init")
+    if args.tiny and not args.random_init:
+        p.error("--tiny needs --random-init")
+    if args.height % 8 or args.width % 8:
+        p.error("--height and --width must be multiples of 8")
+    return args
+
+
+def sample_output_path(path: str, index: int, num_samples: int) -> str:
+    """``path`` for a single video, else the sample index goes in front of the extension (``out_s1.gif``, ``frames_s1``)."""
+    if num_samples == 1:
+        return path
+    root, ext = os.path.splitext(path)
+    return f"{root}_s{index}{ext}"
+
+
+def _clip_normalisation(model_dir):
+    """``(image_mean, image_std)`` of ``<model_dir>/feature_extractor/preprocessor_config.json`` (ref ``:256-258``), or
+    ``(None, None)`` -- the front end's OpenAI CLIP constants -- without that file."""
+    import json
+
+    path = os.path.join(model_dir or "", "feature_extractor", "preprocessor_config.json")
+    if not os.path.exists(path):
+        return None, None
+    with open(path) as fh:
+        cfg = json.load(fh)
+    return cfg.get("image_mean"), cfg.get("image_std")
+
+
+def _build_engines(args, timesteps, device):
+    """``(model, clip, vae_encoder, make_decoder)``: the decoder is built only on the rank that decodes."""
+    from ..models.clip_hip import CLIPVisionHIP, CLIPVisionSpec
+    from ..models.clip_hip import random_state_dict as clip_random_state_dict
+    from ..models.svd_unet import StableVideoUNet
+    from ..models.unet_spec import UNetConfig
+    from ..models.vae_hip import (ImageEncoderHIP, TemporalDecoderHIP, VAEDecoderConfig, random_encoder_state_dict,
+                                  random_state_dict)
+
+    if args.random_init:
+        ucfg = UNetConfig.tiny(64) if args.tiny else UNetConfig.svd()
+        spec = CLIPVisionSpec.tiny(ucfg.cross_attention_dim) if args.tiny else CLIPVisionSpec.svd()
+        vcfg = VAEDecoderConfig.tiny(64) if args.tiny else VAEDecoderConfig.svd()
+        model = StableVideoUNet.from_random_init(timesteps, config=ucfg, seed=args.seed, device=device)
+        clip = CLIPVisionHIP(spec, clip_random_state_dict(spec, seed=args.seed + 1, device=device), device)
+        enc = ImageEncoderHIP(vcfg, random_encoder_state_dict(vcfg, seed=args.seed + 2, device=device), device)
+        return model, clip, enc, lambda: TemporalDecoderHIP(vcfg, random_state_dict(vcfg, seed=args.seed + 3, device=device),
+                                                            device)
+    from ..models.edge_stages import load_edge_engines
+
+    model = StableVideoUNet.from_pretrained(args.model_id, timesteps=timesteps, device=device)
+    clip, enc, dec = load_edge_engines(args.model_id, device)
+    return model, clip, enc, lambda: dec
+
+
+def main(argv=None) -> None:
+    from ..models.edge_stages import encode_image_u8
+    from ..models.image_io import ImageFrontEnd, load_image, save_frames
+    from ..models.svd_unet import StableVideoUNet
+
+    args = parse_args(argv)
+    logging.basicConfig(level=getattr(logging, args.log_level.upper()),
+                        format="%(asctime)s %(levelname)s %(name)s: %(message)s")
+    rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
+    local_rank = int(os.environ.get("LOCAL_RANK", rank))
+    device = torch.device(f"cuda:{local_rank}")
+    torch.cuda.set_device(device)
+    image = load_image(args.input_image)                 # before the process group: a missing file fails alone
+    # one process started without torchrun: nothing is ever sent, the group only has to exist (Gloo, rendezvous in a file)
+    alone = world == 1 and args.init_method is None and "MASTER_ADDR" not in os.environ
+    backend = resolve_backend(None if args.backend == "auto" else args.backend, simulator=alone and args.backend == "auto")
+    rendezvous = tempfile.TemporaryDirectory() if alone else None
+    init_method = f"file://{rendezvous.name}/rendezvous" if alone else args.init_method
+    init_distributed(backend=backend, rank=rank, world_size=world, init_method=init_method)
+    try:
+        with torch.no_grad():
+            timesteps = StableVideoUNet._default_timestep_schedule(args.total_steps)
+            model, clip, enc, make_decoder = _build_engines(args, timesteps, device)
+            mean, std = _clip_normalisation(args.model_id)
+            front = ImageFrontEnd(device, args.height, args.width, clip_size=clip.spec.image_size, clip_mean=mean, clip_std=std)
+            noise = torch.randn((1, 3, args.height, args.width), generator=torch.Generator().manual_seed(args.seed))
+            emb, image_latents = encode_image_u8(image, front, clip, enc, args.num_frames, noise=noise,
+                                                 noise_aug_strength=args.noise_aug_strength)
+            del clip, enc, front
+            model.set_conditioning(emb, image_latents, fps=args.fps, motion_bucket_id=args.motion_bucket_id,
+                                   noise_aug_strength=args.noise_aug_strength, guidance_scale=args.guidance_scale,
+                                   num_frames=args.num_frames)
+            shape = torch.Size((1, 4, args.num_frames, args.height // 8, args.width // 8))
+            spec = LatentSpec(shape=shape, dtype=torch.float16, device=device)
+
+            def supplier(i: int) -> torch.Tensor:
+                torch.manual_seed(args.seed + i)
+                return torch.randn(shape, device=device, dtype=torch.float16) * model.init_noise_sigma
+
+            outs = run_pipeline_latents(model, total_steps=args.total_steps,
+                                        timesteps=list(range(args.total_steps - 1, -1, -1)), world_size=world,
+                                        rank=rank, latent_spec=spec, num_samples=args.num_samples,
+                                        input_supplier=supplier if rank == 0 else None, balanced=args.balanced)
+            if outs:
+                decoder = make_decoder()
+                for i, latents in enumerate(outs):
+                    frames = decoder.decode_latents_uint8(latents.contiguous(), args.num_frames,
+                                                          decode_chunk_size=args.decode_chunk_size)
+                    files = save_frames(frames[0], sample_output_path(args.output, i, args.num_samples), args.fps)
+                    LOGGER.info("sample %d (seed %d): %d frames of %dx%d -> %s", i, args.seed + i, frames.shape[1],
+                                frames.shape[3], frames.shape[2], files[0] if len(files) == 1 else os.path.dirname(files[0]))
+    finally:
+        finalize_distributed()
+        if rendezvous is not None:
+            rendezvous.cleanup()
+
+
+if __name__ == "__main__":
+    main()
