@@ -409,6 +409,53 @@ int sp_image_to_tensor_f16(const void *src, int64_t src_pitch, int h, int w, voi
 int sp_frames_to_u8(const void *frames, int is_fp32, void *out, int batch, int frames_n, int h, int w, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Video files out: baseline JPEG of uint8 frames that are in device memory (the reference hands its frames to imageio /
+ * ffmpeg: /root/reference/scripts/generate_video_demo.py:198-222).  Sequential DCT, 8 bit, YCbCr 4:2:0: an MCU is 16x16
+ * pixels and holds six 8x8 blocks in the order Y00 Y01 Y10 Y11 Cb Cr; mcu_rows = ceil(h/16), mcu_cols = ceil(w/16); h and w
+ * are 1..65535 (what SOF0 can say).  Two stages: coefficients, then the entropy-coded segment of the scan.  Marker
+ * segments (SOI .. SOS, EOI) and containers are written by the host from the two table queries below.
+ * ------------------------------------------------------------------------------------------- */
+/* Host only.  quality 1..100 -> the two quantisation tables in natural (row-major) order, libjpeg's scaling of the Annex K
+ * tables: s = quality < 50 ? 5000/quality : 200 - 2*quality; t = clamp((base*s + 50)/100, 1, 255), integer arithmetic.  The
+ * kernel below evaluates the same function. */
+int sp_jpeg_quant_tables(int quality, uint8_t *luma64, uint8_t *chroma64);
+/* Host only.  The Annex K Huffman table `which` (0 DC luminance, 1 DC chrominance, 2 AC luminance, 3 AC chrominance) as a
+ * DHT segment carries it: bits16[i] = number of codes of length i+1, then the symbols in code order (at most 162).
+ * Returns the number of symbols, or SP_EINVAL. */
+int sp_jpeg_huffman_table(int which, uint8_t *bits16, uint8_t *vals162);
+/* n * mcu_rows * mcu_cols * 6 * 64 * 2 bytes; 0 for sizes the calls below refuse */
+size_t sp_jpeg_coef_bytes(int n, int h, int w);
+/* frames: uint8 [n][h][w][3] RGB -> coef: int16 [n][mcu_rows][mcu_cols][6][64], every block in zigzag order.
+ * Sample (y, x) of the MCU grid reads pixel (min(y, h-1), min(x, w-1)).  Per pixel, in integers (libjpeg's jccolor):
+ *   Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+ *   Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16
+ *   Cr = ( 32768 R - 27439 G -  5329 B + (128 << 16) + 32767) >> 16
+ * chroma is box-averaged 2x2 as (a + b + c + d + bias) >> 2, bias 1 in even output columns and 2 in odd ones (h2v2_downsample).
+ * Each 8x8 block minus 128 goes through the orthonormal 2-D DCT-II in fp32 (row pass, then column pass, 8-term fma chains);
+ * a coefficient is divided by its table entry (fp32 division) and rounded half away from zero; AC terms are clamped to
+ * +-1023, the largest magnitude baseline Huffman codes. */
+int sp_jpeg_dct_quant_u8(const void *frames, int n, int h, int w, int quality, void *coef, void *stream);
+/* Bytes of entropy-coded data no frame can exceed: a block is at most 20 + 63*26 = 1658 bits (luminance: DC 9-bit code + 11
+ * bits, AC 16-bit code + 10 bits per coefficient; chrominance: DC 11 + 11 bits, but at most 12 + 10 per coefficient, 1408
+ * in all), 208 bytes, and byte stuffing at most doubles it:
+ *   416 * 6 * mcu_rows * mcu_cols + 2 * (intervals - 1),   intervals = ceil(mcu_rows * mcu_cols / restart_mcus)
+ * 0 for sizes sp_jpeg_entropy refuses. */
+size_t sp_jpeg_stream_bytes(int h, int w, int restart_mcus);
+/* Scratch of sp_jpeg_entropy: two int32 per (frame, interval), rounded up to 256 bytes, then a staging slot of
+ * 416 * 6 * min(restart_mcus, mcu_rows * mcu_cols) bytes per (frame, interval). */
+size_t sp_jpeg_entropy_ws_bytes(int n, int mcu_rows, int mcu_cols, int restart_mcus);
+/* coef as above -> for frame i the entropy-coded segment of its scan at out + i*cap and its length in out_len[i] (int32,
+ * device).  MCUs in raster order; the DC of each component is coded as the difference to the previous block of that
+ * component, all three predictors being 0 at the start of every restart interval of restart_mcus (1..65535) MCUs; Annex K
+ * tables, ZRL for 16 zeros, EOB unless coefficient 63 is non-zero; every interval is padded to a byte with 1-bits, every
+ * 0xFF byte of coded data is followed by 0x00, and 0xFF 0xD0+(k mod 8) stands between interval k and k+1.  Nothing follows
+ * the last interval (the host appends EOI).  cap (bytes per frame) below sp_jpeg_stream_bytes is refused, so no input can
+ * make a frame leave its slot; bytes of a slot beyond out_len[i] are not written.  Coefficients outside the baseline range
+ * (AC beyond +-1023, DC differences beyond +-2047) give a stream no decoder accepts, within the same bound. */
+int sp_jpeg_entropy(const void *coef, int n, int mcu_rows, int mcu_cols, int restart_mcus, void *out, size_t cap, void *out_len,
+                    void *ws, size_t ws_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement aid (bench.py `roofline.clock_ghz_live`; the reference has no counterpart -- its benchmark reads no clocks,
  * /root/reference/src/modes/benchmark.py:170-262).  One time stamp in stream order: `blocks` one-wave workgroups each write
  * four u64 words to out[block][4]: the id of the XCD the workgroup ran on (HW_REG_XCC_ID), the shader-clock counter

@@ -92,6 +92,13 @@ SIGNATURES = {
     "sp_image_resample_u8": (_I, [_P, _L, _I, _I, _P, _L, _I, _I, _I, _P, _Z, _P]),
     "sp_image_to_tensor_f16": (_I, [_P, _L, _I, _I, _P, _F, _F, _F, _F, _F, _F, _P]),
     "sp_frames_to_u8": (_I, [_P, _I, _P, _I, _I, _I, _I, _P]),
+    "sp_jpeg_quant_tables": (_I, [_I, _P, _P]),
+    "sp_jpeg_huffman_table": (_I, [_I, _P, _P]),
+    "sp_jpeg_coef_bytes": (_Z, [_I, _I, _I]),
+    "sp_jpeg_dct_quant_u8": (_I, [_P, _I, _I, _I, _I, _P, _P]),
+    "sp_jpeg_stream_bytes": (_Z, [_I, _I, _I]),
+    "sp_jpeg_entropy_ws_bytes": (_Z, [_I, _I, _I, _I]),
+    "sp_jpeg_entropy": (_I, [_P, _I, _I, _I, _I, _P, _Z, _P, _P, _Z, _P]),
     "sp_clock_stamp": (_I, [_P, _I, _P]),
     "sp_dummy_unet_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _I, _I, _I, _I, _I, _I, _P]),
 }

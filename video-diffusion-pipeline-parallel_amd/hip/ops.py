@@ -473,6 +473,76 @@ def frames_to_u8(frames, out):
     return out
 
 
+def jpeg_quant_tables(quality: int) -> tuple[bytes, bytes]:
+    """``(luma, chroma)``: 64 bytes each in natural (row-major) order, libjpeg's scaling of the Annex K tables (host only)."""
+    lu, ch = (ctypes.c_uint8 * 64)(), (ctypes.c_uint8 * 64)()
+    _check(load().sp_jpeg_quant_tables(int(quality), ctypes.addressof(lu), ctypes.addressof(ch)), "sp_jpeg_quant_tables")
+    return bytes(lu), bytes(ch)
+
+
+def jpeg_huffman_table(which: int) -> tuple[bytes, bytes]:
+    """``(bits, values)`` of Annex K table ``which`` (0 / 1: DC luminance / chrominance, 2 / 3: AC) as a DHT segment holds them."""
+    bits, vals = (ctypes.c_uint8 * 16)(), (ctypes.c_uint8 * 162)()
+    n = load().sp_jpeg_huffman_table(int(which), ctypes.addressof(bits), ctypes.addressof(vals))
+    if n < 0:
+        _check(n, "sp_jpeg_huffman_table")
+    return bytes(bits), bytes(vals)[:n]
+
+
+def jpeg_mcu_grid(h: int, w: int) -> tuple[int, int]:
+    return (h + 15) // 16, (w + 15) // 16
+
+
+def jpeg_coef_bytes(n: int, h: int, w: int) -> int:
+    return int(load().sp_jpeg_coef_bytes(n, h, w))
+
+
+def jpeg_stream_bytes(h: int, w: int, restart_mcus: int) -> int:
+    return int(load().sp_jpeg_stream_bytes(h, w, restart_mcus))
+
+
+def jpeg_entropy_ws_bytes(n: int, mcu_rows: int, mcu_cols: int, restart_mcus: int) -> int:
+    return int(load().sp_jpeg_entropy_ws_bytes(n, mcu_rows, mcu_cols, restart_mcus))
+
+
+def _dev_buf(t: torch.Tensor, dtype, name: str) -> torch.Tensor:
+    if t.dtype != dtype or not t.is_cuda or not t.is_contiguous():
+        raise TypeError(f"{name} must be a contiguous {dtype} tensor on a HIP device")
+    return t
+
+
+def jpeg_dct_quant(frames_u8, coef, *, quality):
+    """uint8 (n, h, w, 3) RGB -> int16 ``coef`` (n, mcu_rows, mcu_cols, 6, 64): quantised DCT coefficients of the 4:2:0 MCUs,
+    blocks in zigzag order (``sp_jpeg_dct_quant_u8``)."""
+    _dev_buf(frames_u8, torch.uint8, "jpeg_dct_quant: frames")
+    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
+        raise ValueError(f"jpeg_dct_quant: frames must be (n, h, w, 3); got {tuple(frames_u8.shape)}")
+    n, h, w, _ = frames_u8.shape
+    _dev_buf(coef, torch.int16, "jpeg_dct_quant: coef")
+    if tuple(coef.shape) != (n, *jpeg_mcu_grid(h, w), 6, 64):
+        raise ValueError(f"jpeg_dct_quant: coef must be {(n, *jpeg_mcu_grid(h, w), 6, 64)}; got {tuple(coef.shape)}")
+    _check(load().sp_jpeg_dct_quant_u8(frames_u8.data_ptr(), n, h, w, int(quality), coef.data_ptr(), _stream()),
+           "sp_jpeg_dct_quant_u8")
+    return coef
+
+
+def jpeg_entropy(coef, out, out_len, ws, *, restart_mcus):
+    """int16 ``coef`` (n, mcu_rows, mcu_cols, 6, 64) -> the entropy-coded segment of frame i in ``out[i, :out_len[i]]``
+    (``out``: uint8 (n, cap), cap >= ``jpeg_stream_bytes``; ``out_len``: int32 (n,); ``ws``: uint8 scratch of
+    ``jpeg_entropy_ws_bytes``)."""
+    _dev_buf(coef, torch.int16, "jpeg_entropy: coef")
+    if coef.dim() != 5 or tuple(coef.shape[3:]) != (6, 64):
+        raise ValueError(f"jpeg_entropy: coef must be (n, mcu_rows, mcu_cols, 6, 64); got {tuple(coef.shape)}")
+    n, mcu_rows, mcu_cols = coef.shape[:3]
+    _dev_buf(out, torch.uint8, "jpeg_entropy: out"), _dev_buf(ws, torch.uint8, "jpeg_entropy: ws")
+    _dev_buf(out_len, torch.int32, "jpeg_entropy: out_len")
+    if out.dim() != 2 or out.shape[0] != n or out_len.numel() != n:
+        raise ValueError("jpeg_entropy: out must be (n, cap) and out_len (n,)")
+    _check(load().sp_jpeg_entropy(coef.data_ptr(), n, mcu_rows, mcu_cols, int(restart_mcus), out.data_ptr(), out.shape[1],
+                                  out_len.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "sp_jpeg_entropy")
+    return out, out_len
+
+
 class ClockStamps:
     """Stamps of the shader-clock counter against the constant 100 MHz counter, taken in stream order between other work
     (``sp_clock_stamp``; bench.py ``roofline.clock_ghz_live``).  ``stamp()`` enqueues one on the current stream (a ~2 us

@@ -6,7 +6,7 @@ Same argument meaning and return values as the script's functions, minus what is
 ``CLIPImageProcessor`` output (``pixel_values``) and the normalised image tensor are arguments instead of a PIL image.
 ``encode_image_u8`` takes the picture itself (uint8 pixels) and makes those two tensors on the device
 (``image_io.ImageFrontEnd``); ``decode_latents_uint8`` / ``FrameEmitter(output="uint8")`` end in the 8-bit frames the
-script's ``save_video`` writes.
+script's ``save_video`` writes, ``FrameEmitter(output="jpeg")`` in those frames compressed (``image_io.JpegEncoder``).
 """
 
 from __future__ import annotations
@@ -142,20 +142,28 @@ class FrameEmitter:
         frames = emitter.finish(K)                                    # {sample index: (B,3,F,8H,8W) fp32} decoded HERE
 
     ``output="uint8"`` keeps (B,F,8H,8W,3) uint8 frames instead (``decode_latents_uint8``): a quarter of the bytes per
-    kept sample, ready for ``image_io.save_frames``.
+    kept sample, ready for ``image_io.save_frames``.  ``output="jpeg"`` compresses those frames on the decode stream
+    (``image_io.JpegEncoder`` at ``jpeg_quality``) and keeps, per sample, one ``list[bytes]`` of F JPEG files for each of its B
+    videos, ready for ``image_io.write_avi``: the encoder's buffers are reused, so a sample's bytes are fetched when the next
+    sample finishes on this rank (its decode is long over by then) or in ``finish``.
     """
 
     def __init__(self, decoder: TemporalDecoderHIP, stage, num_frames: int, *, decode_chunk_size: int = 14,
-                 spread: bool = True, keep: str = "all", check_finite: bool = False, output: str = "float32") -> None:
+                 spread: bool = True, keep: str = "all", check_finite: bool = False, output: str = "float32",
+                 jpeg_quality: int = 90) -> None:
         from ..pipeline.step_assignment import ring_finish_rank
 
         if keep not in ("all", "last", "none"):
             raise ValueError("keep must be 'all', 'last' or 'none'")
-        if output not in ("float32", "uint8"):
-            raise ValueError("output must be 'float32' or 'uint8'")
-        if check_finite and output == "uint8":
+        if output not in ("float32", "uint8", "jpeg"):
+            raise ValueError("output must be 'float32', 'uint8' or 'jpeg'")
+        if check_finite and output != "float32":
             raise ValueError("check_finite needs output='float32' (an 8-bit level cannot show a non-finite value)")
-        self.output = output
+        if output == "jpeg" and not (isinstance(jpeg_quality, int) and 1 <= jpeg_quality <= 100):
+            raise ValueError(f"jpeg_quality must be an integer from 1 to 100; got {jpeg_quality!r}")
+        self.output, self.jpeg_quality = output, jpeg_quality
+        self._jpeg = None               # the JpegEncoder, made for the first sample's frame size
+        self._pending = None            # (sample index, videos, streams, lengths, event) of the encode still on the device
         self.decoder, self.stage, self.num_frames = decoder, stage, num_frames
         self.chunk, self.keep, self.check_finite = decode_chunk_size, keep, check_finite
         cfg = stage.config
@@ -188,19 +196,47 @@ class FrameEmitter:
         latent.record_stream(self.stream)
         with torch.cuda.stream(self.stream):
             self.stream.wait_event(ready)
-            decode = self.decoder.decode_latents_uint8 if self.output == "uint8" else self.decoder.decode_latents
+            if self.output == "jpeg":
+                self._collect_jpeg()           # before this decode is queued: the encoder's buffers are free again after it
+            decode = self.decoder.decode_latents if self.output == "float32" else self.decoder.decode_latents_uint8
             out = decode(latent.contiguous(), self.num_frames, decode_chunk_size=self.chunk)
+            if self.output == "jpeg":
+                if self._jpeg is None or (self._jpeg.height, self._jpeg.width) != tuple(out.shape[2:4]):
+                    from .image_io import JpegEncoder
+                    self._jpeg = JpegEncoder(self.device, out.shape[2], out.shape[3], self.jpeg_quality)
+                streams, lens = self._jpeg.enqueue(out.flatten(0, 1))
+                done = torch.cuda.Event()
+                done.record(self.stream)
+                self._pending = (idx, out.shape[0], streams, lens, done)
         self.stats["decoded"] += 1
+        if self.output == "jpeg":
+            return
+        self._keep(idx, out)
+
+    def _keep(self, idx: int, out) -> None:
         if self.keep == "all":
             self.frames[idx] = out
         elif self.keep == "last":
             self.frames = {idx: out}
+
+    def _collect_jpeg(self) -> None:
+        if self._pending is None:
+            return
+        idx, videos, streams, lens, done = self._pending
+        self._pending = None
+        done.synchronize()
+        if self.keep != "none":
+            with torch.cuda.stream(self.stream):                      # (the copies queue behind nothing: the stream is idle)
+                files = self._jpeg.collect(streams, lens)
+            per = len(files) // videos
+            self._keep(idx, [files[v * per:(v + 1) * per] for v in range(videos)])
 
     # ---------------------------------------------------------------- end of a run
     def finish(self, num_samples: int) -> dict:
         """Wait for this rank's decodes and return ``{sample index: frames}`` for the samples decoded on THIS rank
         (``keep``: all of them, the last one, or none)."""
         self.stream.synchronize()
+        self._collect_jpeg()
         if self.check_finite:
             for idx, out in self.frames.items():
                 if not bool(torch.isfinite(out).all()):
@@ -210,3 +246,4 @@ class FrameEmitter:
     def reset(self) -> None:
         """Forget the previous run's bookkeeping (bench.py: warm-up, then the timed region)."""
         self.frames = {}
+        self._pending = None

@@ -7,12 +7,16 @@
     the device with the kernels of ``csrc/image.hip``.  Pillow's resize is reproduced to within one 8-bit level (its
     weights are 22-bit fixed point, the kernel's fp32); the geometry rules below are the reference's exactly.
   * ``frames_to_uint8`` / ``save_frames``: ``save_video`` / ``save_gif`` (ref ``:198-222``) without imageio.
+  * ``JpegEncoder`` / ``jpeg_header`` / ``write_avi``: the video file of ``save_video`` as Motion-JPEG in an AVI container
+    (no ffmpeg): frames on the device are compressed there by the kernels of ``csrc/jpeg.hip`` and only the compressed
+    bytes come to the host; the marker segments and the RIFF container are written here.
   * ``load_image``: the decode half of ``load_and_preprocess_image`` (Pillow; a file format is host work).
 """
 
 from __future__ import annotations
 
 import os
+import struct
 
 import numpy as np
 import torch
@@ -117,18 +121,192 @@ def load_image(path: str) -> np.ndarray:
         return np.asarray(im.convert("RGB")).copy()
 
 
-def save_frames(frames_u8, path: str, fps: int = 7) -> list[str]:
-    """Write one video's (F, H, W, 3) uint8 frames and return the files written.  ``*.gif``: an animated GIF that loops
-    for ever, ``1000 / fps`` ms per frame (ref ``save_gif`` :212-222); ``*.npy``: the raw array; a directory or a
-    ``%03d``-style ``*.png`` pattern: one PNG per frame.  ``*.mp4`` is refused: imageio / ffmpeg are not dependencies."""
+def _zigzag() -> list[int]:
+    """Position k of the zigzag sequence -> natural (row-major) index of the 8x8 block."""
+    order = sorted(range(64), key=lambda i: (i // 8 + i % 8, (i // 8) if (i // 8 + i % 8) % 2 else (i % 8)))
+    return order
+
+
+def _check_quality(quality) -> int:
+    if not isinstance(quality, (int, np.integer)) or not 1 <= quality <= 100:
+        raise ValueError(f"quality must be an integer from 1 to 100; got {quality!r}")
+    return int(quality)
+
+
+def _segment(marker: int, payload: bytes) -> bytes:
+    return struct.pack(">BBH", 0xFF, marker, len(payload) + 2) + payload
+
+
+def jpeg_header(height: int, width: int, quality: int, restart_mcus: int) -> bytes:
+    """The fixed front of every frame ``JpegEncoder`` makes, SOI up to and including SOS: JFIF APP0, the two quantisation
+    tables (``sp_jpeg_quant_tables``, written in zigzag order), SOF0 (baseline, 8 bit, three components sampled 2x2, 1x1,
+    1x1), the four Annex K Huffman tables (``sp_jpeg_huffman_table``), DRI and SOS.  The entropy-coded segment and EOI
+    follow it."""
+    if not (1 <= height <= 65535 and 1 <= width <= 65535):
+        raise ValueError(f"a JPEG frame is 1..65535 pixels on a side; got {height}x{width}")
+    if not 1 <= restart_mcus <= 65535:
+        raise ValueError(f"restart_mcus must be 1..65535; got {restart_mcus}")
+    luma, chroma = ops.jpeg_quant_tables(_check_quality(quality))
+    zz = _zigzag()
+    out = [b"\xff\xd8", _segment(0xE0, b"JFIF\0" + struct.pack(">BBBHHBB", 1, 1, 0, 1, 1, 0, 0))]
+    for tq, table in ((0, luma), (1, chroma)):
+        out.append(_segment(0xDB, bytes([tq]) + bytes(table[i] for i in zz)))
+    out.append(_segment(0xC0, struct.pack(">BHHB", 8, height, width, 3) + bytes([1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1])))
+    for which, tc_th in ((0, 0x00), (2, 0x10), (1, 0x01), (3, 0x11)):
+        bits, vals = ops.jpeg_huffman_table(which)
+        out.append(_segment(0xC4, bytes([tc_th]) + bits + vals))
+    out.append(_segment(0xDD, struct.pack(">H", restart_mcus)))
+    out.append(_segment(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0])))
+    return b"".join(out)
+
+
+class JpegEncoder:
+    """(F, H, W, 3) uint8 frames on the device -> one baseline JPEG (4:2:0) per frame, compressed on the device.
+
+    ``restart_mcus`` (default: one MCU row) is the restart interval: intervals are coded concurrently.  Coefficient, stream,
+    length and scratch buffers are kept per frame count; the stream buffer holds ``sp_jpeg_stream_bytes`` per frame (the size
+    no input can exceed), of which only the used bytes are ever copied to the host."""
+
+    def __init__(self, device, height: int, width: int, quality: int = 90, restart_mcus: int | None = None) -> None:
+        self.device = common.hip_device(device, "JpegEncoder")
+        self.height, self.width, self.quality = int(height), int(width), _check_quality(quality)
+        self.mcu_rows, self.mcu_cols = ops.jpeg_mcu_grid(self.height, self.width)
+        self.restart_mcus = int(restart_mcus) if restart_mcus is not None else min(self.mcu_cols, 65535)
+        self.header = jpeg_header(self.height, self.width, self.quality, self.restart_mcus)
+        self.cap = ops.jpeg_stream_bytes(self.height, self.width, self.restart_mcus)
+        self._scratch: dict = {}
+
+    def _buf(self, name: str, shape, dtype) -> torch.Tensor:
+        key = (name, shape)
+        if key not in self._scratch:
+            self._scratch[key] = torch.empty(shape, dtype=dtype, device=self.device)
+        return self._scratch[key]
+
+    def enqueue(self, frames_u8: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+        """Run the two stages on the current stream and return ``(streams (F, cap) uint8, lengths (F,) int32)``: views of
+        this encoder's buffers, valid until the next call with as many frames."""
+        if (not isinstance(frames_u8, torch.Tensor) or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4
+                or tuple(frames_u8.shape[1:]) != (self.height, self.width, 3) or frames_u8.shape[0] == 0):
+            raise ValueError(f"frames must be a (F, {self.height}, {self.width}, 3) uint8 tensor; got "
+                             f"{getattr(frames_u8, 'dtype', type(frames_u8))} {tuple(getattr(frames_u8, 'shape', ()))}")
+        n = frames_u8.shape[0]
+        coef = self._buf("coef", (n, self.mcu_rows, self.mcu_cols, 6, 64), torch.int16)
+        out = self._buf("stream", (n, self.cap), torch.uint8)
+        lens = self._buf("len", (n,), torch.int32)
+        ws = self._buf("ws", (ops.jpeg_entropy_ws_bytes(n, self.mcu_rows, self.mcu_cols, self.restart_mcus),), torch.uint8)
+        ops.jpeg_dct_quant(frames_u8.to(self.device).contiguous(), coef, quality=self.quality)
+        ops.jpeg_entropy(coef, out, lens, ws, restart_mcus=self.restart_mcus)
+        return out, lens
+
+    def collect(self, out: torch.Tensor, lens: torch.Tensor) -> list[bytes]:
+        """The files of an ``enqueue`` whose work has finished: the lengths come to the host first, then only the used bytes."""
+        return [self.header + out[i, :n].cpu().numpy().tobytes() + b"\xff\xd9" for i, n in enumerate(lens.cpu().tolist())]
+
+    def encode(self, frames_u8: torch.Tensor) -> list[bytes]:
+        out, lens = self.enqueue(frames_u8)
+        torch.cuda.current_stream(self.device).synchronize()
+        return self.collect(out, lens)
+
+
+def _jpeg_host(frame: np.ndarray, quality: int) -> bytes:
+    """Pillow's encode of one frame in host memory (4:2:0), for arrays that never were on a GPU."""
+    import io
+
+    from PIL import Image
+
+    buf = io.BytesIO()
+    Image.fromarray(frame).save(buf, format="JPEG", quality=quality, subsampling=2)
+    return buf.getvalue()
+
+
+def _chunk(fourcc: bytes, payload: bytes) -> bytes:
+    return fourcc + struct.pack("<I", len(payload)) + payload + (b"\0" if len(payload) & 1 else b"")
+
+
+AVI_MAX_BYTES = 2 ** 31 - 1          # one RIFF chunk of an AVI 1.0 file (OpenDML extends it; not written here)
+
+
+def write_avi(path: str, jpegs: list[bytes], width: int, height: int, fps: int) -> None:
+    """Motion-JPEG in a plain AVI 1.0 file: ``RIFF 'AVI '`` { ``LIST 'hdrl'`` { ``avih``, ``LIST 'strl'`` { ``strh``
+    (``vids`` / ``MJPG``, scale 1, rate ``fps``), ``strf`` (BITMAPINFOHEADER, ``MJPG``, 24 bit) } }, ``LIST 'movi'`` { one
+    ``00dc`` chunk per frame, padded to even length }, ``idx1`` { one key-frame entry per chunk, offsets from the ``movi``
+    fourcc } }.  Every frame is a complete JPEG file."""
+    if not jpegs:
+        raise ValueError("write_avi: no frames")
+    if not isinstance(fps, (int, np.integer)) or fps <= 0:
+        raise ValueError("fps must be a positive integer")
+    if width <= 0 or height <= 0:
+        raise ValueError("width and height must be positive")
+    n, largest = len(jpegs), max(len(j) for j in jpegs)
+    movi_bytes = 4 + sum(8 + len(j) + (len(j) & 1) for j in jpegs)
+    total = 12 + (8 + 4 + (8 + 56) + (8 + 4 + (8 + 56) + (8 + 40))) + (8 + movi_bytes) + (8 + 16 * n)
+    if total > AVI_MAX_BYTES:
+        raise ValueError(f"'{path}': {total} bytes pass the 2 GiB of an AVI 1.0 file (OpenDML is not written)")
+    avih = struct.pack("<14I", 1000000 // int(fps), largest * int(fps), 0, 0x10, n, 0, 1, largest, width, height, 0, 0, 0, 0)
+    strh = struct.pack("<4s4sIHHIIIIIIIIHHHH", b"vids", b"MJPG", 0, 0, 0, 0, 1, int(fps), 0, n, largest, 0xFFFFFFFF, 0,
+                       0, 0, min(width, 65535), min(height, 65535))
+    strf = struct.pack("<IiiHH4sIiiII", 40, width, height, 1, 24, b"MJPG", width * height * 3, 0, 0, 0, 0)
+    hdrl = b"hdrl" + _chunk(b"avih", avih) + _chunk(b"LIST", b"strl" + _chunk(b"strh", strh) + _chunk(b"strf", strf))
+    movi, index, at = [b"movi"], [], 4
+    for j in jpegs:
+        index.append(struct.pack("<4sIII", b"00dc", 0x10, at, len(j)))
+        movi.append(_chunk(b"00dc", j))
+        at += len(movi[-1])
+    body = b"AVI " + _chunk(b"LIST", hdrl) + _chunk(b"LIST", b"".join(movi)) + _chunk(b"idx1", b"".join(index))
+    assert 8 + len(body) == total
+    with open(path, "wb") as fh:
+        fh.write(b"RIFF" + struct.pack("<I", len(body)) + body)
+
+
+def _jpeg_frames(frames_u8, quality: int) -> tuple[list[bytes], int, int]:
+    """``(files, height, width)``: a tensor on a GPU is compressed there (``JpegEncoder``), anything else by Pillow."""
+    if isinstance(frames_u8, torch.Tensor) and frames_u8.is_cuda:
+        if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or 0 in frames_u8.shape:
+            raise ValueError(f"frames must be (F, H, W, 3) uint8; got {frames_u8.dtype} {tuple(frames_u8.shape)}")
+        _, h, w, _ = frames_u8.shape
+        return JpegEncoder(frames_u8.device, h, w, quality).encode(frames_u8), h, w
+    a = _frames_array(frames_u8)
+    return [_jpeg_host(f, quality) for f in a], a.shape[1], a.shape[2]
+
+
+def _frames_array(frames_u8) -> np.ndarray:
     a = frames_u8.cpu().numpy() if isinstance(frames_u8, torch.Tensor) else np.asarray(frames_u8)
     if a.dtype != np.uint8 or a.ndim != 4 or a.shape[3] != 3:
         raise ValueError(f"frames must be (F, H, W, 3) uint8; got {a.dtype} {a.shape}")
+    return a
+
+
+def save_frames(frames_u8, path: str, fps: int = 7, quality: int = 90) -> list[str]:
+    """Write one video's (F, H, W, 3) uint8 frames and return the files written.  ``*.avi``: Motion-JPEG at ``fps`` frames
+    per second, the video file of the reference's ``save_video`` (ref :198-209) in a container that needs no ffmpeg;
+    ``*.gif``: an animated GIF that loops for ever, ``1000 / fps`` ms per frame (ref ``save_gif`` :212-222); ``*.npy``:
+    the raw array; a ``%03d``-style ``*.jpg`` / ``*.jpeg`` pattern: one JPEG per frame; a directory or a ``%03d``-style
+    ``*.png`` pattern: one PNG per frame.  ``quality`` (1..100) is that of the JPEG frames; a tensor on a GPU is compressed
+    there and only the compressed bytes are copied.  ``*.mp4`` is refused: imageio / ffmpeg are not dependencies."""
     path = os.fspath(path)
     ext = os.path.splitext(path)[1].lower()
-    if ext in (".mp4", ".mov", ".mkv", ".webm", ".avi"):
+    # frames on a GPU stay there for the targets that are compressed there; everything else is host work on an array
+    on_gpu = isinstance(frames_u8, torch.Tensor) and frames_u8.is_cuda and ext in (".avi", ".jpg", ".jpeg")
+    a = None if on_gpu else _frames_array(frames_u8)
+    if ext in (".mp4", ".mov", ".mkv", ".webm"):
         raise ValueError(f"cannot write '{path}': video encoding needs imageio / ffmpeg, which this package does not depend "
-                         f"on; write .gif, .npy or PNG frames (a directory or a %03d.png pattern)")
+                         f"on; write .avi (Motion-JPEG) instead, or .gif, .npy, JPEG or PNG frames (a %03d.jpg / %03d.png "
+                         f"pattern or a directory)")
+    if ext in (".avi", ".jpg", ".jpeg"):
+        _check_quality(quality)
+        if ext == ".avi" and (not isinstance(fps, (int, np.integer)) or fps <= 0):
+            raise ValueError("fps must be a positive integer")
+        if ext != ".avi" and "%" not in path:
+            raise ValueError(f"'{path}': JPEG output needs a frame pattern such as frame_%03d.jpg")
+        jpegs, h, w = _jpeg_frames(frames_u8 if on_gpu else a, quality)
+        if ext == ".avi":
+            write_avi(path, jpegs, w, h, fps)
+            return [path]
+        files = [path % i for i in range(len(jpegs))]
+        for name, data in zip(files, jpegs):
+            with open(name, "wb") as fh:
+                fh.write(data)
+        return files
     if ext == ".npy":
         np.save(path, a)
         return [path]
@@ -148,7 +326,8 @@ def save_frames(frames_u8, path: str, fps: int = 7) -> list[str]:
         os.makedirs(path, exist_ok=True)
         pattern = os.path.join(path, "%03d.png")
     else:
-        raise ValueError(f"'{path}': unknown output format {ext!r} (.gif, .npy, %03d.png pattern or a directory)")
+        raise ValueError(f"'{path}': unknown output format {ext!r} (.avi, .gif, .npy, %03d.jpg / %03d.png pattern or a "
+                         f"directory)")
     files = []
     for i, f in enumerate(a):
         files.append(pattern % i)

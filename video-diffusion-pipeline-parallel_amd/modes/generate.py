@@ -11,7 +11,9 @@ Every rank builds the conditioning from the file itself -- the image kernels, CL
 and the augmentation noise comes from a seeded CPU generator, so nothing is broadcast (the reference encodes on every rank
 as well, ref ``:250-300``).  The steps go through ``run_pipeline_latents`` as in ``production.py``; the rank that ends up
 with the finished latents decodes them to 8-bit frames (``decode_latents_uint8``) and writes them (``image_io.save_frames``:
-``.gif``, ``.npy``, a ``%03d.png`` pattern or a directory of PNGs).
+``.avi`` -- Motion-JPEG, the video file; its frames, like those of a ``%03d.jpg`` pattern, are compressed on the GPU at
+``--jpeg-quality`` and only the compressed bytes come to the host -- ``.gif``, ``.npy``, a ``%03d.png`` pattern or a directory
+of PNGs).
 """
 
 from __future__ import annotations
@@ -32,12 +34,13 @@ LOGGER = logging.getLogger(__name__)
 def parse_args(argv=None) -> argparse.Namespace:
     p = argparse.ArgumentParser(description="Generate video frames from an image (SVD step pipeline)")
     p.add_argument("--input-image", type=str, required=True, help="picture file (anything Pillow decodes)")
-    p.add_argument("--output", type=str, required=True, help=".gif, .npy, a %%03d.png pattern or a directory for PNG frames")
+    p.add_argument("--output", type=str, required=True, help=".avi (Motion-JPEG video), .gif, .npy, a %%03d.jpg or %%03d.png pattern, or a directory for PNG frames")
     p.add_argument("--height", type=int, default=576)
     p.add_argument("--width", type=int, default=1024)
     p.add_argument("--num-frames", type=int, default=14)
     p.add_argument("--total-steps", type=int, default=25)
     p.add_argument("--fps", type=int, default=7)
+    p.add_argument("--jpeg-quality", type=int, default=90, help="quality (1-100) of .avi / .jpg frames")
     p.add_argument("--motion-bucket-id", type=int, default=127)
     p.add_argument("--noise-aug-strength", type=float, default=0.02)
     p.add_argument("--guidance-scale", type=float, default=3.0, help="CFG guidance scale (1.0 disables CFG)")
@@ -56,6 +59,8 @@ def parse_args(argv=None) -> argparse.Namespace:
         p.error("give exactly one of --model-id <local dir> and --random-init")
     if args.tiny and not args.random_init:
         p.error("--tiny needs --random-init")
+    if not 1 <= args.jpeg_quality <= 100:
+        p.error("--jpeg-quality must be from 1 to 100")
     if args.height % 8 or args.width % 8:
         p.error("--height and --width must be multiples of 8")
     return args
@@ -155,7 +160,9 @@ def main(argv=None) -> None:
                 for i, latents in enumerate(outs):
                     frames = decoder.decode_latents_uint8(latents.contiguous(), args.num_frames,
                                                           decode_chunk_size=args.decode_chunk_size)
-                    files = save_frames(frames[0], sample_output_path(args.output, i, args.num_samples), args.fps)
+                    # the device tensor goes in as it is: .avi / .jpg frames are compressed where they are
+                    files = save_frames(frames[0], sample_output_path(args.output, i, args.num_samples), args.fps,
+                                        quality=args.jpeg_quality)
                     LOGGER.info("sample %d (seed %d): %d frames of %dx%d -> %s", i, args.seed + i, frames.shape[1],
                                 frames.shape[3], frames.shape[2], files[0] if len(files) == 1 else os.path.dirname(files[0]))
     finally:
