@@ -456,6 +456,51 @@ int sp_jpeg_entropy(const void *coef, int n, int mcu_rows, int mcu_cols, int res
                     void *ws, size_t ws_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Animated GIF of uint8 frames that are in device memory (the reference's save_gif hands its frames to imageio:
+ * scripts/generate_video_demo.py:212-222 there).  Two stages: a 256-colour palette and the pixels' indices per
+ * frame, then the LZW-coded image data of the frame's image block.  Headers, extensions, descriptors and the trailer are
+ * written by the host.  h and w are 1..65535 (what a descriptor can say) with h*w <= 2^24 (the per-bin channel sums stay
+ * inside 32 bits); strip_rows >= 1 (a value above h means h).  The size functions need no GPU and give 0 for arguments the
+ * calls refuse.
+ * ------------------------------------------------------------------------------------------- */
+/* Scratch of both calls for n frames: per frame the histogram (32^3 bins x two 64-bit words), four summed-volume tables of
+ * 33^3 words and the bin -> index table; then, for the LZW stage, three int32 arrays and a staging slot per (frame, strip)
+ * of the strip's worst case in whole words plus one.  The two stages use disjoint parts. */
+size_t sp_gif_ws_bytes(int n, int h, int w, int strip_rows);
+/* Bytes of image data no frame can exceed.  Bits: the opening CLEAR, 9; at most one code per pixel of at most 12 bits; a
+ * CLEAR of 12 bits whenever 3838 codes have filled a dictionary, at most floor(h*w / 3838) of them; one CLEAR or EOI of at
+ * most 12 bits per strip, strips = ceil(h / strip_rows):
+ *   bytes = ceil((9 + 12*h*w + 12*floor(h*w / 3838) + 12*strips) / 8),   result = 1 + bytes + ceil(bytes / 255) + 1
+ * (the minimum code size in front, a length byte per sub-block of 255, the terminator). */
+size_t sp_gif_stream_bytes(int h, int w, int strip_rows);
+/* frames: uint8 [n][h][w][3] RGB -> palette: uint8 [n][256][3], indices: uint8 [n][h][w].  Integer arithmetic only.  Per frame:
+ *   histogram  32 x 32 x 32 bins at (r>>3, g>>3, b>>3), each with its pixel count and the sums of the three 8-bit values;
+ *   boxes      a box is an inclusive range of bins per axis, always shrunk to the occupied bins inside it.  From the shrunk
+ *              cube, split until there are 256 boxes or none can be split: among the boxes whose longest extent
+ *              e = max(hi - lo) is above 0 take the largest count * e (the lowest index among equals); the axis is the first
+ *              of R, G, B with extent e; cut after plane lo + c, c the smallest offset with
+ *              2 * (pixels in planes lo .. lo+c) >= count, at most e - 1; the lower part keeps the index, the upper part is
+ *              appended, both are shrunk;
+ *   palette    entry i = (2*sum + count) / (2*count) per channel over box i, integer division; unused entries are 0;
+ *   mapping    an occupied bin's colour is its own rounded mean, computed the same way; the bin takes the entry in use with
+ *              the least squared distance to it (the lowest index among equals); a pixel's index is its bin's.
+ * ws needs the quantiser's part of sp_gif_ws_bytes (any strip_rows), 8-byte aligned. */
+int sp_gif_quantise_u8(const void *frames, int n, int h, int w, void *palette, void *indices, void *ws, size_t ws_bytes,
+                       void *stream);
+/* indices: uint8 [n][h][w] -> for frame i the image data of a GIF image block at out + i*cap and its length in out_len[i]
+ * (int32, device): the minimum code size 08, the LZW stream in sub-blocks of at most 255 bytes each behind its length byte,
+ * and the terminator 00.  The frame is cut into strips of strip_rows rows (the last may be shorter), each coded with a
+ * dictionary of its own, so that the strips can be coded concurrently.  The stream: CLEAR (256) at 9 bits; then the strips in
+ * order, each ordinary GIF LZW from an empty dictionary (first free code 258, width 9; after a code is written and its entry
+ * made, the width grows when the next free code is above 2^width; when the next free code is 4096, CLEAR is written at 12
+ * bits and the dictionary starts again); after a strip's last code comes CLEAR, or EOI (257) after the frame's last strip, at
+ * the width in force once that last code's own entry has been counted.  Codes are packed least significant bit first, strips
+ * are joined bit by bit, the last byte is padded with zeros.  cap below sp_gif_stream_bytes is refused; bytes of a slot
+ * beyond out_len[i] are not written.  ws: sp_gif_ws_bytes, 8-byte aligned. */
+int sp_gif_lzw(const void *indices, int n, int h, int w, int strip_rows, void *out, size_t cap, void *out_len, void *ws,
+               size_t ws_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement aid (bench.py `roofline.clock_ghz_live`; the reference has no counterpart -- its benchmark reads no clocks,
  * /root/reference/src/modes/benchmark.py:170-262).  One time stamp in stream order: `blocks` one-wave workgroups each write
  * four u64 words to out[block][4]: the id of the XCD the workgroup ran on (HW_REG_XCC_ID), the shader-clock counter

@@ -99,6 +99,10 @@ SIGNATURES = {
     "sp_jpeg_stream_bytes": (_Z, [_I, _I, _I]),
     "sp_jpeg_entropy_ws_bytes": (_Z, [_I, _I, _I, _I]),
     "sp_jpeg_entropy": (_I, [_P, _I, _I, _I, _I, _P, _Z, _P, _P, _Z, _P]),
+    "sp_gif_ws_bytes": (_Z, [_I, _I, _I, _I]),
+    "sp_gif_stream_bytes": (_Z, [_I, _I, _I]),
+    "sp_gif_quantise_u8": (_I, [_P, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    "sp_gif_lzw": (_I, [_P, _I, _I, _I, _I, _P, _Z, _P, _P, _Z, _P]),
     "sp_clock_stamp": (_I, [_P, _I, _P]),
     "sp_dummy_unet_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _I, _I, _I, _I, _I, _I, _P]),
 }

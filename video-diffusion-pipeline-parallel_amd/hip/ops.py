@@ -543,6 +543,48 @@ def jpeg_entropy(coef, out, out_len, ws, *, restart_mcus):
     return out, out_len
 
 
+def gif_ws_bytes(n: int, h: int, w: int, strip_rows: int) -> int:
+    return int(load().sp_gif_ws_bytes(n, h, w, strip_rows))
+
+
+def gif_stream_bytes(h: int, w: int, strip_rows: int) -> int:
+    return int(load().sp_gif_stream_bytes(h, w, strip_rows))
+
+
+def gif_quantise(frames_u8, palette, indices, ws):
+    """uint8 (n, h, w, 3) RGB -> ``palette`` uint8 (n, 256, 3) and ``indices`` uint8 (n, h, w): a median-cut palette of every
+    frame over a 32^3 histogram and the nearest entry per occupied bin (``sp_gif_quantise_u8``); ``ws``: uint8 scratch of
+    ``gif_ws_bytes``."""
+    _dev_buf(frames_u8, torch.uint8, "gif_quantise: frames")
+    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
+        raise ValueError(f"gif_quantise: frames must be (n, h, w, 3); got {tuple(frames_u8.shape)}")
+    n, h, w, _ = frames_u8.shape
+    _dev_buf(palette, torch.uint8, "gif_quantise: palette"), _dev_buf(indices, torch.uint8, "gif_quantise: indices")
+    _dev_buf(ws, torch.uint8, "gif_quantise: ws")
+    if tuple(palette.shape) != (n, 256, 3) or tuple(indices.shape) != (n, h, w):
+        raise ValueError(f"gif_quantise: palette must be {(n, 256, 3)} and indices {(n, h, w)}; got {tuple(palette.shape)} and "
+                         f"{tuple(indices.shape)}")
+    _check(load().sp_gif_quantise_u8(frames_u8.data_ptr(), n, h, w, palette.data_ptr(), indices.data_ptr(), ws.data_ptr(),
+                                     ws.numel(), _stream()), "sp_gif_quantise_u8")
+    return palette, indices
+
+
+def gif_lzw(indices, out, out_len, ws, *, strip_rows):
+    """uint8 ``indices`` (n, h, w) -> the image data of frame i's GIF image block in ``out[i, :out_len[i]]`` (``out``: uint8
+    (n, cap), cap >= ``gif_stream_bytes``; ``out_len``: int32 (n,); ``ws``: uint8 scratch of ``gif_ws_bytes``)."""
+    _dev_buf(indices, torch.uint8, "gif_lzw: indices")
+    if indices.dim() != 3:
+        raise ValueError(f"gif_lzw: indices must be (n, h, w); got {tuple(indices.shape)}")
+    n, h, w = indices.shape
+    _dev_buf(out, torch.uint8, "gif_lzw: out"), _dev_buf(ws, torch.uint8, "gif_lzw: ws")
+    _dev_buf(out_len, torch.int32, "gif_lzw: out_len")
+    if out.dim() != 2 or out.shape[0] != n or out_len.numel() != n:
+        raise ValueError("gif_lzw: out must be (n, cap) and out_len (n,)")
+    _check(load().sp_gif_lzw(indices.data_ptr(), n, h, w, int(strip_rows), out.data_ptr(), out.shape[1], out_len.data_ptr(),
+                             ws.data_ptr(), ws.numel(), _stream()), "sp_gif_lzw")
+    return out, out_len
+
+
 class ClockStamps:
     """Stamps of the shader-clock counter against the constant 100 MHz counter, taken in stream order between other work
     (``sp_clock_stamp``; bench.py ``roofline.clock_ghz_live``).  ``stamp()`` enqueues one on the current stream (a ~2 us

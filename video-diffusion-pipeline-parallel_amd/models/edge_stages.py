@@ -145,24 +145,29 @@ class FrameEmitter:
     kept sample, ready for ``image_io.save_frames``.  ``output="jpeg"`` compresses those frames on the decode stream
     (``image_io.JpegEncoder`` at ``jpeg_quality``) and keeps, per sample, one ``list[bytes]`` of F JPEG files for each of its B
     videos, ready for ``image_io.write_avi``: the encoder's buffers are reused, so a sample's bytes are fetched when the next
-    sample finishes on this rank (its decode is long over by then) or in ``finish``.
+    sample finishes on this rank (its decode is long over by then) or in ``finish``.  ``output="gif"`` does the same with
+    ``image_io.GifEncoder`` at ``gif_fps`` frames per second and keeps, per sample, one ``bytes`` (a complete animated GIF) for
+    each of its B videos.
     """
 
     def __init__(self, decoder: TemporalDecoderHIP, stage, num_frames: int, *, decode_chunk_size: int = 14,
                  spread: bool = True, keep: str = "all", check_finite: bool = False, output: str = "float32",
-                 jpeg_quality: int = 90) -> None:
+                 jpeg_quality: int = 90, gif_fps=7) -> None:
         from ..pipeline.step_assignment import ring_finish_rank
 
         if keep not in ("all", "last", "none"):
             raise ValueError("keep must be 'all', 'last' or 'none'")
-        if output not in ("float32", "uint8", "jpeg"):
-            raise ValueError("output must be 'float32', 'uint8' or 'jpeg'")
+        if output not in ("float32", "uint8", "jpeg", "gif"):
+            raise ValueError("output must be 'float32', 'uint8', 'jpeg' or 'gif'")
         if check_finite and output != "float32":
             raise ValueError("check_finite needs output='float32' (an 8-bit level cannot show a non-finite value)")
         if output == "jpeg" and not (isinstance(jpeg_quality, int) and 1 <= jpeg_quality <= 100):
             raise ValueError(f"jpeg_quality must be an integer from 1 to 100; got {jpeg_quality!r}")
-        self.output, self.jpeg_quality = output, jpeg_quality
+        if output == "gif" and (isinstance(gif_fps, bool) or not isinstance(gif_fps, (int, float)) or not gif_fps > 0):
+            raise ValueError(f"gif_fps must be a positive number; got {gif_fps!r}")
+        self.output, self.jpeg_quality, self.gif_fps = output, jpeg_quality, gif_fps
         self._jpeg = None               # the JpegEncoder, made for the first sample's frame size
+        self._gif = None                # the GifEncoders, one per video of a sample (a video's buffers wait for the fetch)
         self._pending = None            # (sample index, videos, streams, lengths, event) of the encode still on the device
         self.decoder, self.stage, self.num_frames = decoder, stage, num_frames
         self.chunk, self.keep, self.check_finite = decode_chunk_size, keep, check_finite
@@ -196,7 +201,7 @@ class FrameEmitter:
         latent.record_stream(self.stream)
         with torch.cuda.stream(self.stream):
             self.stream.wait_event(ready)
-            if self.output == "jpeg":
+            if self.output in ("jpeg", "gif"):
                 self._collect_jpeg()           # before this decode is queued: the encoder's buffers are free again after it
             decode = self.decoder.decode_latents if self.output == "float32" else self.decoder.decode_latents_uint8
             out = decode(latent.contiguous(), self.num_frames, decode_chunk_size=self.chunk)
@@ -208,8 +213,16 @@ class FrameEmitter:
                 done = torch.cuda.Event()
                 done.record(self.stream)
                 self._pending = (idx, out.shape[0], streams, lens, done)
+            elif self.output == "gif":
+                if self._gif is None or len(self._gif) != out.shape[0] or (self._gif[0].height, self._gif[0].width) != tuple(out.shape[2:4]):
+                    from .image_io import GifEncoder
+                    self._gif = [GifEncoder(self.device, out.shape[2], out.shape[3], fps=self.gif_fps) for _ in range(out.shape[0])]
+                bufs = [enc.enqueue(video) for enc, video in zip(self._gif, out)]
+                done = torch.cuda.Event()
+                done.record(self.stream)
+                self._pending = (idx, out.shape[0], bufs, None, done)
         self.stats["decoded"] += 1
-        if self.output == "jpeg":
+        if self.output in ("jpeg", "gif"):
             return
         self._keep(idx, out)
 
@@ -227,6 +240,9 @@ class FrameEmitter:
         done.synchronize()
         if self.keep != "none":
             with torch.cuda.stream(self.stream):                      # (the copies queue behind nothing: the stream is idle)
+                if self.output == "gif":
+                    self._keep(idx, [enc.collect(*bufs) for enc, bufs in zip(self._gif, streams)])
+                    return
                 files = self._jpeg.collect(streams, lens)
             per = len(files) // videos
             self._keep(idx, [files[v * per:(v + 1) * per] for v in range(videos)])

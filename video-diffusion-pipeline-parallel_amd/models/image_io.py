@@ -10,6 +10,8 @@
   * ``JpegEncoder`` / ``jpeg_header`` / ``write_avi``: the video file of ``save_video`` as Motion-JPEG in an AVI container
     (no ffmpeg): frames on the device are compressed there by the kernels of ``csrc/jpeg.hip`` and only the compressed
     bytes come to the host; the marker segments and the RIFF container are written here.
+  * ``GifEncoder`` / ``write_gif``: the animated GIF of ``save_gif``: frames on the device are quantised to a palette each
+    and LZW-coded there by the kernels of ``csrc/gif.hip``; the blocks of the file around them are written here.
   * ``load_image``: the decode half of ``load_and_preprocess_image`` (Pillow; a file format is host work).
 """
 
@@ -258,6 +260,96 @@ def write_avi(path: str, jpegs: list[bytes], width: int, height: int, fps: int) 
         fh.write(b"RIFF" + struct.pack("<I", len(body)) + body)
 
 
+def _check_fps(fps) -> float:
+    if isinstance(fps, bool) or not isinstance(fps, (int, float, np.integer, np.floating)) or not fps > 0:
+        raise ValueError(f"fps must be a positive number; got {fps!r}")
+    return float(fps)
+
+
+def write_gif(path, palettes, datas, width: int, height: int, fps=7) -> bytes:
+    """An animated GIF that loops for ever, returned as ``bytes`` and written to ``path`` unless that is ``None``:
+    ``GIF89a``, the logical screen descriptor (no global table), the NETSCAPE2.0 extension with loop count 0, and per frame
+    a graphic control extension (delay ``max(1, round(100 / fps))`` centiseconds, no disposal, no transparency), an image
+    descriptor of the whole screen with a 256-entry local table, the table (``palettes[i]``: 768 bytes or a (256, 3) uint8
+    array) and the image data (``datas[i]``: minimum code size, sub-blocks, terminator -- what ``sp_gif_lzw`` writes); then
+    the trailer."""
+    if len(palettes) == 0 or len(palettes) != len(datas):
+        raise ValueError(f"write_gif: no frames, or {len(palettes)} palettes for {len(datas)} frames")
+    delay = max(1, round(100 / _check_fps(fps)))
+    if not (1 <= width <= 65535 and 1 <= height <= 65535):
+        raise ValueError(f"a GIF is 1..65535 pixels on a side; got {height}x{width}")
+    out = [b"GIF89a", struct.pack("<HHBBB", width, height, 0x70, 0, 0),
+           b"\x21\xff\x0bNETSCAPE2.0\x03\x01" + struct.pack("<H", 0) + b"\x00"]
+    control = b"\x21\xf9\x04" + struct.pack("<BHB", 0, min(delay, 65535), 0) + b"\x00"
+    descriptor = b"\x2c" + struct.pack("<HHHHB", 0, 0, width, height, 0x87)
+    for palette, data in zip(palettes, datas):
+        table = palette if isinstance(palette, (bytes, bytearray)) else np.ascontiguousarray(palette, dtype=np.uint8).tobytes()
+        if len(table) != 768:
+            raise ValueError(f"write_gif: a local table holds 256 x 3 bytes; got {len(table)}")
+        out += [control, descriptor, bytes(table), bytes(data)]
+    out.append(b"\x3b")
+    blob = b"".join(out)
+    if path is not None:
+        with open(path, "wb") as fh:
+            fh.write(blob)
+    return blob
+
+
+class GifEncoder:
+    """(F, H, W, 3) uint8 frames on the device -> one animated GIF, quantised and LZW-coded on the device (``csrc/gif.hip``).
+
+    Every frame has a palette of its own (median cut over a 32^3 histogram, no dithering) and is coded in strips of
+    ``strip_rows`` rows with a dictionary each, so that a frame is many independent sequences; at 576 x 1024 strips of 8 rows
+    cost 2.1 % in size over one dictionary per frame and are the fastest measured (profiles/gif_timing.txt; 16 rows: 0.95 %).  Palette, index, stream, length and scratch buffers are kept
+    per frame count; the stream buffer holds ``sp_gif_stream_bytes`` per frame (the size no input can exceed), of which only
+    the used bytes are ever copied to the host."""
+
+    def __init__(self, device, height: int, width: int, strip_rows: int = 8, fps=7) -> None:
+        self.device = common.hip_device(device, "GifEncoder")
+        self.height, self.width, self.fps = int(height), int(width), _check_fps(fps)
+        if not isinstance(strip_rows, (int, np.integer)) or strip_rows < 1:
+            raise ValueError(f"strip_rows must be a positive integer; got {strip_rows!r}")
+        self.strip_rows = int(strip_rows)
+        self.cap = ops.gif_stream_bytes(self.height, self.width, self.strip_rows)
+        if self.cap == 0:
+            raise ValueError(f"a GIF frame is 1..65535 pixels on a side and at most 2^24 in all; got {height}x{width}")
+        self._scratch: dict = {}
+
+    def _buf(self, name: str, shape, dtype) -> torch.Tensor:
+        key = (name, shape)
+        if key not in self._scratch:
+            self._scratch[key] = torch.empty(shape, dtype=dtype, device=self.device)
+        return self._scratch[key]
+
+    def enqueue(self, frames_u8: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Run the two stages on the current stream and return ``(palettes (F, 256, 3) uint8, streams (F, cap) uint8, lengths
+        (F,) int32)``: views of this encoder's buffers, valid until the next call with as many frames."""
+        if (not isinstance(frames_u8, torch.Tensor) or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4
+                or tuple(frames_u8.shape[1:]) != (self.height, self.width, 3) or frames_u8.shape[0] == 0):
+            raise ValueError(f"frames must be a (F, {self.height}, {self.width}, 3) uint8 tensor; got "
+                             f"{getattr(frames_u8, 'dtype', type(frames_u8))} {tuple(getattr(frames_u8, 'shape', ()))}")
+        n = frames_u8.shape[0]
+        palettes = self._buf("palette", (n, 256, 3), torch.uint8)
+        indices = self._buf("index", (n, self.height, self.width), torch.uint8)
+        out = self._buf("stream", (n, self.cap), torch.uint8)
+        lens = self._buf("len", (n,), torch.int32)
+        ws = self._buf("ws", (ops.gif_ws_bytes(n, self.height, self.width, self.strip_rows),), torch.uint8)
+        ops.gif_quantise(frames_u8.to(self.device).contiguous(), palettes, indices, ws)
+        ops.gif_lzw(indices, out, lens, ws, strip_rows=self.strip_rows)
+        return palettes, out, lens
+
+    def collect(self, palettes: torch.Tensor, out: torch.Tensor, lens: torch.Tensor) -> bytes:
+        """The file of an ``enqueue`` whose work has finished: the lengths come to the host first, then only the used bytes."""
+        tables = palettes.cpu().numpy()
+        datas = [out[i, :n].cpu().numpy().tobytes() for i, n in enumerate(lens.cpu().tolist())]
+        return write_gif(None, list(tables), datas, self.width, self.height, self.fps)
+
+    def encode(self, frames_u8: torch.Tensor) -> bytes:
+        bufs = self.enqueue(frames_u8)
+        torch.cuda.current_stream(self.device).synchronize()
+        return self.collect(*bufs)
+
+
 def _jpeg_frames(frames_u8, quality: int) -> tuple[list[bytes], int, int]:
     """``(files, height, width)``: a tensor on a GPU is compressed there (``JpegEncoder``), anything else by Pillow."""
     if isinstance(frames_u8, torch.Tensor) and frames_u8.is_cuda:
@@ -282,11 +374,15 @@ def save_frames(frames_u8, path: str, fps: int = 7, quality: int = 90) -> list[s
     ``*.gif``: an animated GIF that loops for ever, ``1000 / fps`` ms per frame (ref ``save_gif`` :212-222); ``*.npy``:
     the raw array; a ``%03d``-style ``*.jpg`` / ``*.jpeg`` pattern: one JPEG per frame; a directory or a ``%03d``-style
     ``*.png`` pattern: one PNG per frame.  ``quality`` (1..100) is that of the JPEG frames; a tensor on a GPU is compressed
-    there and only the compressed bytes are copied.  ``*.mp4`` is refused: imageio / ffmpeg are not dependencies."""
+    there and only the compressed bytes are copied.  The same holds for ``*.gif``: a tensor on a GPU is quantised and
+    LZW-coded there (``GifEncoder``: a palette per frame, strips of 8 rows, delays in whole centiseconds), while an array in
+    host memory goes through Pillow as before, byte for byte.  ``*.mp4`` is refused: imageio / ffmpeg are not dependencies."""
     path = os.fspath(path)
     ext = os.path.splitext(path)[1].lower()
     # frames on a GPU stay there for the targets that are compressed there; everything else is host work on an array
-    on_gpu = isinstance(frames_u8, torch.Tensor) and frames_u8.is_cuda and ext in (".avi", ".jpg", ".jpeg")
+    on_gpu = isinstance(frames_u8, torch.Tensor) and frames_u8.is_cuda and ext in (".avi", ".jpg", ".jpeg", ".gif")
+    if on_gpu and ext == ".gif" and frames_u8.dim() == 4 and frames_u8.shape[1] * frames_u8.shape[2] > 2 ** 24:
+        on_gpu = False                 # beyond what sp_gif_quantise_u8 takes: the route such frames always had
     a = None if on_gpu else _frames_array(frames_u8)
     if ext in (".mp4", ".mov", ".mkv", ".webm"):
         raise ValueError(f"cannot write '{path}': video encoding needs imageio / ffmpeg, which this package does not depend "
@@ -309,6 +405,14 @@ def save_frames(frames_u8, path: str, fps: int = 7, quality: int = 90) -> list[s
         return files
     if ext == ".npy":
         np.save(path, a)
+        return [path]
+    if ext == ".gif" and on_gpu:
+        if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or 0 in frames_u8.shape:
+            raise ValueError(f"frames must be (F, H, W, 3) uint8; got {frames_u8.dtype} {tuple(frames_u8.shape)}")
+        _check_fps(fps)
+        data = GifEncoder(frames_u8.device, frames_u8.shape[1], frames_u8.shape[2], fps=fps).encode(frames_u8)
+        with open(path, "wb") as fh:
+            fh.write(data)
         return [path]
     from PIL import Image
 

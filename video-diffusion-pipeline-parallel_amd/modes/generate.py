@@ -12,8 +12,9 @@ and the augmentation noise comes from a seeded CPU generator, so nothing is broa
 as well, ref ``:250-300``).  The steps go through ``run_pipeline_latents`` as in ``production.py``; the rank that ends up
 with the finished latents decodes them to 8-bit frames (``decode_latents_uint8``) and writes them (``image_io.save_frames``:
 ``.avi`` -- Motion-JPEG, the video file; its frames, like those of a ``%03d.jpg`` pattern, are compressed on the GPU at
-``--jpeg-quality`` and only the compressed bytes come to the host -- ``.gif``, ``.npy``, a ``%03d.png`` pattern or a directory
-of PNGs).
+``--jpeg-quality`` and only the compressed bytes come to the host -- ``.gif``, the animated GIF of the demo: quantised to a
+palette per frame and LZW-coded on the GPU as well (``image_io.GifEncoder``), at ``--fps`` -- ``.npy``, a ``%03d.png`` pattern
+or a directory of PNGs).
 """
 
 from __future__ import annotations
