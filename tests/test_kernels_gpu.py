@@ -1112,6 +1112,114 @@ def test_attention_temporal(batch, frames, hw, heads):
     check(o, ref, l2=3e-3, mx=2e-2)
 
 
+# ---- attention judged ROW BY ROW on peaked rows.  One rel-L2 over the whole output hides the rows: a CPU statement of
+# the spatial kernel's arithmetic stays at or below 9e-4 over the tensor from q/k amplitude 1 to 4 while its worst row
+# goes from 8e-4 to 7e-3.  A "row" is one query of one head (64 output values); the reference is fp64 on the fp16-rounded
+# inputs; the bound is 3 x the worst row of a CPU statement of the kernel's rounding points (written here from the header
+# comment of csrc/attention.hip), evaluated on the same inputs.
+LOG2E = 1.4426950408889634
+
+
+def _per_row_err(out, ref):
+    o, r = out.double().cpu().reshape(-1, 64), ref.double().reshape(-1, 64)
+    return (o - r).norm(dim=1) / r.norm(dim=1).clamp_min(1e-30)
+
+
+def _attn_fp64(q, k, v, scale=0.125):
+    return torch.softmax(q.double() @ k.double().transpose(-1, -2) * scale, dim=-1) @ v.double()
+
+
+def _temporal_statement(q, k, v, scale=0.125):
+    """attn_temporal_kernel: fp16 inputs, fp32 scores, scaled (by scale * log2 e) AFTER the product, exp2 against the row
+    maximum, P normalised in fp32 and then rounded to fp16, fp32 sums of P.V, fp16 output."""
+    sl = torch.tensor(scale * LOG2E, dtype=torch.float32)
+    s = q @ k.transpose(-1, -2)
+    p = torch.exp2(s * sl - s.amax(-1, keepdim=True) * sl)
+    p16 = (p * (1.0 / p.sum(-1, keepdim=True))).half().float()
+    return (p16 @ v).half()
+
+
+def _spatial_statement(q, k, v, scale=0.125):
+    """attn_spatial_kernel: Q pre-multiplied by scale * log2 e and rounded to fp16, fp32 scores in log2 units, tiles of 64
+    keys against a running reference m (the first tile's row maximum, raised only when a tile exceeds it by more than 8),
+    P = exp2(s - m) rounded to fp16 (un-normalised), row sums of the ROUNDED P and P.V in fp32, one division, fp16 output."""
+    sl = torch.tensor(scale * LOG2E, dtype=torch.float32)
+    s = (q * sl).half().float() @ k.transpose(-1, -2)
+    m = l = o = None
+    for t0 in range(0, s.shape[-1], 64):
+        st = s[..., t0:t0 + 64]
+        mt = st.amax(-1, keepdim=True)
+        if t0 == 0:
+            m, l, o = mt, torch.zeros_like(mt), torch.zeros_like(q)
+        else:
+            delta = torch.where(mt - m > 8.0, mt - m, torch.zeros_like(mt))
+            m, l, o = m + delta, l * torch.exp2(-delta), o * torch.exp2(-delta)
+        p16 = torch.exp2(st - m).half().float()
+        l = l + p16.sum(-1, keepdim=True)
+        o = o + p16 @ v[..., t0:t0 + 64, :]
+    return (o * (1.0 / l)).half()
+
+
+@pytest.mark.parametrize("amp", [1, 3, 6])
+@pytest.mark.parametrize("frames", [1, 14, 16, 17, 25, 32])
+def test_attention_temporal_peaked_rows_judged_per_row(frames, amp):
+    """Both instantiations (NT = 1 up to 16 frames, NT = 2 beyond) and the seam at key 16; hw = 37 with 3 heads = 111
+    sequences, so the last workgroup has a dead wave; q/k of amplitude 1, 3, 6 (logits of standard deviation amp^2);
+    planted dominant keys (k = 1.5 x some other frame's q: 12 standard deviations above the rest) at frame 0, at the last frame
+    and at frames 15 and 16 where they exist; one all-equal row (q = 0).  With one frame the output is V itself and the
+    bound is 0."""
+    ops = _ops()
+    g = torch.Generator().manual_seed(frames * 10 + amp)
+    hw, heads = 37, 3
+    c = heads * 64
+    q, k, v = [h(torch.randn(hw, heads, frames, 64, generator=g) * a) for a in (amp, amp, 1)]
+    planted = sorted({0, frames - 1, 15, 16} & set(range(frames)))
+    for j, kf in enumerate(planted):                                  # pixel j, head 0: query frame kf + 3 finds key frame kf
+        k[j, 0, kf] = h(1.5 * q[j, 0, (kf + 3) % frames])
+    q[5, 1, frames // 2] = 0.0
+    ref = _attn_fp64(q, k, v)
+    bound = 3.0 * float(_per_row_err(_temporal_statement(q, k, v), ref).max())
+    if frames > 1:
+        p = torch.softmax(q.double() @ k.double().transpose(-1, -2) * 0.125, dim=-1)
+        assert all(float(p[j, 0, (kf + 3) % frames, kf]) > 0.9 for j, kf in enumerate(planted)), "a planted key does not dominate"
+    d = torch.cat([t.permute(2, 0, 1, 3).reshape(frames * hw, c) for t in (q, k, v)], dim=1).half().to(DEV)
+    o = torch.empty(frames * hw, c, dtype=torch.float16, device=DEV)
+    ops.attn_temporal(d[:, :c], d[:, c:2 * c], d[:, 2 * c:], o, ldq=3 * c, ldk=3 * c, ldv=3 * c, ldo=c, batch=1,
+                      frames=frames, hw=hw, heads=heads)
+    got = o.float().cpu().reshape(frames, hw, heads, 64).permute(1, 2, 0, 3)
+    assert torch.isfinite(got).all()
+    err = _per_row_err(got, ref)
+    print(f"temporal attention, {frames} frames, amplitude {amp}: worst row {float(err.max()):.2e}, bound {bound:.2e} "
+          f"(whole tensor {rel_l2(got, ref):.2e})")
+    assert float(err.max()) <= bound, f"worst row {float(err.max()):.3e} (row {int(err.argmax())}) > {bound:.3e}"
+
+
+@pytest.mark.parametrize("amp", [1, 2, 3, 4])
+@pytest.mark.parametrize("seq", [200, 1100])
+def test_attention_spatial_peaked_rows_judged_per_row(seq, amp):
+    """sp_attn_spatial_f16 per row at 200 and 1,100 tokens (ragged last tile; 4 and 18 K/V tiles), two heads.  Asserted
+    at q/k amplitude 1 and 2.  At amplitude 3 and 4 the fp16 rounding of Q.scale.log2e alone puts single rows at 0.3-0.7 %
+    (the statement says so itself): recorded -- printed beside the statement's own worst row -- not asserted."""
+    ops = _ops()
+    g = torch.Generator().manual_seed(seq + amp)
+    heads = 2
+    c = heads * 64
+    q, k, v = [h(torch.randn(heads, seq, 64, generator=g) * a) for a in (amp, amp, 1)]
+    ref = _attn_fp64(q, k, v)
+    own = float(_per_row_err(_spatial_statement(q, k, v), ref).max())
+    d = torch.cat([t.permute(1, 0, 2).reshape(seq, c) for t in (q, k, v)], dim=1).half().to(DEV)
+    o = torch.empty(seq, c, dtype=torch.float16, device=DEV)
+    ops.attn_spatial(d[:, :c], d[:, c:2 * c], d[:, 2 * c:], o, ldq=3 * c, ldk=3 * c, ldv=3 * c, ldo=c, batch=1, seq=seq,
+                     heads=heads)
+    got = o.float().cpu().reshape(seq, heads, 64).permute(1, 0, 2)
+    assert torch.isfinite(got).all()
+    err = _per_row_err(got, ref)
+    print(f"spatial attention, {seq} tokens, amplitude {amp}: worst row {float(err.max()):.2e}, the statement's own {own:.2e} "
+          f"(whole tensor {rel_l2(got, ref):.2e})")
+    if amp <= 2:
+        assert float(err.max()) <= 3.0 * own, f"worst row {float(err.max()):.3e} (row {int(err.argmax())}) > 3 x {own:.3e}"
+
+
 def test_gemv_batched():
     """sp_gemv_batched_f16: a batch of same-shape GEMVs in one launch, shared input (x_stride 0) and per-problem input."""
     ops = _ops()
