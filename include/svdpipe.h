@@ -160,6 +160,25 @@ size_t sp_gemm_workspace_bytes(const sp_gemm_desc *desc);
  * thread-local, valid until that thread's next call): lets a profile attribute FLOPs to kernel templates. */
 const char *sp_gemm_last_kernel(void);
 
+/* Nearest-neighbour x2 upsample followed by a 3x3 convolution (pad 1, stride 1; Upsample2D + conv of the UNet's up blocks)
+ * as FOUR 2x2 convolutions.  After the upsample the nine taps of output pixel (oy, ox) touch a 2x2 window of source pixels
+ * only, and which window, and how the nine weights add up onto it, depends on the parity (py, px) = (oy & 1, ox & 1) alone.
+ * With phase p = 2*py + px, window tap t = 2*ty + tx and source pixel (sy, sx) = (oy >> 1, ox >> 1):
+ *   d[img][2*sy + py][2*sx + px][:] = bias + sum_t a[img][sy + py - 1 + ty][sx + px - 1 + tx][:] . w[p][:][t*cin : (t+1)*cin]^T
+ * (pixels outside the source image are zero), where the row weights of the fold are (w0, w1 + w2) for py = 0 and
+ * (w0 + w1, w2) for py = 1, the same for columns with px (models/weights.py::pack_conv3x3_up2x folds in fp32 and rounds to
+ * fp16 once).  K = 4*cin instead of the 9*cin of sp_gemm_f16 with upsample2x; same result up to that one rounding.
+ *   a: fp16 [n_img*hin*win][lda] (NHWC rows), w: fp16 [4][n][4*cin], bias: fp32 [n] or NULL, d: fp16 [n_img*2hin*2win][ldd];
+ *   gn_part: NULL, or fp32 [n_img*4*hin*win/256][2][n][2] column sums for the next GroupNorm as sp_gemm_desc.gn_part leaves
+ *   them -- the 256-row tiles of one phase of one image cover the same 256 source pixels, so their sums stand at tile index
+ *   img*4t + p*t + j (t = hin*win/256): the 4t tiles of an image are contiguous, which is all the folding kernels rely on.
+ * Checked before anything is launched (SP_EINVAL, the message names the argument): a, w, d, zero_page non-NULL, all
+ * pointers 16-byte aligned; cin a multiple of 64; n a multiple of 256 or 320; lda >= cin, ldd >= n, both multiples of 8;
+ * positive geometry, 4*n_img*hin*win below 2^31; with gn_part hin*win a multiple of 256.
+ * Runs as "gemm_pp_kernel<256, 256 | 320, 8192>" (the name sp_gemm_last_kernel reports afterwards). */
+int sp_conv_up2x_f16(const void *a, int64_t lda, int cin, int n_img, int hin, int win, const void *w, int n,
+                     const float *bias, void *d, int64_t ldd, float *gn_part, const void *zero_page, void *stream);
+
 /* Test / micro-benchmark hook (no counterpart in the reference): pins the kernel family sp_gemm_f16 picks for the
  * shapes that family supports; everything else keeps the automatic choice.  Process-wide, not thread-safe: set it
  * before the calls it should affect.  route 0 = automatic (default), 1 = small tiles only, 2 = ping-pong large tiles

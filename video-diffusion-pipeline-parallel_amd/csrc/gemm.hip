@@ -693,6 +693,38 @@ extern "C" int sp_gemm_f32out_f16(const void *a_, int64_t lda, const void *w, vo
   return spgemm::launch_pp(a, 256, 256, (hipStream_t)stream);
 }
 
+// Nearest x2 upsample + 3x3 convolution (pad 1) as four 2x2 convolutions, one per parity phase of the output pixel (see
+// include/svdpipe.h): K = 4*cin instead of 9*cin.  One launch of gemm_pp_kernel<256, BN, 8192> covers the four phases.
+extern "C" int sp_conv_up2x_f16(const void *a_, int64_t lda, int cin, int n_img, int hin, int win, const void *w, int n,
+                                const float *bias, void *d, int64_t ldd, float *gn_part, const void *zero_page, void *stream) {
+  SP_REQUIRE(a_ && w && d && zero_page, "sp_conv_up2x_f16: null a/w/d/zero_page");
+  SP_REQUIRE((((uintptr_t)a_ | (uintptr_t)w | (uintptr_t)d | (uintptr_t)zero_page | (uintptr_t)bias | (uintptr_t)gn_part) & 15) == 0,
+             "sp_conv_up2x_f16: a, w, d, zero_page, bias and gn_part must be 16-byte aligned");
+  SP_REQUIRE(cin > 0 && cin % 64 == 0, "sp_conv_up2x_f16: cin=%d must be a positive multiple of 64", cin);
+  SP_REQUIRE(n > 0 && (n % 256 == 0 || n % 320 == 0), "sp_conv_up2x_f16: n=%d must be a positive multiple of 256 or 320", n);
+  SP_REQUIRE(lda >= cin && lda % 8 == 0, "sp_conv_up2x_f16: lda=%lld must be >= cin (%d) and a multiple of 8", (long long)lda, cin);
+  SP_REQUIRE(ldd >= n && ldd % 8 == 0, "sp_conv_up2x_f16: ldd=%lld must be >= n (%d) and a multiple of 8", (long long)ldd, n);
+  SP_REQUIRE(n_img > 0 && hin > 0 && win > 0, "sp_conv_up2x_f16: geometry (n_img=%d, hin=%d, win=%d) must be positive", n_img,
+             hin, win);
+  const int64_t rows = (int64_t)n_img * hin * win;          // source pixels = output rows of one phase
+  SP_REQUIRE(4 * rows <= 0x7fffffff, "sp_conv_up2x_f16: n_img*hin*win=%lld: the 4x as many output rows must fit an int",
+             (long long)rows);
+  SP_REQUIRE(!gn_part || ((int64_t)hin * win) % 256 == 0,
+             "sp_conv_up2x_f16: gn_part needs frames of whole 256-row tiles per phase (hin*win = %lld)", (long long)hin * win);
+  GemmArgs a{};
+  a.a = (const f16 *)a_; a.w = (const f16 *)w; a.bias = bias; a.d = (f16 *)d; a.zero = (const char *)zero_page;
+  a.gn_part = gn_part;
+  a.lda = lda; a.ldd = ldd;
+  a.mode = SP_A_CONV3X3; a.cin = cin; a.taps = 4;
+  a.n_img = n_img; a.hin = hin; a.win = win; a.hout = 2 * hin; a.wout = 2 * win; a.stride = 1; a.ups = 1;
+  a.m = (int)rows; a.n = n; a.k = 4 * cin;
+  a.oscale = 1.0f; a.r1scale = 1.0f; a.r2scale = 1.0f;
+  a.bias2_rows = a.m; a.ldb2 = n;
+  a.up_tiles = (a.m + 255) / 256;
+  a.up_gn_tiles = gn_part ? hin * win / 256 : 1;
+  return spgemm::launch_pp_up2x(a, n % 320 == 0 ? 320 : 256, (hipStream_t)stream);
+}
+
 extern "C" int sp_gemm_f16(const sp_gemm_desc *d, void *stream) {
   SP_REQUIRE(d != nullptr, "sp_gemm_f16: null descriptor");
   SP_REQUIRE(d->a && d->w && d->d && d->zero_page, "sp_gemm_f16: null a/w/d/zero_page");

@@ -49,6 +49,10 @@ struct GemmArgs {
   float *partial;
   int dbg;   // ablation builds only (-DSP_GEMM_EXPERIMENTS + SP_GEMM_DBG): selects gemm_pp_kernel<.., EXP>
   int stagger;   // ablation builds only (SP_GEMM_STAGGER): first-round workgroups start (b/8 & 3) * stagger us late
+  // upsampling convolution as four 2x2 phases (sp_conv_up2x_f16; gemm_pp_kernel<256, BN, 8192>): m = rows of ONE phase
+  // (n_img*hin*win source pixels), taps = 4, w = [4][n][4*cin]
+  int up_tiles;      // 256-row tiles per phase; the grid's tiles_m = 4 * up_tiles, phase-major
+  int up_gn_tiles;   // with gn_part: hin*win / 256, tiles per frame and phase
 };
 
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
@@ -66,6 +70,8 @@ void note_kernel_suffix(const char *suffix);   // appended to the name note_kern
 
 // ping-pong large-tile kernels (gemm_pp.hip): bm in {128 (bn 256 only), 192, 256}, bn in {256, 320}
 int launch_pp(GemmArgs &a, int bm, int bn, hipStream_t s);
+// upsampling convolution as four 2x2 phases on 256 x bn tiles (bn in {256, 320}); see GemmArgs::up_tiles
+int launch_pp_up2x(GemmArgs &a, int bn, hipStream_t s);
 
 // persistent-stream kernels (gemm_ps.hip): (bm, bn) in {(256,256), (192,256)}; see ps_supported
 bool ps_supported(const GemmArgs &a, int bm, int bn);

@@ -71,9 +71,12 @@ __device__ __forceinline__ void wait_dma(int ksteps_left) {
 // so that their latency overlaps the LDS round trip, and all arithmetic precedes the first store: on gfx9 stores
 // count in vmcnt like loads, so a load consumed after a store was issued waits for that store's acknowledgement.
 #define WROWS_OF(pbm, wtm) ((pbm) / (wtm))      /* wave rows of a tile */
-template <int PBM, int BN, int TN, int TM, int WTN, int WTM, bool GEGLU, int NT, bool GNRES = false>
+// UP (gemm_pp_kernel's EXP & 8192, a nearest x2 upsample + 3x3 convolution as four 2x2 phases): tile_m counts the row tiles of
+// ONE phase, row m = (img, sy, sx) of the source image goes to output pixel (2*sy + py, 2*sx + px), phase = 2*py + px; the
+// column sums land where the frame's 4 * up_gn_tiles tiles are contiguous.  Bias only (host).
+template <int PBM, int BN, int TN, int TM, int WTN, int WTM, bool GEGLU, int NT, bool GNRES = false, bool UP = false>
 __device__ __forceinline__ void pp_epilogue(const GemmArgs &p, f32x4 (&acc)[TN][TM], char *smem, int tile_m,
-                                            int tile_n, int wm, int wn, int tid, int fr, int fq) {
+                                            int tile_n, int wm, int wn, int tid, int fr, int fq, int phase = 0) {
   constexpr int bno = GEGLU ? BN / 2 : BN;
   constexpr int cpr = bno >> 3;                          // 16-byte chunks per row (a multiple of 8)
   constexpr int TNO = GEGLU ? TN / 2 : TN;
@@ -128,7 +131,12 @@ __device__ __forceinline__ void pp_epilogue(const GemmArgs &p, f32x4 (&acc)[TN][
         v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));  // row_mirror
         return v;
       };
-      float *dst = p.gn_part + (((int64_t)tile_m * WROWS_OF(PBM, WTM) + wm) * p.n + (int64_t)tile_n * BN + wn * WTN) * 2;
+      int gn_tile = tile_m;
+      if constexpr (UP) {     // frame-major, then phase: a frame's tiles stay contiguous for the kernels that fold them
+        const int frame = tile_m / p.up_gn_tiles;
+        gn_tile = (frame * 4 + phase) * p.up_gn_tiles + (tile_m - frame * p.up_gn_tiles);
+      }
+      float *dst = p.gn_part + (((int64_t)gn_tile * WROWS_OF(PBM, WTM) + wm) * p.n + (int64_t)tile_n * BN + wn * WTN) * 2;
 #pragma unroll
       for (int i = 0; i < TN; ++i) {
         f32x4 sm = {0.f, 0.f, 0.f, 0.f}, sq = {0.f, 0.f, 0.f, 0.f};
@@ -257,9 +265,15 @@ __device__ __forceinline__ void pp_epilogue(const GemmArgs &p, f32x4 (&acc)[TN][
   for (int it = 0; it < ITERS; ++it) {
     const int idx = tid + it * NT;
     const int r = idx / cpr, c = idx - r * cpr;
-    const int64_t m = mbase + r;
+    int64_t m = mbase + r;
     const int col = tile_n * bno + c * 8;
     if (idx >= NCH || m >= p.m || col >= nstore) continue;
+    if constexpr (UP) {                   // source pixel -> its output pixel of this phase (m < p.m: fits an int)
+      const int mi = (int)m, per_img = p.hin * p.win;
+      const int img = mi / per_img, rem = mi - img * per_img;
+      const int sy = rem / p.win, sx = rem - sy * p.win;
+      m = ((int64_t)img * (2 * p.hin) + 2 * sy + (phase >> 1)) * (2 * p.win) + 2 * sx + (phase & 1);
+    }
     if (col + 8 <= nstore) {
 #ifdef SP_GEMM_EXPERIMENTS
       // (non-temporal stores measured here too: no difference on any shape -- a one-tile workgroup ends behind its stores,
@@ -377,6 +391,11 @@ __global__ __launch_bounds__(BM == 128 ? 256 : 512, 2) void gemm_pp_kernel(const
   // channels of a SECOND tensor's rows (same row index as the output) against the weight columns that follow -- a resnet's
   // 1x1 shortcut convolution folded into its second 3x3 convolution: the skip tensor is neither written nor read
   constexpr bool A2 = (EXP & 4096) != 0;
+  // Nearest x2 upsample + 3x3 convolution as four 2x2 convolutions (EXP & 8192, its own instantiations, sp_conv_up2x_f16):
+  // the nine taps of an output pixel touch a 2x2 window of source pixels that depends on the pixel's parity (py, px) only,
+  // so each parity phase is a 4-tap convolution with pre-summed weights (w = [4][n][4*cin], models/weights.py).  Row tiles
+  // are phase-major (p.up_tiles per phase, p.m = rows of ONE phase = source pixels), no tile mixes phases.
+  constexpr bool UP = (EXP & 8192) != 0;
   constexpr int NWV = BM == 128 ? 4 : 8, NT = NWV * 64, WROWS = NWV / 4;   // waves, threads, wave rows (x 4 columns)
   constexpr int PSTAGES = pp_stages(BM, BN), PDIST = PSTAGES - 1;
   constexpr int TN = BN / 4 / 16;                 // weight sub-tiles per wave (4 or 5)
@@ -438,7 +457,9 @@ __global__ __launch_bounds__(BM == 128 ? 256 : 512, 2) void gemm_pp_kernel(const
   const int gsz = min(p.tiles_m - first_m, GM);
   const int in_group = t - group * per_group;
   const int tile_n = in_group / gsz;
-  const int tile_m = first_m + (in_group - tile_n * gsz);
+  const int tile_mg = first_m + (in_group - tile_n * gsz);       // row tile of the grid
+  const int phase = UP ? tile_mg / p.up_tiles : 0;
+  const int tile_m = UP ? tile_mg - phase * p.up_tiles : tile_mg;   // ... of the phase
 
   // ---------------------------------------------------------------- per-lane gather state
   const int lrow = lane >> 2, lchunk = lane & 3;  // 16 rows x 4 chunks per 1-KiB piece
@@ -453,7 +474,15 @@ __global__ __launch_bounds__(BM == 128 ? 256 : 512, 2) void gemm_pp_kernel(const
     const int m = tile_m * PBM + r;
     a_in[i] = m < p.m && r < PBM;
     schunk_a[i] = (lchunk ^ swz4(r)) * 8;
-    if (p.mode == SP_A_CONV3X3) {
+    if constexpr (UP) {
+      const int per_img = p.hin * p.win;
+      const int img = m / per_img;
+      const int rem = m - img * per_img;
+      const int sy = rem / p.win;
+      a_i0[i] = img;
+      a_i1[i] = sy + (phase >> 1) - 1;                      // top-left source pixel of the phase's 2x2 window
+      a_i2[i] = (rem - sy * p.win) + (phase & 1) - 1;
+    } else if (p.mode == SP_A_CONV3X3) {
       const int per_img = p.hout * p.wout;
       const int img = m / per_img;
       const int rem = m - img * per_img;
@@ -495,7 +524,10 @@ __global__ __launch_bounds__(BM == 128 ? 256 : 512, 2) void gemm_pp_kernel(const
 #else
       if (a_in[i]) {
 #endif
-        if (p.mode == SP_A_CONV3X3) {
+        if constexpr (UP) {
+          const int iy = a_i1[i] + (tap >> 1), ix = a_i2[i] + (tap & 1);
+          if (iy >= 0 && iy < p.hin && ix >= 0 && ix < p.win) row = ((int64_t)a_i0[i] * p.hin + iy) * p.win + ix;
+        } else if (p.mode == SP_A_CONV3X3) {
           const int ky = tap / 3, kx = tap - ky * 3;
           const int iy = a_i1[i] + ky, ix = a_i2[i] + kx;
           const int hv = p.hin << p.ups, wv = p.win << p.ups;
@@ -528,6 +560,7 @@ __global__ __launch_bounds__(BM == 128 ? 256 : 512, 2) void gemm_pp_kernel(const
     bptr[j] = p.w + (int64_t)n * p.k + (lchunk ^ swz4(r)) * 8;
     // per-row-group weights (a GroupNorm folded into this linear layer: one scaled copy per frame; host: no tile straddles)
     if (p.w_group_rows > 0) bptr[j] += ((int64_t)tile_m * PBM / p.w_group_rows) * p.w_group_stride;
+    if constexpr (UP) bptr[j] += (int64_t)phase * p.n * p.k;      // the phase's folded weights
   }
 
   bool skip_a = false;                            // (experiments build: see HALO_COUNT)
@@ -605,7 +638,7 @@ __global__ __launch_bounds__(BM == 128 ? 256 : 512, 2) void gemm_pp_kernel(const
     if (s < nk) stage_next();
   PP_TRACE(11);
   __builtin_amdgcn_sched_barrier(0);
-  if (p.bias2 && !SPLITK) {
+  if (!UP && p.bias2 && !SPLITK) {
     int brow[TM];
 #pragma unroll
     for (int j = 0; j < TM; ++j) {
@@ -762,10 +795,11 @@ __global__ __launch_bounds__(BM == 128 ? 256 : 512, 2) void gemm_pp_kernel(const
           *(f32x4 *)(slab + m * p.n + tile_n * BN + wn * WTN + i * 16 + 4 * fq) = acc[i][j];
       }
     }
-  } else if (p.geglu) {
+  } else if (!UP && p.geglu) {
     if constexpr (TN % 2 == 0) pp_epilogue<PBM, BN, TN, TM, WTN, WTM, true, NT>(p, acc, smem, tile_m, tile_n, wm, wn, tid, fr, fq);
   } else {
-    pp_epilogue<PBM, BN, TN, TM, WTN, WTM, false, NT, (EXP & 2048) != 0>(p, acc, smem, tile_m, tile_n, wm, wn, tid, fr, fq);
+    pp_epilogue<PBM, BN, TN, TM, WTN, WTM, false, NT, (EXP & 2048) != 0, UP>(p, acc, smem, tile_m, tile_n, wm, wn, tid, fr, fq,
+                                                                             phase);
   }
   PP_TRACE(3);
 }
@@ -779,7 +813,7 @@ int launch_pp(GemmArgs &a, hipStream_t s) {
   static bool attr_set[SP_MAX_DEVICES] = {};
   if (int rc = sp_ensure_dyn_lds((const void *)gemm_pp_kernel<BM, BN, EXP>, (int)lds, attr_set, "sp_gemm_f16(pp)"))
     return rc;
-  a.tiles_m = (a.m + BM - 1) / BM;
+  a.tiles_m = (EXP & 8192) ? 4 * a.up_tiles : (a.m + BM - 1) / BM;     // (four phases of up_tiles row tiles each)
   a.tiles_n = a.n / BN;
   note_kernel((EXP & 128) ? "gemm_pp_kernel<%d, %d, %d> + splitk_reduce_kernel" : "gemm_pp_kernel<%d, %d, %d>", BM, BN, EXP);
   SP_CLEAR_STALE_ERROR();
@@ -790,6 +824,10 @@ int launch_pp(GemmArgs &a, hipStream_t s) {
 }
 
 }  // namespace
+
+int launch_pp_up2x(GemmArgs &a, int bn, hipStream_t s) {
+  return bn == 256 ? launch_pp<256, 256, 8192>(a, s) : launch_pp<256, 320, 8192>(a, s);
+}
 
 int launch_pp(GemmArgs &a, int bm, int bn, hipStream_t s) {
   if (a.ksplit >= 1 && a.partial) return launch_pp<256, 256, 128>(a, s);   // raw fp32 sums per K slice (1 slice: sp_gemm_f32out_f16)

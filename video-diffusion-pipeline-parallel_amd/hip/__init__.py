@@ -54,6 +54,7 @@ SIGNATURES = {
     "sp_gemm_workspace_bytes": (_Z, [ctypes.POINTER(GemmDesc)]),
     "sp_gemm_set_route": (_I, [_I, _I, _I]),
     "sp_gemm_last_kernel": (ctypes.c_char_p, []),
+    "sp_conv_up2x_f16": (_I, [_P, _L, _I, _I, _I, _I, _P, _I, _P, _P, _L, _P, _P, _P]),
     "sp_gemv_f16": (_I, [_P, _L, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P]),
     "sp_gemv_batched_f16": (_I, [_P, _L, _L, _P, _L, _P, _L, _P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _P]),
     "sp_sinusoid_f16": (_I, [_P, _P, _I, _I, _P]),

@@ -83,11 +83,24 @@ def gemm(a, w, out, *, m, n, cin, mode=A_LINEAR, lda=None, conv=None, temporal=N
          bias2=None, bias2_rows=0, ldb2=0, res1=None, r1scale=1.0, res2=None, r2scale=1.0, oscale=1.0,
          geglu=False, n_store=0, ldd=None, ldr1=None, ldr2=None, ln_stats=None, ln_colsum=None, euler=None,
          workspace=None, ln_out=None, ln_out_eps=1e-5, w_group_rows=0, w_group_stride=0, gn_part=None, a2=None, cin2=0,
-         lda2=None):
+         lda2=None, up2x_phases=False):
     """``out[m][:] = epilogue(sum_taps A_tap @ W^T)``; see ``sp_gemm_desc`` in include/svdpipe.h.
     ``ln_stats`` / ``ln_colsum``: LayerNorm folded into the contraction (``a`` is the UN-normalised tensor).
     ``w_group_rows`` / ``w_group_stride``: ``w`` holds one weight matrix per group of that many output rows (a GroupNorm
-    folded into this linear layer, ``groupnorm_fold_linear``)."""
+    folded into this linear layer, ``groupnorm_fold_linear``).
+    ``up2x_phases``: an upsampling convolution (``mode=A_CONV3X3``, ``conv[-1] == 1``) as four 2x2 phase convolutions;
+    ``w`` is then the phase-major pack ``[4][n][4*cin]`` (``weights.pack_conv3x3_up2x``), bias only (``sp_conv_up2x_f16``)."""
+    if up2x_phases:
+        # the phase entry takes a bias and nothing else of the epilogue: every other keyword must be at its neutral value
+        # (``workspace`` is scratch the call may leave unused; pitches and scales of absent operands mean nothing)
+        refused = dict(temporal=(temporal, None), bias2=(bias2, None), res1=(res1, None), res2=(res2, None),
+                       ln_stats=(ln_stats, None), ln_colsum=(ln_colsum, None), euler=(euler, None), ln_out=(ln_out, None),
+                       a2=(a2, None), geglu=(bool(geglu), False), n_store=(n_store, 0), w_group_rows=(w_group_rows, 0),
+                       oscale=(oscale, 1.0))
+        extra = sorted(k for k, (v, neutral) in refused.items() if (v is not None if neutral is None else v != neutral))
+        if extra:
+            raise ValueError(f"gemm(up2x_phases=True) takes a bias only; got {', '.join(extra)}")
+        return _conv_up2x(a, w, out, m=m, n=n, cin=cin, mode=mode, lda=lda, conv=conv, bias=bias, ldd=ldd, gn_part=gn_part)
     d = GemmDesc()
     d.lda = int(lda if lda is not None else cin)
     d.a, d.mode, d.cin = _rows(a, "a", d.lda).data_ptr(), mode, cin
@@ -135,6 +148,32 @@ def gemm(a, w, out, *, m, n, cin, mode=A_LINEAR, lda=None, conv=None, temporal=N
     with _Timed("gemm", 2.0 * m * n * (taps * cin + k2), nbytes, (m, n, cin, mode, bool(geglu))) as tm:
         _check(load().sp_gemm_f16(ctypes.byref(d), _stream()), "sp_gemm_f16")
         if PROFILE is not None:      # which kernel template took it (per-template FLOPs in the profile summary)
+            tm.tag = tm.tag + (load().sp_gemm_last_kernel().decode(),)
+    return out
+
+
+def _conv_up2x(a, w, out, *, m, n, cin, mode, lda, conv, bias, ldd, gn_part):
+    """The ``up2x_phases`` leg of :func:`gemm`: same launch record (kind ``"gemm"``, same tag form), executed FLOPs."""
+    if mode != A_CONV3X3 or conv is None or conv[-1] != 1 or conv[5] != 1:
+        raise ValueError("gemm(up2x_phases=True) needs mode=A_CONV3X3 and an upsampling geometry (stride 1, upsample2x = 1)")
+    n_img, hin, win, hout, wout = conv[:5]
+    if (hout, wout) != (2 * hin, 2 * win) or m != n_img * hout * wout:
+        raise ValueError(f"gemm(up2x_phases=True): m = {m}, output {hout}x{wout} do not match {n_img} images of {hin}x{win} doubled")
+    if tuple(_f16(w, "w").shape) != (4, n, 4 * cin) or not w.is_contiguous():
+        raise ValueError(f"gemm(up2x_phases=True): w must be the contiguous phase-major pack [4][{n}][{4 * cin}]; got {tuple(w.shape)}")
+    lda = int(lda if lda is not None else cin)
+    ldd = int(ldd if ldd is not None else n)
+    _rows(a, "a", lda)
+    _rows(out, "out", ldd)
+    if gn_part is not None:            # fp32 [m/256][2][n][2], a frame's 4 * (hin*win/256) tiles contiguous (svdpipe.h)
+        if gn_part.dtype != torch.float32 or not gn_part.is_cuda or gn_part.numel() < (m // 256) * 2 * n * 2:
+            raise TypeError("gn_part must be a float32 HIP tensor of (m/256)*2*n*2 elements")
+    # algorithmic bytes: every operand element once (the four phases' weights are 16*cin per output channel), output once
+    nbytes = 2.0 * (n_img * hin * win * cin + n * 16 * cin + m * n)
+    with _Timed("gemm", 2.0 * m * n * 4 * cin, nbytes, (m, n, cin, mode, False)) as tm:
+        _check(load().sp_conv_up2x_f16(a.data_ptr(), lda, cin, n_img, hin, win, w.data_ptr(), n, _ptr(bias), out.data_ptr(),
+                                       ldd, _ptr(gn_part), zero_page(a.device).data_ptr(), _stream()), "sp_conv_up2x_f16")
+        if PROFILE is not None:
             tm.tag = tm.tag + (load().sp_gemm_last_kernel().decode(),)
     return out
 

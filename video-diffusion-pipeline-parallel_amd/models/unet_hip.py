@@ -137,6 +137,9 @@ class SVDUNetHIP:
         # LayerNorm row statistics from the producing contraction's epilogue also for rows of three / four column tiles
         # (1,280 channels at the 576-token level)
         self.ln_out_wide = os.environ.get("VDPP_LN_OUT_WIDE", "1") != "0"
+        # the up blocks' "nearest x2, then 3x3" convolutions as four 2x2 phase convolutions with pre-summed weights (K = 4*C
+        # instead of 9*C; _upsample_plan has the rule).  VDPP_UPSAMPLE_PHASES=0: always the nine-tap gather
+        self.upsample_phases = os.environ.get("VDPP_UPSAMPLE_PHASES", "1") != "0"
         self.device = dev = common.hip_device(device, "SVDUNetHIP")
         sd = state_dict
         self._temb_w, self._temb_b, self._temb_n = [], [], 0
@@ -179,6 +182,12 @@ class SVDUNetHIP:
                 if attn:
                     att.append(self._transformer(sd, f"up_blocks.{i}.attentions.{j}", out_ch))
             us = _Dense.conv3x3(sd, f"up_blocks.{i}.upsamplers.0.conv", dev) if ups else None
+            if us is not None and us.n == us.n_true and (us.n % 256 == 0 or us.n % 320 == 0):
+                # the phase pack beside the nine-tap one (16/9 of its size: 118 MB more for the three layers of SVD).  Both
+                # are kept whatever ``upsample_phases`` says at construction: it is an attribute that may be flipped on a
+                # live engine (tools/ab_forward.py alternates the arms in one process), and _upsample_plan falls back to the
+                # nine taps layer by layer.  An engine that will never take the phase path can ``del us.w_up2x``.
+                us.w_up2x = W.pack_conv3x3_up2x(sd[f"up_blocks.{i}.upsamplers.0.conv.weight"].to(dev), us.cin, us.n)
             self.up.append((res, att, us))
         self.norm_out = _Norm(sd, "conv_norm_out", dev, 1e-5)
         self.conv_out = _Dense.conv3x3(sd, "conv_out", dev)
@@ -359,7 +368,7 @@ class SVDUNetHIP:
         # ``w_groups`` = (w_f [instances][n][c] fp16, bias_f [instances][n] fp32, rows per instance): a GroupNorm folded
         # into this linear layer (ops.groupnorm_fold_linear) -- every instance's rows meet their own scaled weights
         w_groups = kw.pop("w_groups", None)
-        weight, bias = layer.w, layer.bias
+        weight, bias = kw.pop("weight", layer.w), layer.bias      # (``weight``: another pack of the layer's weights)
         if w_groups is not None:
             weight, bias = w_groups[0], None
             kw.update(bias2=w_groups[1], bias2_rows=w_groups[2], w_group_rows=w_groups[2],
@@ -434,6 +443,26 @@ class SVDUNetHIP:
         ops.groupnorm(x, norm.g, norm.b, y, instances=inst, rows=rows, c=c, groups=groups,
                       eps=norm.eps, silu=silu, ws=r.gn_ws, ldx=x.stride(0))
         return y
+
+    def _upsample_plan(self, us: _Dense, n_img, hin, win):
+        """(phases, sums) for the upsampling convolution of ``n_img`` images of ``hin`` x ``win``: run it as four 2x2 phase
+        convolutions?  may its epilogue leave the next GroupNorm's column sums?  The phase kernel leaves them only where a
+        SOURCE frame is whole 256-row tiles; the nine-tap kernel where an OUTPUT frame is.  Where the phase path would take
+        sums away from a norm that folds them today, that norm gets its statistics pass back, so the phases must save
+        clearly more than the pass costs."""
+        hout, wout = 2 * hin, 2 * win
+        m_out = n_img * hout * wout
+        nine_tap_sums = (hout * wout) % 256 == 0 and m_out % 256 == 0
+        if not self.upsample_phases or getattr(us, "w_up2x", None) is None:
+            return False, True                            # (_gemm knows where the nine-tap kernel can leave them)
+        if nine_tap_sums and (hin * win) % 256 != 0:
+            # round figures from profiles/: the large-K convolutions run at about 1 PFLOP/s in the forward (10 = 2 * (9 - 4)
+            # FLOPs saved per row, column and channel), a statistics pass at about 4 TB/s behind a 10 us launch
+            saved = 10.0 * m_out * us.n * us.cin / 1e15
+            stats_pass = 10e-6 + 2.0 * m_out * us.n / 4e12
+            if saved < 2.0 * stats_pass:
+                return False, True
+        return True, (hin * win) % 256 == 0
 
     def _conv_geom(self, r: _Run, stride=1, ups=0):
         hv, wv = r.h << ups, r.w << ups
@@ -694,7 +723,9 @@ class SVDUNetHIP:
                 geom, ho, wo = self._conv_geom(r, ups=1)
                 m_up = r.b * r.f * ho * wo
                 r.h, r.w = ho, wo                    # (the output's level decides whether its frames are whole tiles)
-                x = skips.left(self._gemm(r, us, x.t, m=m_up, conv=geom, out=skips.left_dest(), gn_next=True))
+                phases, sums = self._upsample_plan(us, *geom[:3])
+                up = dict(up2x_phases=True, weight=us.w_up2x) if phases else {}
+                x = skips.left(self._gemm(r, us, x.t, m=m_up, conv=geom, out=skips.left_dest(), gn_next=sums, **up))
         x = self._gn(r, self.norm_out, x, temporal=False, silu=True)
         geom, _, _ = self._conv_geom(r)
         if euler is not None:
