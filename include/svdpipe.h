@@ -520,6 +520,52 @@ int sp_gif_lzw(const void *indices, int n, int h, int w, int strip_rows, void *o
                size_t ws_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * PNG / APNG frames of uint8 frames that are in device memory (the lossless output: the reference writes frames through
+ * imageio / Pillow on the host).  Two stages: the filtered rows of every frame, then the complete zlib stream of a frame's
+ * filtered bytes.  Signature, chunks and their CRC-32 are host work: a CRC covers compressed bytes that the host has anyway
+ * (zlib.crc32); the Adler-32 inside the stream covers the filtered bytes, which never leave the device, and is made there.
+ * h and w are 1..65535 with h*w <= 2^24; strip_rows >= 1 (a value above h means h).  The size functions need no GPU and give
+ * 0 for arguments the kernels refuse.
+ * ------------------------------------------------------------------------------------------- */
+/* Scratch of the deflate stage for n frames: per (frame, strip) four int32 (bits, bit offset, two Adler partials), an int32
+ * per frame, and a staging slot per (frame, strip) of the strip's worst case in whole words plus one. */
+size_t sp_png_ws_bytes(int n, int h, int w, int strip_rows);
+/* Bytes of zlib stream no frame can exceed.  Bits per strip: a block header of at most
+ *   3 + 14 + 19*3 + (286 + 2) * 14 = 4106
+ * (BFINAL and BTYPE; HLIT, HDIST, HCLEN; 19 lengths of 3 bits; per code length a run-length symbol of at most 7 bits and at
+ * most 7 extra bits), at most 15 bits per token and at most one token per byte (a literal has at most 15 bits; a match has
+ * at most 15 + 5 + 1 and covers at least 3 bytes), and an end-of-block code of at most 15 bits.  With strips =
+ * ceil(h / strip_rows):
+ *   result = 2 + ceil((strips * (4106 + 15) + 15 * h * (1 + 3*w)) / 8) + 4. */
+size_t sp_png_stream_bytes(int h, int w, int strip_rows);
+/* frames: uint8 [n][h][w][3] RGB -> filtered: uint8 [n][h][1 + 3*w], the rows of an 8-bit RGB image without interlace, each
+ * behind its filter type.  Every row takes the type (0 None, 1 Sub, 2 Up, 3 Average, 4 Paeth; bpp = 3) with the least sum of
+ * min(b, 256 - b) over its filtered bytes, the lowest type among equals.  The row above is the frame's own (zeros above row
+ * 0), so every row is independent. */
+int sp_png_filter_u8(const void *frames, int n, int h, int w, void *filtered, void *stream);
+/* filtered: uint8 [n][h][1 + 3*w] -> frame i's complete zlib stream at out + i*cap, its length in out_len[i] (int32, device):
+ * 78 9C, the deflate blocks of the strips joined bit by bit, zero bits up to a byte, the Adler-32 of the frame's filtered
+ * bytes, big-endian.  A strip is strip_rows rows, tags included (the last may be shorter), and one dynamic-Huffman block
+ * (BTYPE 2); BFINAL is set on the frame's last strip only.  Nothing refers back across the start of a strip.
+ *   tokens   the strip's first byte is a literal.  At a later position p, r is the number of bytes from p on that equal byte
+ *            p-1, capped at 258 and at the strip's end: r >= 3 gives a match of length r at distance 1 and p += r, else the
+ *            literal at p.  (Per run of n equal bytes: a literal, floor((n-1) / 258) matches of 258, then the remainder as a
+ *            match if it is at least 3, else as literals.)
+ *   codes    literal/length code lengths: plain Huffman over the strip's counts with end-of-block counted once.  The two
+ *            least nodes are joined until one is left; nodes are ordered by weight, then by age: the leaves, in order of
+ *            (count, symbol), are older than every joined node, and joined nodes age in order of their making.  A code with
+ *            fewer than two symbols in use gives count 1 to its lowest unused symbols first.  While a length passes 15,
+ *            every non-zero count f becomes (f + 1) >> 1 and the code is made again.  Codes are the canonical ones of RFC
+ *            1951 3.2.2.  The distance code is constant: symbols 0 and 1 with one bit each; a match's distance is the bit 0.
+ *   header   HLIT and HCLEN trimmed as in RFC 1951, HDIST = 1; the code lengths in zlib's run-length form (16 / 17 / 18;
+ *            the literal/length lengths and the two distance lengths are scanned separately); the 19-symbol code by the
+ *            same construction with limit 7.
+ * Deflate packs least significant bit first; Huffman codes go in most significant bit first.  cap below
+ * sp_png_stream_bytes is refused; bytes of a slot beyond out_len[i] are not written.  ws: sp_png_ws_bytes, 8-byte aligned. */
+int sp_png_deflate(const void *filtered, int n, int h, int w, int strip_rows, void *out, size_t cap, void *out_len, void *ws,
+                   size_t ws_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement aid (bench.py `roofline.clock_ghz_live`; the reference has no counterpart -- its benchmark reads no clocks,
  * /root/reference/src/modes/benchmark.py:170-262).  One time stamp in stream order: `blocks` one-wave workgroups each write
  * four u64 words to out[block][4]: the id of the XCD the workgroup ran on (HW_REG_XCC_ID), the shader-clock counter

@@ -624,6 +624,44 @@ def gif_lzw(indices, out, out_len, ws, *, strip_rows):
     return out, out_len
 
 
+def png_ws_bytes(n: int, h: int, w: int, strip_rows: int) -> int:
+    return int(load().sp_png_ws_bytes(n, h, w, strip_rows))
+
+
+def png_stream_bytes(h: int, w: int, strip_rows: int) -> int:
+    return int(load().sp_png_stream_bytes(h, w, strip_rows))
+
+
+def png_filter(frames_u8, filtered):
+    """uint8 (n, h, w, 3) RGB -> ``filtered`` uint8 (n, h, 1 + 3w): every row behind the PNG filter type that gives the least
+    sum of min(b, 256 - b) (``sp_png_filter_u8``)."""
+    _dev_buf(frames_u8, torch.uint8, "png_filter: frames")
+    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
+        raise ValueError(f"png_filter: frames must be (n, h, w, 3); got {tuple(frames_u8.shape)}")
+    n, h, w, _ = frames_u8.shape
+    _dev_buf(filtered, torch.uint8, "png_filter: filtered")
+    if tuple(filtered.shape) != (n, h, 1 + 3 * w):
+        raise ValueError(f"png_filter: filtered must be {(n, h, 1 + 3 * w)}; got {tuple(filtered.shape)}")
+    _check(load().sp_png_filter_u8(frames_u8.data_ptr(), n, h, w, filtered.data_ptr(), _stream()), "sp_png_filter_u8")
+    return filtered
+
+
+def png_deflate(filtered, out, out_len, ws, *, strip_rows):
+    """uint8 ``filtered`` (n, h, 1 + 3w) -> frame i's complete zlib stream in ``out[i, :out_len[i]]`` (``out``: uint8 (n, cap),
+    cap >= ``png_stream_bytes``; ``out_len``: int32 (n,); ``ws``: uint8 scratch of ``png_ws_bytes``)."""
+    _dev_buf(filtered, torch.uint8, "png_deflate: filtered")
+    if filtered.dim() != 3 or filtered.shape[2] < 4 or (filtered.shape[2] - 1) % 3:
+        raise ValueError(f"png_deflate: filtered must be (n, h, 1 + 3w); got {tuple(filtered.shape)}")
+    n, h, pitch = filtered.shape
+    _dev_buf(out, torch.uint8, "png_deflate: out"), _dev_buf(ws, torch.uint8, "png_deflate: ws")
+    _dev_buf(out_len, torch.int32, "png_deflate: out_len")
+    if out.dim() != 2 or out.shape[0] != n or out_len.numel() != n:
+        raise ValueError("png_deflate: out must be (n, cap) and out_len (n,)")
+    _check(load().sp_png_deflate(filtered.data_ptr(), n, h, (pitch - 1) // 3, int(strip_rows), out.data_ptr(), out.shape[1],
+                                 out_len.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "sp_png_deflate")
+    return out, out_len
+
+
 class ClockStamps:
     """Stamps of the shader-clock counter against the constant 100 MHz counter, taken in stream order between other work
     (``sp_clock_stamp``; bench.py ``roofline.clock_ghz_live``).  ``stamp()`` enqueues one on the current stream (a ~2 us

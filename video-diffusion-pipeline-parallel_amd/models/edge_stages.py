@@ -147,7 +147,8 @@ class FrameEmitter:
     videos, ready for ``image_io.write_avi``: the encoder's buffers are reused, so a sample's bytes are fetched when the next
     sample finishes on this rank (its decode is long over by then) or in ``finish``.  ``output="gif"`` does the same with
     ``image_io.GifEncoder`` at ``gif_fps`` frames per second and keeps, per sample, one ``bytes`` (a complete animated GIF) for
-    each of its B videos.
+    each of its B videos.  ``output="png"`` mirrors ``"jpeg"`` with ``image_io.PngEncoder``: per sample one ``list[bytes]`` of F PNG
+    files (lossless) for each of its B videos.
     """
 
     def __init__(self, decoder: TemporalDecoderHIP, stage, num_frames: int, *, decode_chunk_size: int = 14,
@@ -157,8 +158,8 @@ class FrameEmitter:
 
         if keep not in ("all", "last", "none"):
             raise ValueError("keep must be 'all', 'last' or 'none'")
-        if output not in ("float32", "uint8", "jpeg", "gif"):
-            raise ValueError("output must be 'float32', 'uint8', 'jpeg' or 'gif'")
+        if output not in ("float32", "uint8", "jpeg", "gif", "png"):
+            raise ValueError("output must be 'float32', 'uint8', 'jpeg', 'gif' or 'png'")
         if check_finite and output != "float32":
             raise ValueError("check_finite needs output='float32' (an 8-bit level cannot show a non-finite value)")
         if output == "jpeg" and not (isinstance(jpeg_quality, int) and 1 <= jpeg_quality <= 100):
@@ -166,7 +167,7 @@ class FrameEmitter:
         if output == "gif" and (isinstance(gif_fps, bool) or not isinstance(gif_fps, (int, float)) or not gif_fps > 0):
             raise ValueError(f"gif_fps must be a positive number; got {gif_fps!r}")
         self.output, self.jpeg_quality, self.gif_fps = output, jpeg_quality, gif_fps
-        self._jpeg = None               # the JpegEncoder, made for the first sample's frame size
+        self._jpeg = None               # the JpegEncoder (or, for output="png", the PngEncoder), made for the first sample's frame size
         self._gif = None                # the GifEncoders, one per video of a sample (a video's buffers wait for the fetch)
         self._pending = None            # (sample index, videos, streams, lengths, event) of the encode still on the device
         self.decoder, self.stage, self.num_frames = decoder, stage, num_frames
@@ -201,14 +202,15 @@ class FrameEmitter:
         latent.record_stream(self.stream)
         with torch.cuda.stream(self.stream):
             self.stream.wait_event(ready)
-            if self.output in ("jpeg", "gif"):
+            if self.output in ("jpeg", "gif", "png"):
                 self._collect_jpeg()           # before this decode is queued: the encoder's buffers are free again after it
             decode = self.decoder.decode_latents if self.output == "float32" else self.decoder.decode_latents_uint8
             out = decode(latent.contiguous(), self.num_frames, decode_chunk_size=self.chunk)
-            if self.output == "jpeg":
+            if self.output in ("jpeg", "png"):
                 if self._jpeg is None or (self._jpeg.height, self._jpeg.width) != tuple(out.shape[2:4]):
-                    from .image_io import JpegEncoder
-                    self._jpeg = JpegEncoder(self.device, out.shape[2], out.shape[3], self.jpeg_quality)
+                    from .image_io import JpegEncoder, PngEncoder
+                    self._jpeg = (JpegEncoder(self.device, out.shape[2], out.shape[3], self.jpeg_quality) if self.output == "jpeg"
+                                  else PngEncoder(self.device, out.shape[2], out.shape[3]))
                 streams, lens = self._jpeg.enqueue(out.flatten(0, 1))
                 done = torch.cuda.Event()
                 done.record(self.stream)
@@ -222,7 +224,7 @@ class FrameEmitter:
                 done.record(self.stream)
                 self._pending = (idx, out.shape[0], bufs, None, done)
         self.stats["decoded"] += 1
-        if self.output in ("jpeg", "gif"):
+        if self.output in ("jpeg", "gif", "png"):
             return
         self._keep(idx, out)
 

@@ -12,6 +12,9 @@
     bytes come to the host; the marker segments and the RIFF container are written here.
   * ``GifEncoder`` / ``write_gif``: the animated GIF of ``save_gif``: frames on the device are quantised to a palette each
     and LZW-coded there by the kernels of ``csrc/gif.hip``; the blocks of the file around them are written here.
+  * ``PngEncoder`` / ``png_file`` / ``write_apng``: the lossless frames (a directory or a ``%03d.png`` pattern) and an
+    animated PNG: frames on the device are filtered and deflated there by the kernels of ``csrc/png.hip``; signature, chunks
+    and their CRC-32 (over compressed bytes the host has anyway) are written here.
   * ``load_image``: the decode half of ``load_and_preprocess_image`` (Pillow; a file format is host work).
 """
 
@@ -19,6 +22,8 @@ from __future__ import annotations
 
 import os
 import struct
+import zlib
+from fractions import Fraction
 
 import numpy as np
 import torch
@@ -350,6 +355,120 @@ class GifEncoder:
         return self.collect(*bufs)
 
 
+PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+
+
+def _png_chunk(kind: bytes, payload: bytes) -> bytes:
+    return struct.pack(">I", len(payload)) + kind + payload + struct.pack(">I", zlib.crc32(payload, zlib.crc32(kind)))
+
+
+def _png_ihdr(height: int, width: int) -> bytes:
+    if not (1 <= width <= 2 ** 31 - 1 and 1 <= height <= 2 ** 31 - 1):
+        raise ValueError(f"a PNG is 1..2^31-1 pixels on a side; got {height}x{width}")
+    return _png_chunk(b"IHDR", struct.pack(">IIBBBBB", width, height, 8, 2, 0, 0, 0))       # 8 bit, RGB, no interlace
+
+
+def png_file(height: int, width: int, zlib_stream: bytes) -> bytes:
+    """A PNG file around the zlib stream of an 8-bit RGB image's filtered rows (what ``sp_png_deflate`` writes): signature,
+    IHDR, one IDAT, IEND.  The CRC-32 of every chunk is computed here (``zlib.crc32``)."""
+    return PNG_SIGNATURE + _png_ihdr(height, width) + _png_chunk(b"IDAT", bytes(zlib_stream)) + _png_chunk(b"IEND", b"")
+
+
+def write_apng(path, streams, width: int, height: int, fps=7) -> bytes:
+    """An animated PNG that loops for ever, returned as ``bytes`` and written to ``path`` unless that is ``None``: signature,
+    IHDR, acTL (``num_plays`` 0), and per frame an fcTL (the whole frame, delay ``1 / fps`` s as a fraction of two 16-bit
+    numbers, dispose none, blend source) and its zlib stream, in IDAT for frame 0 and in fdAT behind a sequence number for the
+    others; then IEND.  A viewer that knows no APNG shows frame 0."""
+    if len(streams) == 0:
+        raise ValueError("write_apng: no frames")
+    delay = (1 / Fraction(_check_fps(fps))).limit_denominator(65535)
+    if not 0 < delay.numerator <= 65535:
+        raise ValueError(f"write_apng: a delay of 1 / {fps} s does not fit the frame control chunk")
+    out, seq = [PNG_SIGNATURE, _png_ihdr(height, width), _png_chunk(b"acTL", struct.pack(">II", len(streams), 0))], 0
+    for i, stream in enumerate(streams):
+        out.append(_png_chunk(b"fcTL", struct.pack(">IIIIIHHBB", seq, width, height, 0, 0, delay.numerator, delay.denominator, 0, 0)))
+        seq += 1
+        if i == 0:
+            out.append(_png_chunk(b"IDAT", bytes(stream)))
+        else:
+            out.append(_png_chunk(b"fdAT", struct.pack(">I", seq) + bytes(stream)))
+            seq += 1
+    out.append(_png_chunk(b"IEND", b""))
+    blob = b"".join(out)
+    if path is not None:
+        with open(path, "wb") as fh:
+            fh.write(blob)
+    return blob
+
+
+PNG_STRIP_ROWS = 16                  # the fastest of 4 / 8 / 16 / 32 rows within 1 % of one strip per frame (profiles/png_timing.txt)
+
+
+class PngEncoder:
+    """(F, H, W, 3) uint8 frames on the device -> one PNG file per frame, filtered and deflated on the device (``csrc/png.hip``).
+
+    Every row takes the filter with the least sum of min(b, 256 - b); a frame is coded in strips of ``strip_rows`` rows, each
+    one dynamic-Huffman block of literals and of matches at distance 1 (zlib's ``Z_RLE`` idea), so that a frame is many
+    independent sequences; at 576 x 1024 strips of 16 rows cost 0.11 % in size over one strip per frame and are the fastest
+    measured (profiles/png_timing.txt).  Filtered, stream, length and scratch
+    buffers are kept per frame count; the stream buffer holds ``sp_png_stream_bytes`` per frame (the size no input can exceed),
+    of which only the used bytes are ever copied to the host."""
+
+    def __init__(self, device, height: int, width: int, strip_rows: int = PNG_STRIP_ROWS) -> None:
+        self.device = common.hip_device(device, "PngEncoder")
+        self.height, self.width = int(height), int(width)
+        if isinstance(strip_rows, bool) or not isinstance(strip_rows, (int, np.integer)) or strip_rows < 1:
+            raise ValueError(f"strip_rows must be a positive integer; got {strip_rows!r}")
+        self.strip_rows = int(strip_rows)
+        self.cap = ops.png_stream_bytes(self.height, self.width, self.strip_rows)
+        if self.cap == 0:
+            raise ValueError(f"a frame for the PNG kernels is 1..65535 pixels on a side and at most 2^24 in all; got {height}x{width}")
+        self._scratch: dict = {}
+
+    def _buf(self, name: str, shape, dtype) -> torch.Tensor:
+        key = (name, shape)
+        if key not in self._scratch:
+            self._scratch[key] = torch.empty(shape, dtype=dtype, device=self.device)
+        return self._scratch[key]
+
+    def enqueue(self, frames_u8: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+        """Run the two stages on the current stream and return ``(streams (F, cap) uint8, lengths (F,) int32)``: views of
+        this encoder's buffers, valid until the next call with as many frames."""
+        if (not isinstance(frames_u8, torch.Tensor) or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4
+                or tuple(frames_u8.shape[1:]) != (self.height, self.width, 3) or frames_u8.shape[0] == 0):
+            raise ValueError(f"frames must be a (F, {self.height}, {self.width}, 3) uint8 tensor; got "
+                             f"{getattr(frames_u8, 'dtype', type(frames_u8))} {tuple(getattr(frames_u8, 'shape', ()))}")
+        n = frames_u8.shape[0]
+        filtered = self._buf("filtered", (n, self.height, 1 + 3 * self.width), torch.uint8)
+        out = self._buf("stream", (n, self.cap), torch.uint8)
+        lens = self._buf("len", (n,), torch.int32)
+        ws = self._buf("ws", (ops.png_ws_bytes(n, self.height, self.width, self.strip_rows),), torch.uint8)
+        ops.png_filter(frames_u8.to(self.device).contiguous(), filtered)
+        ops.png_deflate(filtered, out, lens, ws, strip_rows=self.strip_rows)
+        return out, lens
+
+    def collect_streams(self, out: torch.Tensor, lens: torch.Tensor) -> list[bytes]:
+        """The zlib streams of an ``enqueue`` whose work has finished: the lengths come to the host first, then only the used
+        bytes."""
+        return [out[i, :n].cpu().numpy().tobytes() for i, n in enumerate(lens.cpu().tolist())]
+
+    def collect(self, out: torch.Tensor, lens: torch.Tensor) -> list[bytes]:
+        """The PNG files of an ``enqueue`` whose work has finished."""
+        return [png_file(self.height, self.width, s) for s in self.collect_streams(out, lens)]
+
+    def encode(self, frames_u8: torch.Tensor) -> list[bytes]:
+        out, lens = self.enqueue(frames_u8)
+        torch.cuda.current_stream(self.device).synchronize()
+        return self.collect(out, lens)
+
+    def encode_apng(self, frames_u8: torch.Tensor, fps=7) -> bytes:
+        """One animated PNG of the frames (``write_apng`` around the same streams)."""
+        _check_fps(fps)
+        out, lens = self.enqueue(frames_u8)
+        torch.cuda.current_stream(self.device).synchronize()
+        return write_apng(None, self.collect_streams(out, lens), self.width, self.height, fps)
+
+
 def _jpeg_frames(frames_u8, quality: int) -> tuple[list[bytes], int, int]:
     """``(files, height, width)``: a tensor on a GPU is compressed there (``JpegEncoder``), anything else by Pillow."""
     if isinstance(frames_u8, torch.Tensor) and frames_u8.is_cuda:
@@ -376,13 +495,21 @@ def save_frames(frames_u8, path: str, fps: int = 7, quality: int = 90) -> list[s
     ``*.png`` pattern: one PNG per frame.  ``quality`` (1..100) is that of the JPEG frames; a tensor on a GPU is compressed
     there and only the compressed bytes are copied.  The same holds for ``*.gif``: a tensor on a GPU is quantised and
     LZW-coded there (``GifEncoder``: a palette per frame, strips of 8 rows, delays in whole centiseconds), while an array in
-    host memory goes through Pillow as before, byte for byte.  ``*.mp4`` is refused: imageio / ffmpeg are not dependencies."""
+    host memory goes through Pillow as before, byte for byte.  PNG frames (a directory or a ``%03d.png`` pattern) and
+    ``*.apng`` (one animated PNG, lossless, ``1 / fps`` s per frame) of a tensor on a GPU are filtered and deflated there
+    (``PngEncoder``); an array in host memory goes through Pillow.  ``*.mp4`` is refused: imageio / ffmpeg are not dependencies."""
     path = os.fspath(path)
     ext = os.path.splitext(path)[1].lower()
     # frames on a GPU stay there for the targets that are compressed there; everything else is host work on an array
-    on_gpu = isinstance(frames_u8, torch.Tensor) and frames_u8.is_cuda and ext in (".avi", ".jpg", ".jpeg", ".gif")
+    on_gpu = isinstance(frames_u8, torch.Tensor) and frames_u8.is_cuda and ext in (".avi", ".jpg", ".jpeg", ".gif", ".apng", "")
     if on_gpu and ext == ".gif" and frames_u8.dim() == 4 and frames_u8.shape[1] * frames_u8.shape[2] > 2 ** 24:
         on_gpu = False                 # beyond what sp_gif_quantise_u8 takes: the route such frames always had
+    if isinstance(frames_u8, torch.Tensor) and frames_u8.is_cuda and ext == ".png" and "%" in path:
+        on_gpu = True                  # (a bare x.png is refused below, as it always was)
+    if on_gpu and ext in (".png", ".apng", ""):
+        # frames the PNG kernels do not take (or that are no frames at all) keep the host route and its messages
+        on_gpu = (frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4 and frames_u8.shape[3] == 3 and frames_u8.shape[0] > 0
+                  and ops.png_stream_bytes(frames_u8.shape[1], frames_u8.shape[2], PNG_STRIP_ROWS) > 0)
     a = None if on_gpu else _frames_array(frames_u8)
     if ext in (".mp4", ".mov", ".mkv", ".webm"):
         raise ValueError(f"cannot write '{path}': video encoding needs imageio / ffmpeg, which this package does not depend "
@@ -414,8 +541,28 @@ def save_frames(frames_u8, path: str, fps: int = 7, quality: int = 90) -> list[s
         with open(path, "wb") as fh:
             fh.write(data)
         return [path]
+    if on_gpu and ext in (".png", ".apng", ""):
+        enc = PngEncoder(frames_u8.device, frames_u8.shape[1], frames_u8.shape[2])
+        if ext == ".apng":
+            data = enc.encode_apng(frames_u8, fps)
+            with open(path, "wb") as fh:
+                fh.write(data)
+            return [path]
+        if ext == "":
+            os.makedirs(path, exist_ok=True)
+        pattern = path if ext == ".png" else os.path.join(path, "%03d.png")
+        files = [pattern % i for i in range(frames_u8.shape[0])]
+        for name, data in zip(files, enc.encode(frames_u8)):
+            with open(name, "wb") as fh:
+                fh.write(data)
+        return files
     from PIL import Image
 
+    if ext == ".apng":
+        _check_fps(fps)
+        ims = [Image.fromarray(f) for f in a]
+        ims[0].save(path, format="PNG", save_all=True, append_images=ims[1:], loop=0, duration=1000.0 / fps)
+        return [path]
     if ext == ".gif":
         if fps <= 0:
             raise ValueError("fps must be positive")
@@ -430,7 +577,7 @@ def save_frames(frames_u8, path: str, fps: int = 7, quality: int = 90) -> list[s
         os.makedirs(path, exist_ok=True)
         pattern = os.path.join(path, "%03d.png")
     else:
-        raise ValueError(f"'{path}': unknown output format {ext!r} (.avi, .gif, .npy, %03d.jpg / %03d.png pattern or a "
+        raise ValueError(f"'{path}': unknown output format {ext!r} (.avi, .gif, .apng, .npy, %03d.jpg / %03d.png pattern or a "
                          f"directory)")
     files = []
     for i, f in enumerate(a):

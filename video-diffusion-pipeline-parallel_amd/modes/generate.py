@@ -14,7 +14,8 @@ with the finished latents decodes them to 8-bit frames (``decode_latents_uint8``
 ``.avi`` -- Motion-JPEG, the video file; its frames, like those of a ``%03d.jpg`` pattern, are compressed on the GPU at
 ``--jpeg-quality`` and only the compressed bytes come to the host -- ``.gif``, the animated GIF of the demo: quantised to a
 palette per frame and LZW-coded on the GPU as well (``image_io.GifEncoder``), at ``--fps`` -- ``.npy``, a ``%03d.png`` pattern
-or a directory of PNGs).
+or a directory of PNGs, and ``.apng``, one lossless animated PNG at ``--fps``: PNG rows are filtered and deflated on the GPU
+too (``image_io.PngEncoder``)).
 """
 
 from __future__ import annotations
@@ -35,7 +36,7 @@ LOGGER = logging.getLogger(__name__)
 def parse_args(argv=None) -> argparse.Namespace:
     p = argparse.ArgumentParser(description="Generate video frames from an image (SVD step pipeline)")
     p.add_argument("--input-image", type=str, required=True, help="picture file (anything Pillow decodes)")
-    p.add_argument("--output", type=str, required=True, help=".avi (Motion-JPEG video), .gif, .npy, a %%03d.jpg or %%03d.png pattern, or a directory for PNG frames")
+    p.add_argument("--output", type=str, required=True, help=".avi (Motion-JPEG video), .gif, .apng (lossless animated PNG), .npy, a %%03d.jpg or %%03d.png pattern, or a directory for PNG frames")
     p.add_argument("--height", type=int, default=576)
     p.add_argument("--width", type=int, default=1024)
     p.add_argument("--num-frames", type=int, default=14)
