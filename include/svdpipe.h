@@ -566,6 +566,70 @@ int sp_png_deflate(const void *filtered, int n, int h, int w, int strip_rows, vo
                    size_t ws_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Lossless WebP of uint8 frames that are in device memory (the full-colour animated output: still .webp files and one
+ * animated .webp).  Two stages: the transforms of every frame (subtract green, spatial prediction), then the complete VP8L
+ * bitstream of a frame from its signature byte 0x2f on.  The RIFF container around it (RIFF / WEBP / VP8L, and VP8X / ANIM /
+ * ANMF for an animation) has no checksum and is host work.  h and w are 1..16384 (the format's 14-bit fields) with
+ * h*w <= 2^24; pred_bits is 2..9; group_bits is 0 or 2..9.  The size functions need no GPU and give 0 for arguments the
+ * kernels refuse.
+ * ------------------------------------------------------------------------------------------- */
+/* Scratch for n frames: two uint64 sums per frame (all that the transform stage uses), per segment of the stream (2 + 2G per
+ * frame, G = groups) two int32 (bits, bit offset), and a staging slot per segment of its worst case in whole words plus two. */
+size_t sp_webp_ws_bytes(int n, int h, int w, int pred_bits, int group_bits);
+/* Bytes of VP8L stream no frame can exceed.  A prefix code's header is at most 4 bits in the simple form with a 1-bit symbol,
+ * 11 with an 8-bit symbol, and in the normal form 1 + 4 + 19*3 + 1 + 14*A for an alphabet of A symbols (the form bit, the
+ * count of 19-symbol lengths, those lengths, the max_symbol bit, per code length a run-length symbol of at most 7 bits and at
+ * most 7 extra bits): 3983 for green's 280, 3647 for 256.  The main image's alpha is always 0 and its distance symbol always
+ * 1, so those two codes are simple and cost no bits per token; a group's five codes take at most
+ *   3983 + 2*3647 + 4 + 4 = 11285
+ * bits, and a token at most 45 per pixel (a literal: three codes of at most 15 bits; a copy: 15 + 10 extra bits for at least
+ * 3 pixels).  A sub-image (the mode image, the entropy image) has blue 0 and alpha 255 throughout: its codes take at most
+ *   3983 + 3647 + 4 + 11 + 4 = 7649
+ * bits and a token at most 30.  With bh x bw blocks of 2^pred_bits, G = ceil(h / 2^group_bits) groups and
+ * E = ceil(w / 2^group_bits) (G = 1 and no entropy image for group_bits = 0):
+ *   bits = 40 + 3 + 6 + 1 + 7649 + 30*bh*bw          signature and sizes, subtract green, predictor, cache bit, mode image
+ *        + 3                                         no more transforms, no colour cache, entropy image or not
+ *        + (3 + 1 + 7649 + 30*G*E  if group_bits)    its block size, its cache bit, the entropy image
+ *        + G*11285 + 45*h*w
+ *   result = ceil(bits / 8). */
+size_t sp_webp_stream_bytes(int h, int w, int pred_bits, int group_bits);
+/* frames: uint8 [n][h][w][3] RGB -> flags: int32 [n], modes: uint8 [n][bh][bw] (bh = ceil(h / 2^pred_bits), bw likewise),
+ * residual: uint8 [n][h][w][4], per pixel the residual bytes of B, G, R and of alpha, which is always 0.
+ *   flags    1 if green is taken out of red and blue before the prediction.  Over the frame, sum min(d, 256 - d) of the
+ *            left-neighbour differences d (mod 256) of the R and B bytes, once of R - G and B - G and once of R and B as they
+ *            are, in 64 bits; the flag is set when the first sum is the smaller one (ties take the plain form).
+ *   modes    pixels are ARGB with A = 255.  A block of 2^pred_bits pixels square takes, of the format's 14 predictors, the
+ *            one with the least sum of min(b, 256 - b) over its residual bytes, the lowest among equals (the first row and
+ *            column of the frame have the same residuals under every mode).  Edges are the format's: the top-left pixel
+ *            predicts 0xff000000, the top row L, the left column T, and the top-right neighbour of a row's last pixel is
+ *            the first pixel of the current row.  Predictor 13's (a - TL) / 2 truncates toward zero.
+ * ws: at least 16*n bytes, 8-byte aligned (sp_webp_ws_bytes covers it). */
+int sp_webp_transform_u8(const void *frames, int n, int h, int w, int pred_bits, void *residual, void *modes, void *flags,
+                         void *ws, size_t ws_bytes, void *stream);
+/* residual, modes, flags as above (a residual's alpha byte is ignored and coded as 0) -> frame i's complete VP8L stream at
+ * out + i*cap, its length in out_len[i] (int32, device).  In order: the signature 0x2f, w-1 and h-1 in 14 bits each, alpha 0,
+ * version 0; the subtract-green transform if flags[i]; the predictor transform with its mode image (the mode in green,
+ * alpha 255) as a sub-image with one code set; no further transform; the main image without colour cache.  For group_bits > 0
+ * an entropy image of blocks of 2^group_bits gives every block of block row g the group g (green = g & 255, red = g >> 8,
+ * alpha 255), so that a frame is coded in strips of 2^group_bits rows, each with five prefix codes of its own; group_bits = 0
+ * is one group and no entropy image.  All groups' codes come first, then the strips' pixels in order.
+ *   tokens   as sp_png_deflate's, in pixels: a strip's (or sub-image's) first pixel is a literal.  At a later position p, r is
+ *            the number of pixels from p on that equal pixel p-1, capped at 4096 and at the strip's end: r >= 3 gives a copy
+ *            of length r at distance 1 (plane code 2: distance symbol 1, no extra bits) and p += r, else the literal at p.
+ *            Runs of 1 or 2 are literals.  Nothing refers back across the start of a strip; there is no colour cache.
+ *   codes    an alphabet with fewer than two symbols in use, that symbol below 256, takes the simple form with one symbol
+ *            (symbol 0 if none is in use) and no bits per token: always so for alpha and distance.  Otherwise a normal code
+ *            by sp_png_deflate's construction (plain Huffman with its order of equal weights, count 1 for the lowest unused
+ *            symbols of a one-leaf code, halving while a length passes 15, canonical codes), its lengths for the whole
+ *            alphabet (max_symbol unused) in zlib's run-length form (16 / 17 / 18) under a 19-symbol code of the same
+ *            construction with limit 7, whose lengths are sent in the format's order, trailing zeros trimmed down to 4.
+ * Bits are packed least significant first; Huffman codes go in most significant bit first; the last byte is padded with
+ * zeros.  cap below sp_webp_stream_bytes is refused; bytes of a slot beyond out_len[i] are not written.  ws:
+ * sp_webp_ws_bytes, 8-byte aligned. */
+int sp_webp_code(const void *residual, const void *modes, const void *flags, int n, int h, int w, int pred_bits, int group_bits,
+                 void *out, size_t cap, void *out_len, void *ws, size_t ws_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement aid (bench.py `roofline.clock_ghz_live`; the reference has no counterpart -- its benchmark reads no clocks,
  * /root/reference/src/modes/benchmark.py:170-262).  One time stamp in stream order: `blocks` one-wave workgroups each write
  * four u64 words to out[block][4]: the id of the XCD the workgroup ran on (HW_REG_XCC_ID), the shader-clock counter

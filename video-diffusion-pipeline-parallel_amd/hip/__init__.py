@@ -108,6 +108,10 @@ SIGNATURES = {
     "sp_png_stream_bytes": (_Z, [_I, _I, _I]),
     "sp_png_filter_u8": (_I, [_P, _I, _I, _I, _P, _P]),
     "sp_png_deflate": (_I, [_P, _I, _I, _I, _I, _P, _Z, _P, _P, _Z, _P]),
+    "sp_webp_ws_bytes": (_Z, [_I, _I, _I, _I, _I]),
+    "sp_webp_stream_bytes": (_Z, [_I, _I, _I, _I]),
+    "sp_webp_transform_u8": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
+    "sp_webp_code": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _Z, _P, _P, _Z, _P]),
     "sp_clock_stamp": (_I, [_P, _I, _P]),
     "sp_dummy_unet_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _I, _I, _I, _I, _I, _I, _P]),
 }

@@ -662,6 +662,59 @@ def png_deflate(filtered, out, out_len, ws, *, strip_rows):
     return out, out_len
 
 
+def webp_ws_bytes(n: int, h: int, w: int, pred_bits: int, group_bits: int) -> int:
+    return int(load().sp_webp_ws_bytes(n, h, w, pred_bits, group_bits))
+
+
+def webp_stream_bytes(h: int, w: int, pred_bits: int, group_bits: int) -> int:
+    return int(load().sp_webp_stream_bytes(h, w, pred_bits, group_bits))
+
+
+def webp_transform(frames_u8, residual, modes, flags, ws, *, pred_bits):
+    """uint8 (n, h, w, 3) RGB -> ``flags`` int32 (n,): subtract green or not; ``modes`` uint8 (n, bh, bw): the predictor of every
+    block of 2^pred_bits pixels square; ``residual`` uint8 (n, h, w, 4): the residual bytes B, G, R, 0 (``sp_webp_transform_u8``)."""
+    _dev_buf(frames_u8, torch.uint8, "webp_transform: frames")
+    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
+        raise ValueError(f"webp_transform: frames must be (n, h, w, 3); got {tuple(frames_u8.shape)}")
+    n, h, w, _ = frames_u8.shape
+    pred_bits = int(pred_bits)
+    if not 2 <= pred_bits <= 9:
+        raise ValueError(f"webp_transform: pred_bits must be 2..9; got {pred_bits}")
+    bh, bw = -(-h // (1 << pred_bits)), -(-w // (1 << pred_bits))
+    _dev_buf(residual, torch.uint8, "webp_transform: residual"), _dev_buf(modes, torch.uint8, "webp_transform: modes")
+    _dev_buf(flags, torch.int32, "webp_transform: flags"), _dev_buf(ws, torch.uint8, "webp_transform: ws")
+    if tuple(residual.shape) != (n, h, w, 4) or tuple(modes.shape) != (n, bh, bw) or flags.numel() != n:
+        raise ValueError(f"webp_transform: residual must be {(n, h, w, 4)}, modes {(n, bh, bw)} and flags ({n},); got "
+                         f"{tuple(residual.shape)}, {tuple(modes.shape)} and {tuple(flags.shape)}")
+    _check(load().sp_webp_transform_u8(frames_u8.data_ptr(), n, h, w, pred_bits, residual.data_ptr(), modes.data_ptr(),
+                                       flags.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "sp_webp_transform_u8")
+    return residual, modes, flags
+
+
+def webp_code(residual, modes, flags, out, out_len, ws, *, pred_bits, group_bits):
+    """The transform's outputs -> frame i's complete VP8L stream in ``out[i, :out_len[i]]`` (``out``: uint8 (n, cap), cap >=
+    ``webp_stream_bytes``; ``out_len``: int32 (n,); ``ws``: uint8 scratch of ``webp_ws_bytes``)."""
+    _dev_buf(residual, torch.uint8, "webp_code: residual")
+    if residual.dim() != 4 or residual.shape[3] != 4:
+        raise ValueError(f"webp_code: residual must be (n, h, w, 4); got {tuple(residual.shape)}")
+    n, h, w, _ = residual.shape
+    pred_bits, group_bits = int(pred_bits), int(group_bits)
+    if not 2 <= pred_bits <= 9 or not (group_bits == 0 or 2 <= group_bits <= 9):
+        raise ValueError(f"webp_code: pred_bits must be 2..9 and group_bits 0 or 2..9; got {pred_bits} and {group_bits}")
+    bh, bw = -(-h // (1 << pred_bits)), -(-w // (1 << pred_bits))
+    _dev_buf(modes, torch.uint8, "webp_code: modes"), _dev_buf(flags, torch.int32, "webp_code: flags")
+    _dev_buf(out, torch.uint8, "webp_code: out"), _dev_buf(ws, torch.uint8, "webp_code: ws")
+    _dev_buf(out_len, torch.int32, "webp_code: out_len")
+    if tuple(modes.shape) != (n, bh, bw) or flags.numel() != n:
+        raise ValueError(f"webp_code: modes must be {(n, bh, bw)} and flags ({n},); got {tuple(modes.shape)} and {tuple(flags.shape)}")
+    if out.dim() != 2 or out.shape[0] != n or out_len.numel() != n:
+        raise ValueError("webp_code: out must be (n, cap) and out_len (n,)")
+    _check(load().sp_webp_code(residual.data_ptr(), modes.data_ptr(), flags.data_ptr(), n, h, w, pred_bits, group_bits,
+                               out.data_ptr(), out.shape[1], out_len.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+           "sp_webp_code")
+    return out, out_len
+
+
 class ClockStamps:
     """Stamps of the shader-clock counter against the constant 100 MHz counter, taken in stream order between other work
     (``sp_clock_stamp``; bench.py ``roofline.clock_ghz_live``).  ``stamp()`` enqueues one on the current stream (a ~2 us

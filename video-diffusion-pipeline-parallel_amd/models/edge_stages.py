@@ -148,7 +148,8 @@ class FrameEmitter:
     sample finishes on this rank (its decode is long over by then) or in ``finish``.  ``output="gif"`` does the same with
     ``image_io.GifEncoder`` at ``gif_fps`` frames per second and keeps, per sample, one ``bytes`` (a complete animated GIF) for
     each of its B videos.  ``output="png"`` mirrors ``"jpeg"`` with ``image_io.PngEncoder``: per sample one ``list[bytes]`` of F PNG
-    files (lossless) for each of its B videos.
+    files (lossless) for each of its B videos.  ``output="webp"`` mirrors ``"gif"`` with ``image_io.WebpEncoder``: per sample one
+    ``bytes`` (a complete animated lossless WebP at ``gif_fps`` frames per second) for each of its B videos.
     """
 
     def __init__(self, decoder: TemporalDecoderHIP, stage, num_frames: int, *, decode_chunk_size: int = 14,
@@ -158,17 +159,17 @@ class FrameEmitter:
 
         if keep not in ("all", "last", "none"):
             raise ValueError("keep must be 'all', 'last' or 'none'")
-        if output not in ("float32", "uint8", "jpeg", "gif", "png"):
-            raise ValueError("output must be 'float32', 'uint8', 'jpeg', 'gif' or 'png'")
+        if output not in ("float32", "uint8", "jpeg", "gif", "png", "webp"):
+            raise ValueError("output must be 'float32', 'uint8', 'jpeg', 'gif', 'png' or 'webp'")
         if check_finite and output != "float32":
             raise ValueError("check_finite needs output='float32' (an 8-bit level cannot show a non-finite value)")
         if output == "jpeg" and not (isinstance(jpeg_quality, int) and 1 <= jpeg_quality <= 100):
             raise ValueError(f"jpeg_quality must be an integer from 1 to 100; got {jpeg_quality!r}")
-        if output == "gif" and (isinstance(gif_fps, bool) or not isinstance(gif_fps, (int, float)) or not gif_fps > 0):
+        if output in ("gif", "webp") and (isinstance(gif_fps, bool) or not isinstance(gif_fps, (int, float)) or not gif_fps > 0):
             raise ValueError(f"gif_fps must be a positive number; got {gif_fps!r}")
         self.output, self.jpeg_quality, self.gif_fps = output, jpeg_quality, gif_fps
         self._jpeg = None               # the JpegEncoder (or, for output="png", the PngEncoder), made for the first sample's frame size
-        self._gif = None                # the GifEncoders, one per video of a sample (a video's buffers wait for the fetch)
+        self._gif = None                # the GifEncoders (or, for output="webp", the WebpEncoders), one per video of a sample (a video's buffers wait for the fetch)
         self._pending = None            # (sample index, videos, streams, lengths, event) of the encode still on the device
         self.decoder, self.stage, self.num_frames = decoder, stage, num_frames
         self.chunk, self.keep, self.check_finite = decode_chunk_size, keep, check_finite
@@ -202,7 +203,7 @@ class FrameEmitter:
         latent.record_stream(self.stream)
         with torch.cuda.stream(self.stream):
             self.stream.wait_event(ready)
-            if self.output in ("jpeg", "gif", "png"):
+            if self.output in ("jpeg", "gif", "png", "webp"):
                 self._collect_jpeg()           # before this decode is queued: the encoder's buffers are free again after it
             decode = self.decoder.decode_latents if self.output == "float32" else self.decoder.decode_latents_uint8
             out = decode(latent.contiguous(), self.num_frames, decode_chunk_size=self.chunk)
@@ -215,16 +216,17 @@ class FrameEmitter:
                 done = torch.cuda.Event()
                 done.record(self.stream)
                 self._pending = (idx, out.shape[0], streams, lens, done)
-            elif self.output == "gif":
+            elif self.output in ("gif", "webp"):
                 if self._gif is None or len(self._gif) != out.shape[0] or (self._gif[0].height, self._gif[0].width) != tuple(out.shape[2:4]):
-                    from .image_io import GifEncoder
-                    self._gif = [GifEncoder(self.device, out.shape[2], out.shape[3], fps=self.gif_fps) for _ in range(out.shape[0])]
+                    from .image_io import GifEncoder, WebpEncoder
+                    self._gif = [GifEncoder(self.device, out.shape[2], out.shape[3], fps=self.gif_fps) if self.output == "gif"
+                                 else WebpEncoder(self.device, out.shape[2], out.shape[3]) for _ in range(out.shape[0])]
                 bufs = [enc.enqueue(video) for enc, video in zip(self._gif, out)]
                 done = torch.cuda.Event()
                 done.record(self.stream)
                 self._pending = (idx, out.shape[0], bufs, None, done)
         self.stats["decoded"] += 1
-        if self.output in ("jpeg", "gif", "png"):
+        if self.output in ("jpeg", "gif", "png", "webp"):
             return
         self._keep(idx, out)
 
@@ -244,6 +246,11 @@ class FrameEmitter:
             with torch.cuda.stream(self.stream):                      # (the copies queue behind nothing: the stream is idle)
                 if self.output == "gif":
                     self._keep(idx, [enc.collect(*bufs) for enc, bufs in zip(self._gif, streams)])
+                    return
+                if self.output == "webp":
+                    from .image_io import write_webp
+                    self._keep(idx, [write_webp(None, enc.collect_streams(*bufs), enc.width, enc.height, self.gif_fps)
+                                     for enc, bufs in zip(self._gif, streams)])
                     return
                 files = self._jpeg.collect(streams, lens)
             per = len(files) // videos

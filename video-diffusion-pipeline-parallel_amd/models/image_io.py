@@ -15,6 +15,9 @@
   * ``PngEncoder`` / ``png_file`` / ``write_apng``: the lossless frames (a directory or a ``%03d.png`` pattern) and an
     animated PNG: frames on the device are filtered and deflated there by the kernels of ``csrc/png.hip``; signature, chunks
     and their CRC-32 (over compressed bytes the host has anyway) are written here.
+  * ``WebpEncoder`` / ``webp_file`` / ``write_webp``: lossless WebP stills and one animated WebP, full colour and playable
+    in a browser: frames on the device become VP8L bitstreams there by the kernels of ``csrc/webp.hip``; the RIFF container
+    has no checksum, so the host only wraps bytes.
   * ``load_image``: the decode half of ``load_and_preprocess_image`` (Pillow; a file format is host work).
 """
 
@@ -469,6 +472,136 @@ class PngEncoder:
         return write_apng(None, self.collect_streams(out, lens), self.width, self.height, fps)
 
 
+def _riff_chunk(kind: bytes, payload: bytes) -> list[bytes]:
+    """The pieces of a RIFF chunk (an odd payload is padded to even); the caller joins all pieces of a file once, so that a
+    frame's bytes are copied once."""
+    return [kind, struct.pack("<I", len(payload)), payload] + ([b"\0"] if len(payload) & 1 else [])
+
+
+def _riff_file(pieces: list[bytes]) -> bytes:
+    return b"".join([b"RIFF", struct.pack("<I", 4 + sum(len(p) for p in pieces)), b"WEBP"] + pieces)
+
+
+def _u24(value: int) -> bytes:
+    return struct.pack("<I", value)[:3]
+
+
+def webp_file(stream: bytes) -> bytes:
+    """A still lossless WebP around a VP8L bitstream (what ``sp_webp_code`` writes): RIFF, WEBP, one VP8L chunk (an odd
+    payload is padded to even).  The container has no checksum."""
+    return _riff_file(_riff_chunk(b"VP8L", bytes(stream)))
+
+
+def write_webp(path, streams, width: int, height: int, fps=7) -> bytes:
+    """An animated lossless WebP that loops for ever, returned as ``bytes`` and written to ``path`` unless that is ``None``:
+    VP8X (the animation flag only; the canvas is the frame), ANIM (background 0, loop count 0), and per frame an ANMF (offsets
+    0, the whole frame, ``round(1000 / fps)`` ms in the 24-bit duration field, no blending, no disposal) around the frame's
+    VP8L chunk."""
+    if len(streams) == 0:
+        raise ValueError("write_webp: no frames")
+    ms = round(1000 / _check_fps(fps))
+    if not 0 <= ms < 1 << 24:
+        raise ValueError(f"write_webp: a duration of 1 / {fps} s does not fit the frame's 24-bit field of milliseconds")
+    if not (1 <= width <= 16384 and 1 <= height <= 16384):
+        raise ValueError(f"a lossless WebP frame is 1..16384 pixels on a side; got {height}x{width}")
+    size = _u24(width - 1) + _u24(height - 1)
+    out = _riff_chunk(b"VP8X", bytes([0x02, 0, 0, 0]) + size) + _riff_chunk(b"ANIM", struct.pack("<IH", 0, 0))
+    frame_head = _u24(0) + _u24(0) + size + _u24(ms) + bytes([0x02])
+    for stream in streams:
+        inner = _riff_chunk(b"VP8L", bytes(stream))                 # (even in all, so the ANMF around it needs no padding)
+        out += [b"ANMF", struct.pack("<I", len(frame_head) + sum(len(p) for p in inner)), frame_head] + inner
+    blob = _riff_file(out)
+    if path is not None:
+        with open(path, "wb") as fh:
+            fh.write(blob)
+    return blob
+
+
+# blocks of 8 x 8 pixels and strips of 16 rows: the fastest whole call of the grid 4 / 8 / 16 / 32 x 8 / 16 / 32, or within the
+# spread of the rounds of it, its files within 0.6 % of the grid's smallest (profiles/webp_timing.txt)
+WEBP_PRED_BITS = 3
+WEBP_GROUP_BITS = 4
+
+
+def _check_webp_bits(pred_bits, group_bits) -> tuple[int, int]:
+    if isinstance(pred_bits, bool) or not isinstance(pred_bits, (int, np.integer)) or not 2 <= pred_bits <= 9:
+        raise ValueError(f"pred_bits must be an integer in 2..9; got {pred_bits!r}")
+    if isinstance(group_bits, bool) or not isinstance(group_bits, (int, np.integer)) or not (group_bits == 0 or 2 <= group_bits <= 9):
+        raise ValueError(f"group_bits must be 0 or an integer in 2..9; got {group_bits!r}")
+    return int(pred_bits), int(group_bits)
+
+
+class WebpEncoder:
+    """(F, H, W, 3) uint8 frames on the device -> one lossless WebP per frame or one animated WebP, transformed and entropy-coded
+    on the device (``csrc/webp.hip``).
+
+    Green is taken out of red and blue when an integer rule says it pays; every block of ``2^pred_bits`` pixels square takes
+    the predictor with the least sum of min(b, 256 - b); a frame is coded in strips of ``2^group_bits`` rows, each with five
+    prefix codes of its own (``group_bits = 0``: one set for the frame), of literals and of copies at distance 1, so that a
+    frame is many independent sequences.  The defaults are blocks of 8 and strips of 16 rows: of the grid 4 / 8 / 16 / 32 x
+    8 / 16 / 32 measured on one video of 14 x 576 x 1024 (profiles/webp_timing.txt) the row "pred_bits 3, group_bits 4" is the
+    fastest whole call with channels that follow green (3.01 ms) and 0.1 ms, less than the spread of its rounds, behind
+    "pred_bits 4, group_bits 4" with independent channels (3.62 against 3.52 ms); its file is within 0.2 % (independent
+    channels) and 0.6 % (channels that follow green) of the smallest of the grid; strips of 16 rows have the fastest coder at
+    every block size, strips of 8 and of 32 rows are 0.1 to 0.2 ms slower.  Residual, mode, flag, stream, length and scratch buffers are kept per frame count; the
+    stream buffer holds ``sp_webp_stream_bytes`` per frame (the size no input can exceed), of which only the used bytes are
+    ever copied to the host."""
+
+    def __init__(self, device, height: int, width: int, pred_bits: int = WEBP_PRED_BITS, group_bits: int = WEBP_GROUP_BITS) -> None:
+        self.device = common.hip_device(device, "WebpEncoder")
+        self.height, self.width = int(height), int(width)
+        self.pred_bits, self.group_bits = _check_webp_bits(pred_bits, group_bits)
+        self.cap = ops.webp_stream_bytes(self.height, self.width, self.pred_bits, self.group_bits)
+        if self.cap == 0:
+            raise ValueError(f"a frame for the WebP kernels is 1..16384 pixels on a side and at most 2^24 in all; got {height}x{width}")
+        self._scratch: dict = {}
+
+    def _buf(self, name: str, shape, dtype) -> torch.Tensor:
+        key = (name, shape)
+        if key not in self._scratch:
+            self._scratch[key] = torch.empty(shape, dtype=dtype, device=self.device)
+        return self._scratch[key]
+
+    def enqueue(self, frames_u8: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+        """Run the two stages on the current stream and return ``(streams (F, cap) uint8, lengths (F,) int32)``: views of
+        this encoder's buffers, valid until the next call with as many frames."""
+        if (not isinstance(frames_u8, torch.Tensor) or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4
+                or tuple(frames_u8.shape[1:]) != (self.height, self.width, 3) or frames_u8.shape[0] == 0):
+            raise ValueError(f"frames must be a (F, {self.height}, {self.width}, 3) uint8 tensor; got "
+                             f"{getattr(frames_u8, 'dtype', type(frames_u8))} {tuple(getattr(frames_u8, 'shape', ()))}")
+        n, block = frames_u8.shape[0], 1 << self.pred_bits
+        residual = self._buf("residual", (n, self.height, self.width, 4), torch.uint8)
+        modes = self._buf("modes", (n, -(-self.height // block), -(-self.width // block)), torch.uint8)
+        flags = self._buf("flags", (n,), torch.int32)
+        out = self._buf("stream", (n, self.cap), torch.uint8)
+        lens = self._buf("len", (n,), torch.int32)
+        ws = self._buf("ws", (ops.webp_ws_bytes(n, self.height, self.width, self.pred_bits, self.group_bits),), torch.uint8)
+        ops.webp_transform(frames_u8.to(self.device).contiguous(), residual, modes, flags, ws, pred_bits=self.pred_bits)
+        ops.webp_code(residual, modes, flags, out, lens, ws, pred_bits=self.pred_bits, group_bits=self.group_bits)
+        return out, lens
+
+    def collect_streams(self, out: torch.Tensor, lens: torch.Tensor) -> list[bytes]:
+        """The VP8L streams of an ``enqueue`` whose work has finished: the lengths come to the host first, then only the used
+        bytes."""
+        return [out[i, :n].cpu().numpy().tobytes() for i, n in enumerate(lens.cpu().tolist())]
+
+    def collect(self, out: torch.Tensor, lens: torch.Tensor) -> list[bytes]:
+        """The still ``.webp`` files of an ``enqueue`` whose work has finished."""
+        return [webp_file(s) for s in self.collect_streams(out, lens)]
+
+    def encode(self, frames_u8: torch.Tensor) -> list[bytes]:
+        out, lens = self.enqueue(frames_u8)
+        torch.cuda.current_stream(self.device).synchronize()
+        return self.collect(out, lens)
+
+    def encode_animation(self, frames_u8: torch.Tensor, fps=7) -> bytes:
+        """One animated WebP of the frames (``write_webp`` around the same streams)."""
+        _check_fps(fps)
+        out, lens = self.enqueue(frames_u8)
+        torch.cuda.current_stream(self.device).synchronize()
+        return write_webp(None, self.collect_streams(out, lens), self.width, self.height, fps)
+
+
 def _jpeg_frames(frames_u8, quality: int) -> tuple[list[bytes], int, int]:
     """``(files, height, width)``: a tensor on a GPU is compressed there (``JpegEncoder``), anything else by Pillow."""
     if isinstance(frames_u8, torch.Tensor) and frames_u8.is_cuda:
@@ -497,7 +630,10 @@ def save_frames(frames_u8, path: str, fps: int = 7, quality: int = 90) -> list[s
     LZW-coded there (``GifEncoder``: a palette per frame, strips of 8 rows, delays in whole centiseconds), while an array in
     host memory goes through Pillow as before, byte for byte.  PNG frames (a directory or a ``%03d.png`` pattern) and
     ``*.apng`` (one animated PNG, lossless, ``1 / fps`` s per frame) of a tensor on a GPU are filtered and deflated there
-    (``PngEncoder``); an array in host memory goes through Pillow.  ``*.mp4`` is refused: imageio / ffmpeg are not dependencies."""
+    (``PngEncoder``); an array in host memory goes through Pillow.  ``*.webp`` is lossless WebP: one animated file
+    (``round(1000 / fps)`` ms per frame, looping for ever), or with a ``%03d``-style pattern one still per frame; a tensor on
+    a GPU is transformed and entropy-coded there (``WebpEncoder``), an array in host memory, or frames the kernels refuse, go
+    through Pillow (``lossless=True``).  ``*.mp4`` is refused: imageio / ffmpeg are not dependencies."""
     path = os.fspath(path)
     ext = os.path.splitext(path)[1].lower()
     # frames on a GPU stay there for the targets that are compressed there; everything else is host work on an array
@@ -510,11 +646,15 @@ def save_frames(frames_u8, path: str, fps: int = 7, quality: int = 90) -> list[s
         # frames the PNG kernels do not take (or that are no frames at all) keep the host route and its messages
         on_gpu = (frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4 and frames_u8.shape[3] == 3 and frames_u8.shape[0] > 0
                   and ops.png_stream_bytes(frames_u8.shape[1], frames_u8.shape[2], PNG_STRIP_ROWS) > 0)
+    if isinstance(frames_u8, torch.Tensor) and frames_u8.is_cuda and ext == ".webp":
+        # likewise for the WebP kernels
+        on_gpu = (frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4 and frames_u8.shape[3] == 3 and frames_u8.shape[0] > 0
+                  and ops.webp_stream_bytes(frames_u8.shape[1], frames_u8.shape[2], WEBP_PRED_BITS, WEBP_GROUP_BITS) > 0)
     a = None if on_gpu else _frames_array(frames_u8)
     if ext in (".mp4", ".mov", ".mkv", ".webm"):
         raise ValueError(f"cannot write '{path}': video encoding needs imageio / ffmpeg, which this package does not depend "
-                         f"on; write .avi (Motion-JPEG) instead, or .gif, .npy, JPEG or PNG frames (a %03d.jpg / %03d.png "
-                         f"pattern or a directory)")
+                         f"on; write .avi (Motion-JPEG) instead, or .gif, .webp (lossless, animated), .npy, JPEG or PNG frames (a "
+                         f"%03d.jpg / %03d.png pattern or a directory)")
     if ext in (".avi", ".jpg", ".jpeg"):
         _check_quality(quality)
         if ext == ".avi" and (not isinstance(fps, (int, np.integer)) or fps <= 0):
@@ -556,8 +696,30 @@ def save_frames(frames_u8, path: str, fps: int = 7, quality: int = 90) -> list[s
             with open(name, "wb") as fh:
                 fh.write(data)
         return files
+    if ext == ".webp" and on_gpu:
+        enc = WebpEncoder(frames_u8.device, frames_u8.shape[1], frames_u8.shape[2])
+        if "%" not in path:
+            data = enc.encode_animation(frames_u8, fps)
+            with open(path, "wb") as fh:
+                fh.write(data)
+            return [path]
+        files = [path % i for i in range(frames_u8.shape[0])]
+        for name, data in zip(files, enc.encode(frames_u8)):
+            with open(name, "wb") as fh:
+                fh.write(data)
+        return files
     from PIL import Image
 
+    if ext == ".webp":
+        if "%" not in path:
+            ms = round(1000 / _check_fps(fps))
+            ims = [Image.fromarray(f) for f in a]
+            ims[0].save(path, format="WEBP", save_all=True, append_images=ims[1:], lossless=True, loop=0, duration=ms)
+            return [path]
+        files = [path % i for i in range(len(a))]
+        for name, f in zip(files, a):
+            Image.fromarray(f).save(name, format="WEBP", lossless=True)
+        return files
     if ext == ".apng":
         _check_fps(fps)
         ims = [Image.fromarray(f) for f in a]
@@ -577,8 +739,8 @@ def save_frames(frames_u8, path: str, fps: int = 7, quality: int = 90) -> list[s
         os.makedirs(path, exist_ok=True)
         pattern = os.path.join(path, "%03d.png")
     else:
-        raise ValueError(f"'{path}': unknown output format {ext!r} (.avi, .gif, .apng, .npy, %03d.jpg / %03d.png pattern or a "
-                         f"directory)")
+        raise ValueError(f"'{path}': unknown output format {ext!r} (.avi, .gif, .apng, .webp, .npy, %03d.jpg / %03d.png / "
+                         f"%03d.webp pattern or a directory)")
     files = []
     for i, f in enumerate(a):
         files.append(pattern % i)

@@ -15,7 +15,9 @@ with the finished latents decodes them to 8-bit frames (``decode_latents_uint8``
 ``--jpeg-quality`` and only the compressed bytes come to the host -- ``.gif``, the animated GIF of the demo: quantised to a
 palette per frame and LZW-coded on the GPU as well (``image_io.GifEncoder``), at ``--fps`` -- ``.npy``, a ``%03d.png`` pattern
 or a directory of PNGs, and ``.apng``, one lossless animated PNG at ``--fps``: PNG rows are filtered and deflated on the GPU
-too (``image_io.PngEncoder``)).
+too (``image_io.PngEncoder``) -- and ``.webp``, lossless WebP in full colour that a browser plays: one animated file at
+``--fps``, or with a ``%03d.webp`` pattern one still per frame, transformed and entropy-coded on the GPU
+(``image_io.WebpEncoder``)).  The frames go to ``save_frames`` as the device tensor they are.
 """
 
 from __future__ import annotations
@@ -36,7 +38,7 @@ LOGGER = logging.getLogger(__name__)
 def parse_args(argv=None) -> argparse.Namespace:
     p = argparse.ArgumentParser(description="Generate video frames from an image (SVD step pipeline)")
     p.add_argument("--input-image", type=str, required=True, help="picture file (anything Pillow decodes)")
-    p.add_argument("--output", type=str, required=True, help=".avi (Motion-JPEG video), .gif, .apng (lossless animated PNG), .npy, a %%03d.jpg or %%03d.png pattern, or a directory for PNG frames")
+    p.add_argument("--output", type=str, required=True, help=".avi (Motion-JPEG video), .gif, .apng (lossless animated PNG), .webp (lossless animated WebP), .npy, a %%03d.jpg, %%03d.png or %%03d.webp pattern, or a directory for PNG frames")
     p.add_argument("--height", type=int, default=576)
     p.add_argument("--width", type=int, default=1024)
     p.add_argument("--num-frames", type=int, default=14)
