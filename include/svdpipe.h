@@ -521,9 +521,10 @@ int sp_gif_lzw(const void *indices, int n, int h, int w, int strip_rows, void *o
 
 /* ---------------------------------------------------------------------------------------------
  * PNG / APNG frames of uint8 frames that are in device memory (the lossless output: the reference writes frames through
- * imageio / Pillow on the host).  Two stages: the filtered rows of every frame, then the complete zlib stream of a frame's
- * filtered bytes.  Signature, chunks and their CRC-32 are host work: a CRC covers compressed bytes that the host has anyway
- * (zlib.crc32); the Adler-32 inside the stream covers the filtered bytes, which never leave the device, and is made there.
+ * imageio / Pillow on the host).  Three stages: the filtered rows of every frame, the complete zlib stream of a frame's
+ * filtered bytes, and the files around the streams (sp_png_wrap: signature, chunks and their CRC-32, see sp_crc32_rows; a
+ * caller may stop after the second stage and put the chunks together on the host).  The Adler-32 inside the stream covers the
+ * filtered bytes, which never leave the device, and is made there.
  * h and w are 1..65535 with h*w <= 2^24; strip_rows >= 1 (a value above h means h).  The size functions need no GPU and give
  * 0 for arguments the kernels refuse.
  * ------------------------------------------------------------------------------------------- */
@@ -564,6 +565,45 @@ int sp_png_filter_u8(const void *frames, int n, int h, int w, void *filtered, vo
  * sp_png_stream_bytes is refused; bytes of a slot beyond out_len[i] are not written.  ws: sp_png_ws_bytes, 8-byte aligned. */
 int sp_png_deflate(const void *filtered, int n, int h, int w, int strip_rows, void *out, size_t cap, void *out_len, void *ws,
                    size_t ws_bytes, void *stream);
+/* Bytes no still file can exceed: sp_png_stream_bytes + 57 (signature 8, IHDR 25, IDAT 12 around its payload, IEND 12). */
+size_t sp_png_file_bytes(int h, int w, int strip_rows);
+/* Bytes no animation of n frames can exceed, S = sp_png_stream_bytes: signature 8, IHDR 25, acTL 20, IEND 12, per frame an
+ * fcTL of 38 and a data chunk of 12 + S, and 4 more in each of the n - 1 fdAT:
+ *   result = 65 + n * (50 + S) + 4 * (n - 1);  0 for n <= 0. */
+size_t sp_apng_file_bytes(int n, int h, int w, int strip_rows);
+/* Scratch of sp_png_wrap for n streams in slots of cap bytes: 16 bytes per frame (the stream's place, the seed and the CRC of
+ * its chunk) rounded up to 256, and sp_crc32_ws_bytes(n, cap). */
+size_t sp_png_wrap_ws_bytes(int n, size_t cap);
+/* streams: n zlib streams as sp_png_deflate leaves them (stream i at streams + i*cap, lens[i] bytes of it, int32 on the
+ * device; a length outside 0..cap counts as the nearer end) -> complete files, made on the device from the first byte to the
+ * last.  8-bit RGB without interlace, h x w.
+ *   animate == 0   slot i of files (at files + i*file_cap) is one still: signature, IHDR, one IDAT (length, type, stream i,
+ *                  CRC-32 over type and stream), IEND; file_len[i] = lens[i] + 57.  file_cap >= cap + 57.
+ *   animate != 0   files is ONE animated PNG that loops for ever: signature, IHDR, acTL (n frames, num_plays 0); per frame an
+ *                  fcTL (sequence number, the whole frame at offset 0, delay delay_num / delay_den seconds, dispose 0, blend
+ *                  0) and its stream, in IDAT for frame 0 and in fdAT behind a sequence number for the others; IEND.
+ *                  Sequence numbers count the fcTL and fdAT chunks in file order from 0 (frame i > 0: fcTL 2i - 1, fdAT 2i).
+ *                  file_len[0] is the file's length; the frames' places are an exclusive sum of the lengths made on the
+ *                  device.  file_cap >= 65 + n * (50 + cap) + 4 * (n - 1) <= 2^31 - 1.  delay_num is 1..65535, delay_den
+ *                  0..65535 (which the format reads as 100).
+ * Either way the bytes equal those the host puts together from the same streams (image_io.png_file / write_apng); bytes of a
+ * file (slot) beyond file_len are not written.  file_len: int32 [n] on the device (animate: only [0] is written).  ws:
+ * sp_png_wrap_ws_bytes, 8-byte aligned.  Nothing about the lengths reaches the host. */
+int sp_png_wrap(const void *streams, size_t cap, const void *lens, int n, int h, int w, int animate, int delay_num, int delay_den,
+                void *files, size_t file_cap, void *file_len, void *ws, size_t ws_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * CRC-32 of rows of bytes in device memory: the checksum of PNG chunks, gzip and zip (reflected polynomial 0xEDB88320; seed
+ * and result in zlib's convention: crc[i] == zlib.crc32(row_i[:lens[i]], seed[i])).  Row i is data + i*pitch, of which the
+ * first lens[i] bytes count; pitch is 1..2^31-1 and need not be a multiple of 4.  lens (int32 [n]) is read on the device: a
+ * negative length counts as 0 and one above pitch as pitch, so that nothing outside a row is read; a length of 0 gives
+ * seed[i].  seed: uint32 [n] on the device, or NULL for 0.  crc: uint32 [n].  The work is parallel within a row (pieces of 64
+ * bytes, each piece's register multiplied by x^(8 * bytes behind it) mod P, all XORed), so one long row is as good as many.
+ * ------------------------------------------------------------------------------------------- */
+/* Scratch: one uint32 per (row, span of 16384 bytes of pitch); 0 for arguments the kernel refuses. */
+size_t sp_crc32_ws_bytes(int n, size_t pitch);
+int sp_crc32_rows(const void *data, size_t pitch, const void *lens, const void *seed, int n, void *crc, void *ws,
+                  size_t ws_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Lossless WebP of uint8 frames that are in device memory (the full-colour animated output: still .webp files and one

@@ -6,7 +6,13 @@
     PngEncoder.encode as a whole (host clock around a call that ends synchronised);
   * the route without the kernels: the device-to-host copy of the uint8 frames, then Pillow's PNG writer per frame on the host
     (what save_frames did with a device tensor before; one thread);
-  * the bytes of the files of both, and of one strip per frame (strip_rows = 576) for the cost of the strips.
+  * the bytes of the files of both, and of one strip per frame (strip_rows = 576) for the cost of the strips;
+  * at the default strip height, the two ways to the files in the same run: assemble="host" (the streams to the host,
+    png_file / write_apng and zlib.crc32 there) and assemble="device" (sp_png_wrap: chunks, CRC-32 and an animation's layout on
+    the device, finished files to the host), PngEncoder.encode and encode_apng under each, and device events around
+    sp_crc32_rows over the streams and around sp_png_wrap (stills, animation) alone.  Both routes must give the same bytes.
+
+The strip heights are compared on the host route, whose parts the lines name.
 
 The default strip height is the fastest of the four whose files are within 1 % of one strip per frame.
 Input: a smooth two-sinusoid colour field that moves from frame to frame plus sigma = 8 noise (the field of the tests).
@@ -84,8 +90,10 @@ def line(name, t):
 def main():
     host_frames = scene()
     frames = torch.from_numpy(host_frames).to(dev)
-    encs = {r: PngEncoder(dev, H, W, strip_rows=r) for r in STRIP_ROWS}
+    encs = {r: PngEncoder(dev, H, W, strip_rows=r, assemble="host") for r in STRIP_ROWS}
+    routes = {a: PngEncoder(dev, H, W, assemble=a) for a in ("host", "device")}
     keys = [f"{k}{r}" for r in STRIP_ROWS for k in ("filter", "deflate", "collect", "crc", "encode")] + ["raw_copy", "pillow"]
+    keys += [f"{k}_{a}" for a in routes for k in ("encode", "apng")] + ["crc_rows", "wrap_stills", "wrap_apng"]
     t = {k: [] for k in keys}
     sizes = {}
     for it in range(NWARM + NREP):
@@ -103,6 +111,22 @@ def main():
             r_[f"encode{r}"], again = host_ms(lambda: enc.encode(frames))
             assert ours == again
             sizes[r] = sum(len(f) for f in ours)
+        made = {}
+        for a, enc in routes.items():
+            r_[f"encode_{a}"], stills = host_ms(lambda: enc.encode(frames))
+            r_[f"apng_{a}"], movie = host_ms(lambda: enc.encode_apng(frames, 7))
+            made[a] = (stills, movie)
+        assert made["host"] == made["device"], "the two routes give different bytes"
+        enc, n = routes["device"], frames.shape[0]
+        out, lens = enc.enqueue(frames)
+        crc = enc._buf("crc", (n,), torch.int32)
+        crc_ws = enc._buf("crc_ws", (ops.crc32_ws_bytes(n, enc.cap),), torch.uint8)
+        files, file_lens = enc._buf("files", (n, ops.png_file_bytes(H, W, enc.strip_rows)), torch.uint8), enc._buf("file_len", (n,), torch.int32)
+        movie_buf = enc._buf("apng", (ops.apng_file_bytes(n, H, W, enc.strip_rows),), torch.uint8)
+        wrap_ws = enc._buf("wrap_ws", (ops.png_wrap_ws_bytes(n, enc.cap),), torch.uint8)
+        r_["crc_rows"], _ = device_ms(lambda: ops.crc32_rows(out, lens, crc, crc_ws))
+        r_["wrap_stills"], _ = device_ms(lambda: ops.png_wrap(out, lens, files, file_lens, wrap_ws, height=H, width=W))
+        r_["wrap_apng"], _ = device_ms(lambda: ops.png_wrap(out, lens, movie_buf, file_lens, wrap_ws, height=H, width=W, animate=True))
         r_["raw_copy"], raw = host_ms(lambda: frames.cpu().numpy())
         r_["pillow"], theirs = host_ms(lambda: pillow(raw))
         sizes["pillow"] = sum(len(f) for f in theirs)
@@ -117,7 +141,7 @@ def main():
     print(f"device: {torch.cuda.get_device_name(0)}; {F} frames of {H}x{W}; {NWARM} warm-up rounds, then {NREP} timed rounds per line")
     host = med(t["raw_copy"]) + med(t["pillow"])
     for r in STRIP_ROWS:
-        print(f"GPU route, strip_rows {r} ({F * -(-H // r)} strips):")
+        print(f"GPU route, files put together on the host, strip_rows {r} ({F * -(-H // r)} strips):")
         print(line("sp_png_filter_u8, one kernel (device events)", t[f"filter{r}"]))
         print(line("sp_png_deflate, three kernels (device events)", t[f"deflate{r}"]))
         print(line("lengths, then the used bytes to the host, chunks and CRC-32, files put together (host clock)", t[f"collect{r}"]))
@@ -131,6 +155,15 @@ def main():
     print(line(f"the uint8 frames to the host, {frames.numel() / 1e6:.1f} MB (host clock)", t["raw_copy"]))
     print(line("Pillow's PNG writer on the frames, default settings, 1 thread (host clock)", t["pillow"]))
     print(f"  files {sizes['pillow']} bytes")
+    print(f"files put together on the host and on the device, strip_rows {routes['device'].strip_rows}, the same bytes:")
+    for a in routes:
+        print(line(f'PngEncoder(assemble="{a}").encode, {F} stills (host clock)', t[f"encode_{a}"]))
+        print(line(f'PngEncoder(assemble="{a}").encode_apng, one animation (host clock)', t[f"apng_{a}"]))
+    print(line(f"sp_crc32_rows over the {F} streams, two kernels (device events)", t["crc_rows"]))
+    print(line("sp_png_wrap, stills: chunks, CRC-32, the streams into the files, four kernels (device events)", t["wrap_stills"]))
+    print(line("sp_png_wrap, one animation, four kernels (device events)", t["wrap_apng"]))
+    print(f"  host route over device route, medians: encode {med(t['encode_host']) / med(t['encode_device']):.2f} x, "
+          f"encode_apng {med(t['apng_host']) / med(t['apng_device']):.2f} x")
     within = [r for r in STRIP_ROWS if sizes[r] <= 1.01 * sizes["one"]]
     best = min(within, key=lambda r: med(t[f"encode{r}"])) if within else None
     print(f"strip heights within 1 % of one strip per frame: {within}; the fastest of them: {best}")

@@ -103,7 +103,7 @@ def measure(name, host_frames):
     frames = torch.from_numpy(host_frames).to(dev)
     grid = [(p, g) for p in PRED_BITS for g in GROUP_BITS]
     encs = {pg: WebpEncoder(dev, H, W, pred_bits=pg[0], group_bits=pg[1]) for pg in grid}
-    png = PngEncoder(dev, H, W)
+    png = PngEncoder(dev, H, W, assemble="host")              # the route the lines name (the device route: profiles/png_timing.txt)
     keys = [f"{k}{pg}" for pg in grid for k in ("transform", "code", "collect", "wrap", "encode")] + ["apng", "raw_copy", "pillow"]
     t = {k: [] for k in keys}
     sizes, ours = {}, {}

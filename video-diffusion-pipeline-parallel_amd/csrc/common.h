@@ -101,6 +101,27 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// Bytes off .. off + 3 of row[0 .. len), little-endian, zeros for those at or behind len (off >= 0).  Rows of bytes start
+// anywhere: where the two aligned dwords around the four bytes lie inside the row they are loaded whole and put together
+// (v_alignbyte_b32), at the row's two ends the bytes are loaded one by one, so nothing outside the row is read.
+__device__ __forceinline__ unsigned load_bytes4(const unsigned char *row, int64_t off, int64_t len) {
+  const unsigned char *p = row + off;
+  const unsigned mis = (unsigned)((uintptr_t)p & 3);
+  if (off >= (int64_t)mis && off - mis + (mis ? 8 : 4) <= len) {
+    const unsigned *q = (const unsigned *)(p - mis);
+    const unsigned lo = q[0];
+    return mis ? __builtin_amdgcn_alignbyte(q[1], lo, mis) : lo;
+  }
+  unsigned v = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (off + k < len) v |= (unsigned)p[k] << (8 * k);
+  return v;
+}
+
+// crc32.hip: the two launches of the segmented CRC-32 (arguments as sp_crc32_rows, already checked)
+void sp_crc32_launch(const void *data, size_t pitch, const void *lens, const void *seed, int n, void *crc, void *ws, hipStream_t s);
+
 // global -> LDS direct load, 16 bytes per lane (global_load_lds_dwordx4).
 // LDS destination = wave-uniform base + lane*16; the global source address is per lane.
 __device__ __forceinline__ void glds16(const void *gsrc, void *lds_dst) {

@@ -1,7 +1,7 @@
 // PNG / APNG frames of uint8 frames that are already in device memory: the lossless output of save_frames.  The library makes,
-// per frame, the filtered rows and the complete zlib stream of them; chunks, their CRC-32 (over compressed bytes the host has
-// anyway) and the files are host work (models/image_io.py png_file / write_apng).  include/svdpipe.h fixes the rules,
-// tests/png_model.py restates them.
+// per frame, the filtered rows and the complete zlib stream of them, and then the files around the streams: one still per
+// frame or one animation, byte for byte what models/image_io.py png_file / write_apng build on the host (which remain the
+// statement the device files are held to).  include/svdpipe.h fixes the rules, tests/png_model.py restates them.
 //
 //   png_filter_kernel  : a workgroup per row: the five sums of min(b, 256 - b), the choice, then the chosen row (bytes: the
 //                        pitch 1 + 3w is rarely aligned).
@@ -20,6 +20,13 @@
 //   png_scan_kernel    : per frame the exclusive sum of the strips' bit counts, the byte count, 78 9C in front, the Adler-32
 //                        folded from the strips' partials behind, out_len.
 //   png_place_kernel   : one workgroup per strip writes the bytes whose first bit lies in the strip (gif_place_kernel's rule).
+//   png_head_kernel    : one workgroup, a thread per frame: the exclusive sum of the chunk sizes (an animation's frames follow
+//                        one another), and every byte of the files that is no stream and no stream's CRC: signature, IHDR,
+//                        acTL, fcTL, the length and type of IDAT / fdAT and an fdAT's sequence number, IEND, each small chunk's
+//                        CRC bit by bit; the CRC-32 of a data chunk's type (and sequence number) as the seed of its stream's.
+//   (crc32.hip)        : the CRC-32 of every stream from that seed, parallel within a stream.
+//   png_copy_kernel    : a workgroup per 16 KiB of a stream: the stream to its place in whole words of the destination, the
+//                        CRC behind it.
 // Nothing here is tuned beyond its layout; profiles/png_timing.txt has what it costs.
 #include "common.h"
 
@@ -574,6 +581,141 @@ __global__ __launch_bounds__(256) void png_place_kernel(const u8 *__restrict__ s
   }
 }
 
+// ---------------------------------------------------------------------------------------------- files
+constexpr int COPY_WORDS = 4096;        // words of a file that one workgroup of png_copy_kernel writes
+constexpr int STILL_EXTRA = 57;         // signature 8, IHDR 25, IDAT 12 around its payload, IEND 12
+constexpr int APNG_FIXED = 65;          // signature 8, IHDR 25, acTL 20, IEND 12
+constexpr int APNG_FRAME = 50;          // fcTL 38, IDAT 12 around its payload; an fdAT has its sequence number, 4 more
+
+__device__ __forceinline__ void put_be16(u8 *p, u32 v) { p[0] = (u8)(v >> 8); p[1] = (u8)v; }
+__device__ __forceinline__ void put_be32(u8 *p, u32 v) { p[0] = (u8)(v >> 24); p[1] = (u8)(v >> 16); p[2] = (u8)(v >> 8); p[3] = (u8)v; }
+// a chunk's length and type
+__device__ __forceinline__ void put_head(u8 *p, u32 len, char a, char b, char c, char d) {
+  put_be32(p, len);
+  p[4] = (u8)a; p[5] = (u8)b; p[6] = (u8)c; p[7] = (u8)d;
+}
+// zlib.crc32 of a few bytes, bit by bit
+__device__ u32 crc_small(const u8 *p, int n) {
+  u32 r = 0xffffffffu;
+  for (int i = 0; i < n; ++i) {
+    r ^= p[i];
+    for (int k = 0; k < 8; ++k) r = (r >> 1) ^ (0xEDB88320u & (0u - (r & 1u)));
+  }
+  return ~r;
+}
+// the CRC behind the chunk at p, whose type and n bytes of payload this thread has written
+__device__ __forceinline__ void seal(u8 *p, int n) { put_be32(p + 8 + n, crc_small(p + 4, 4 + n)); }
+
+__device__ void put_front(u8 *p, int h, int w) {              // the signature and IHDR: 8 bits, RGB, no interlace
+  const u8 sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
+  for (int i = 0; i < 8; ++i) p[i] = sig[i];
+  p += 8;
+  put_head(p, 13, 'I', 'H', 'D', 'R');
+  put_be32(p + 8, (u32)w);
+  put_be32(p + 12, (u32)h);
+  p[16] = 8; p[17] = 2; p[18] = 0; p[19] = 0; p[20] = 0;
+  seal(p, 13);
+}
+__device__ void put_iend(u8 *p) {
+  put_head(p, 0, 'I', 'E', 'N', 'D');
+  seal(p, 0);
+}
+
+// One workgroup of 256, a thread per frame: everything of the files but the streams and their CRCs.  where[i]: the place of
+// frame i's stream in `files`; seed[i]: the CRC-32 of what the chunk's CRC covers in front of the stream (the type, and an
+// fdAT's sequence number).  A length outside 0 .. cap counts as the nearer end, here and in the two kernels behind.
+__global__ __launch_bounds__(256) void png_head_kernel(const int *__restrict__ lens, int n, int64_t cap, int h, int w, int animate,
+                                                       int delay_num, int delay_den, u8 *files, int64_t file_cap, int *file_len,
+                                                       int64_t *__restrict__ where, u32 *__restrict__ seed) {
+  __shared__ int wave_tot[4];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  int running = APNG_FIXED - 12;                             // where frame 0's fcTL starts
+  for (int k0 = 0; k0 < n; k0 += 256) {
+    const int i = k0 + tid;
+    const int len = i < n ? (int)min((int64_t)max(lens[i], 0), cap) : 0;
+    if (!animate) {
+      if (i < n) {
+        u8 *p = files + i * file_cap;
+        put_front(p, h, w);
+        put_head(p + 33, (u32)len, 'I', 'D', 'A', 'T');
+        seed[i] = crc_small(p + 37, 4);
+        where[i] = i * file_cap + 41;
+        put_iend(p + 41 + len + 4);
+        file_len[i] = len + STILL_EXTRA;
+      }
+      continue;
+    }
+    const int v = i < n ? APNG_FRAME + len + (i ? 4 : 0) : 0;
+    int incl = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int up = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += up;
+    }
+    __syncthreads();
+    if (lane == 63) wave_tot[wv] = incl;
+    __syncthreads();
+    int before = running;
+    for (int k = 0; k < wv; ++k) before += wave_tot[k];
+    if (i < n) {
+      u8 *p = files + before + incl - v;
+      if (i == 0) {
+        put_front(files, h, w);
+        put_head(files + 33, 8, 'a', 'c', 'T', 'L');
+        put_be32(files + 41, (u32)n);
+        put_be32(files + 45, 0);                             // num_plays: for ever
+        seal(files + 33, 8);
+      }
+      put_head(p, 26, 'f', 'c', 'T', 'L');
+      put_be32(p + 8, i ? 2u * i - 1 : 0u);
+      put_be32(p + 12, (u32)w);
+      put_be32(p + 16, (u32)h);
+      put_be32(p + 20, 0);
+      put_be32(p + 24, 0);
+      put_be16(p + 28, (u32)delay_num);
+      put_be16(p + 30, (u32)delay_den);
+      p[32] = 0; p[33] = 0;                                  // dispose none, blend source
+      seal(p, 26);
+      p += 38;
+      if (i == 0) put_head(p, (u32)len, 'I', 'D', 'A', 'T');
+      else {
+        put_head(p, (u32)len + 4, 'f', 'd', 'A', 'T');
+        put_be32(p + 8, 2u * i);
+      }
+      seed[i] = crc_small(p + 4, i ? 8 : 4);
+      where[i] = (p - files) + (i ? 12 : 8);
+    }
+    running += wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+  }
+  if (animate && tid == 0) {
+    put_iend(files + running);
+    file_len[0] = running + 12;
+  }
+}
+
+// grid: frames * chunks workgroups of 256, chunks = ceil(cap / (4 COPY_WORDS)): frame i's stream to where[i] in whole words
+// of the destination (the source comes through load_bytes4), its ends in bytes, and the chunk's CRC behind it
+__global__ __launch_bounds__(256) void png_copy_kernel(const u8 *__restrict__ streams, int64_t cap, const int *__restrict__ lens,
+                                                       int chunks, const int64_t *__restrict__ where, const u32 *__restrict__ crc,
+                                                       u8 *__restrict__ files) {
+  const int tid = threadIdx.x;
+  const int64_t bid = blockIdx.x;
+  const int j = (int)(bid % chunks);
+  const int64_t i = bid / chunks;
+  const int len = (int)min((int64_t)max(lens[i], 0), cap);
+  const u8 *src = streams + i * cap;
+  u8 *dst = files + where[i];
+  const int head = min(len, (int)((0 - (uintptr_t)dst) & 3)), words = (len - head) >> 2, tail = len - head - 4 * words;
+  if (j == 0) {
+    if (tid < head) dst[tid] = src[tid];
+    if (tid < tail) dst[head + 4 * words + tid] = src[head + 4 * words + tid];
+    if (tid < 4) dst[len + tid] = (u8)(crc[i] >> (24 - 8 * tid));
+  }
+  u32 *body = (u32 *)(dst + head);
+  const int k1 = min(words, (j + 1) * COPY_WORDS);
+  for (int k = j * COPY_WORDS + tid; k < k1; k += 256) body[k] = load_bytes4(src, head + 4 * (int64_t)k, len);
+}
+
 struct PngLayout {
   int rows, strips, pitch;
   size_t ints, stage, total;
@@ -610,6 +752,56 @@ extern "C" size_t sp_png_stream_bytes(int h, int w, int strip_rows) {
   const int64_t rows = strip_rows < h ? strip_rows : h, strips = (h + rows - 1) / rows;
   const int64_t bits = strips * (HEADER_BITS_MAX + TOKEN_BITS_MAX) + (int64_t)TOKEN_BITS_MAX * h * (1 + 3 * (int64_t)w);
   return (size_t)(2 + (bits + 7) / 8 + 4);
+}
+
+extern "C" size_t sp_png_file_bytes(int h, int w, int strip_rows) {
+  const size_t s = sp_png_stream_bytes(h, w, strip_rows);
+  return s ? s + STILL_EXTRA : 0;
+}
+
+extern "C" size_t sp_apng_file_bytes(int n, int h, int w, int strip_rows) {
+  const size_t s = sp_png_stream_bytes(h, w, strip_rows);
+  return (s && n > 0) ? APNG_FIXED + (size_t)n * (APNG_FRAME + s) + 4 * ((size_t)n - 1) : 0;
+}
+
+// ws: where (int64 per frame), seeds and CRCs (uint32 per frame each) | the CRC's scratch
+extern "C" size_t sp_png_wrap_ws_bytes(int n, size_t cap) {
+  const size_t crc = sp_crc32_ws_bytes(n, cap);
+  return crc ? align256((size_t)16 * n) + crc : 0;
+}
+
+extern "C" int sp_png_wrap(const void *streams, size_t cap, const void *lens, int n, int h, int w, int animate, int delay_num,
+                           int delay_den, void *files, size_t file_cap, void *file_len, void *ws, size_t ws_bytes, void *stream) {
+  SP_REQUIRE(streams && lens && files && file_len && ws, "sp_png_wrap: null pointer");
+  SP_REQUIRE(n > 0 && png_dims_ok(h, w), "sp_png_wrap: n must be positive, h and w in 1..65535 and h*w <= 2^24 (n=%d, %dx%d)", n, h, w);
+  SP_REQUIRE(cap > 0 && cap <= (size_t)0x7fffffff - STILL_EXTRA, "sp_png_wrap: cap %zu is not in 1..2^31-58", cap);
+  const size_t need_file = animate ? APNG_FIXED + (size_t)n * (APNG_FRAME + cap) + 4 * ((size_t)n - 1) : cap + STILL_EXTRA;
+  SP_REQUIRE(need_file <= (size_t)0x7fffffff, "sp_png_wrap: an animation of %d frames of %zu bytes does not fit an int32 length", n, cap);
+  SP_REQUIRE(file_cap >= need_file, "sp_png_wrap: file_cap is %zu bytes, streams of cap %zu can need %zu (sp_png_file_bytes / sp_apng_file_bytes)",
+             file_cap, cap, need_file);
+  if (animate) {
+    SP_REQUIRE(delay_num >= 1 && delay_num <= 65535 && delay_den >= 0 && delay_den <= 65535,
+               "sp_png_wrap: the delay %d / %d does not fit fcTL's 16-bit fields (numerator 1..65535, denominator 0..65535)", delay_num,
+               delay_den);
+  }
+  const size_t need = sp_png_wrap_ws_bytes(n, cap);
+  SP_REQUIRE(ws_bytes >= need, "sp_png_wrap: ws holds %zu bytes, needs %zu (sp_png_wrap_ws_bytes)", ws_bytes, need);
+  SP_REQUIRE((uintptr_t)ws % 8 == 0 && (uintptr_t)lens % 4 == 0 && (uintptr_t)file_len % 4 == 0,
+             "sp_png_wrap: ws must be 8-byte, lens and file_len 4-byte aligned");
+  const int chunks = (int)((cap + 4 * (size_t)COPY_WORDS - 1) / (4 * (size_t)COPY_WORDS));
+  SP_REQUIRE((int64_t)n * chunks <= 0x7fffffff && sp_crc32_ws_bytes(n, cap) / 4 <= (size_t)0x7fffffff, "sp_png_wrap: too many frames (%d)", n);
+  hipStream_t s = (hipStream_t)stream;
+  u8 *base = (u8 *)ws;
+  int64_t *where = (int64_t *)base;
+  u32 *seed = (u32 *)(where + n), *crc = seed + n;
+  SP_CLEAR_STALE_ERROR();
+  hipLaunchKernelGGL(png_head_kernel, dim3(1), dim3(256), 0, s, (const int *)lens, n, (int64_t)cap, h, w, animate, delay_num, delay_den,
+                     (u8 *)files, (int64_t)file_cap, (int *)file_len, where, seed);
+  sp_crc32_launch(streams, cap, lens, seed, n, crc, base + align256((size_t)16 * n), s);
+  hipLaunchKernelGGL(png_copy_kernel, dim3((unsigned)((int64_t)n * chunks)), dim3(256), 0, s, (const u8 *)streams, (int64_t)cap,
+                     (const int *)lens, chunks, (const int64_t *)where, (const u32 *)crc, (u8 *)files);
+  SP_CHECK_LAUNCH("sp_png_wrap");
+  return SP_OK;
 }
 
 extern "C" int sp_png_filter_u8(const void *frames, int n, int h, int w, void *filtered, void *stream) {

@@ -108,7 +108,13 @@ SIGNATURES = {
     "sp_png_stream_bytes": (_Z, [_I, _I, _I]),
     "sp_png_filter_u8": (_I, [_P, _I, _I, _I, _P, _P]),
     "sp_png_deflate": (_I, [_P, _I, _I, _I, _I, _P, _Z, _P, _P, _Z, _P]),
-    "sp_webp_ws_bytes": (_Z, [_I, _I, _I, _I, _I]),
+    "sp_png_file_bytes": (_Z, [_I, _I, _I]),
+    "sp_apng_file_bytes": (_Z, [_I, _I, _I, _I]),
+    "sp_png_wrap_ws_bytes": (_Z, [_I, _Z]),
+    "sp_png_wrap": (_I, [_P, _Z, _P, _I, _I, _I, _I, _I, _I, _P, _Z, _P, _P, _Z, _P]),
+    "sp_crc32_ws_bytes": (_Z, [_I, _Z]),
+    "sp_crc32_rows": (_I, [_P, _Z, _P, _P, _I, _P, _P, _Z, _P]),
+    "sp_webp_ws_bytes":(_Z, [_I, _I, _I, _I, _I]),
     "sp_webp_stream_bytes": (_Z, [_I, _I, _I, _I]),
     "sp_webp_transform_u8": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
     "sp_webp_code": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _Z, _P, _P, _Z, _P]),

@@ -662,6 +662,71 @@ def png_deflate(filtered, out, out_len, ws, *, strip_rows):
     return out, out_len
 
 
+def png_file_bytes(h: int, w: int, strip_rows: int) -> int:
+    return int(load().sp_png_file_bytes(h, w, strip_rows))
+
+
+def apng_file_bytes(n: int, h: int, w: int, strip_rows: int) -> int:
+    return int(load().sp_apng_file_bytes(n, h, w, strip_rows))
+
+
+def png_wrap_ws_bytes(n: int, cap: int) -> int:
+    return int(load().sp_png_wrap_ws_bytes(n, cap))
+
+
+def png_wrap(streams, lens, files, file_len, ws, *, height, width, animate=False, delay=(1, 7)):
+    """The zlib streams ``streams[i, :lens[i]]`` (uint8 (n, cap), int32 (n,): what ``png_deflate`` leaves) -> complete files on
+    the device (``sp_png_wrap``).  ``animate`` false: ``files`` is uint8 (n, file_cap), file_cap >= cap + 57, and row i one still
+    of ``file_len[i]`` bytes; true: ``files`` is one uint8 buffer of at least 65 + n (50 + cap) + 4 (n - 1) bytes that receives one
+    animated PNG of ``file_len[0]`` bytes, ``delay`` = (numerator, denominator) seconds per frame.  ``file_len``: int32 (n,);
+    ``ws``: uint8 scratch of ``png_wrap_ws_bytes``."""
+    _dev_buf(streams, torch.uint8, "png_wrap: streams"), _dev_buf(files, torch.uint8, "png_wrap: files")
+    _dev_buf(lens, torch.int32, "png_wrap: lens"), _dev_buf(file_len, torch.int32, "png_wrap: file_len")
+    _dev_buf(ws, torch.uint8, "png_wrap: ws")
+    if streams.dim() != 2 or lens.numel() != streams.shape[0] or file_len.numel() != streams.shape[0]:
+        raise ValueError("png_wrap: streams must be (n, cap), lens and file_len (n,)")
+    n, cap = streams.shape
+    if animate:
+        if files.dim() != 1:
+            raise ValueError(f"png_wrap: an animation's files must be one flat buffer; got {tuple(files.shape)}")
+        file_cap = files.numel()
+    else:
+        if files.dim() != 2 or files.shape[0] != n:
+            raise ValueError(f"png_wrap: files must be (n, file_cap); got {tuple(files.shape)}")
+        file_cap = files.shape[1]
+    _check(load().sp_png_wrap(streams.data_ptr(), cap, lens.data_ptr(), n, int(height), int(width), 1 if animate else 0,
+                              int(delay[0]), int(delay[1]), files.data_ptr(), file_cap, file_len.data_ptr(), ws.data_ptr(),
+                              ws.numel(), _stream()), "sp_png_wrap")
+    return files, file_len
+
+
+def crc32_ws_bytes(n: int, pitch: int) -> int:
+    return int(load().sp_crc32_ws_bytes(n, pitch))
+
+
+_WORD32 = tuple(t for t in (torch.int32, getattr(torch, "uint32", None)) if t is not None)
+
+
+def crc32_rows(data, lens, crc, ws, seed=None):
+    """``crc[i] = zlib.crc32(data[i, :lens[i]], seed[i])`` on the device (``sp_crc32_rows``).  ``data``: uint8 (n, pitch), any
+    pitch; ``lens``: int32 (n,), read on the device (below 0 counts as 0, above pitch as pitch); ``seed``: (n,) 32-bit words or
+    ``None`` for 0; ``crc``: (n,) 32-bit words (``torch.int32`` holds the bit pattern, ``torch.uint32`` is taken too); ``ws``:
+    uint8 scratch of ``crc32_ws_bytes``."""
+    _dev_buf(data, torch.uint8, "crc32_rows: data"), _dev_buf(lens, torch.int32, "crc32_rows: lens")
+    _dev_buf(ws, torch.uint8, "crc32_rows: ws")
+    if data.dim() != 2 or lens.numel() != data.shape[0]:
+        raise ValueError("crc32_rows: data must be (n, pitch) and lens (n,)")
+    n, pitch = data.shape
+    for name, t in (("crc", crc), ("seed", seed)):
+        if t is None and name == "seed":
+            continue
+        if t.dtype not in _WORD32 or not t.is_cuda or not t.is_contiguous() or t.numel() < n:
+            raise TypeError(f"crc32_rows: {name} must be a contiguous tensor of n 32-bit words on a HIP device")
+    _check(load().sp_crc32_rows(data.data_ptr(), pitch, lens.data_ptr(), _ptr(seed), n, crc.data_ptr(), ws.data_ptr(), ws.numel(),
+                                _stream()), "sp_crc32_rows")
+    return crc
+
+
 def webp_ws_bytes(n: int, h: int, w: int, pred_bits: int, group_bits: int) -> int:
     return int(load().sp_webp_ws_bytes(n, h, w, pred_bits, group_bits))
 

@@ -148,8 +148,9 @@ class FrameEmitter:
     sample finishes on this rank (its decode is long over by then) or in ``finish``.  ``output="gif"`` does the same with
     ``image_io.GifEncoder`` at ``gif_fps`` frames per second and keeps, per sample, one ``bytes`` (a complete animated GIF) for
     each of its B videos.  ``output="png"`` mirrors ``"jpeg"`` with ``image_io.PngEncoder``: per sample one ``list[bytes]`` of F PNG
-    files (lossless) for each of its B videos.  ``output="webp"`` mirrors ``"gif"`` with ``image_io.WebpEncoder``: per sample one
-    ``bytes`` (a complete animated lossless WebP at ``gif_fps`` frames per second) for each of its B videos.
+    files (lossless) for each of its B videos; the files are finished on the device (chunks and CRC-32 too) and the fetch only
+    copies them.  ``output="webp"`` mirrors ``"gif"`` with ``image_io.WebpEncoder``: per sample one ``bytes`` (a complete
+    animated lossless WebP at ``gif_fps`` frames per second) for each of its B videos.
     """
 
     def __init__(self, decoder: TemporalDecoderHIP, stage, num_frames: int, *, decode_chunk_size: int = 14,
@@ -170,7 +171,7 @@ class FrameEmitter:
         self.output, self.jpeg_quality, self.gif_fps = output, jpeg_quality, gif_fps
         self._jpeg = None               # the JpegEncoder (or, for output="png", the PngEncoder), made for the first sample's frame size
         self._gif = None                # the GifEncoders (or, for output="webp", the WebpEncoders), one per video of a sample (a video's buffers wait for the fetch)
-        self._pending = None            # (sample index, videos, streams, lengths, event) of the encode still on the device
+        self._pending = None            # (sample index, videos, streams or files, lengths, event) of the encode still on the device
         self.decoder, self.stage, self.num_frames = decoder, stage, num_frames
         self.chunk, self.keep, self.check_finite = decode_chunk_size, keep, check_finite
         cfg = stage.config
@@ -212,7 +213,9 @@ class FrameEmitter:
                     from .image_io import JpegEncoder, PngEncoder
                     self._jpeg = (JpegEncoder(self.device, out.shape[2], out.shape[3], self.jpeg_quality) if self.output == "jpeg"
                                   else PngEncoder(self.device, out.shape[2], out.shape[3]))
-                streams, lens = self._jpeg.enqueue(out.flatten(0, 1))
+                # (a PngEncoder that assembles on the device hands over finished files in place of streams)
+                enqueue = self._jpeg.enqueue_files if self._device_files() else self._jpeg.enqueue
+                streams, lens = enqueue(out.flatten(0, 1))
                 done = torch.cuda.Event()
                 done.record(self.stream)
                 self._pending = (idx, out.shape[0], streams, lens, done)
@@ -236,6 +239,9 @@ class FrameEmitter:
         elif self.keep == "last":
             self.frames = {idx: out}
 
+    def _device_files(self) -> bool:
+        return self.output == "png" and self._jpeg.assemble == "device"
+
     def _collect_jpeg(self) -> None:
         if self._pending is None:
             return
@@ -252,7 +258,7 @@ class FrameEmitter:
                     self._keep(idx, [write_webp(None, enc.collect_streams(*bufs), enc.width, enc.height, self.gif_fps)
                                      for enc, bufs in zip(self._gif, streams)])
                     return
-                files = self._jpeg.collect(streams, lens)
+                files = (self._jpeg.collect_files if self._device_files() else self._jpeg.collect)(streams, lens)
             per = len(files) // videos
             self._keep(idx, [files[v * per:(v + 1) * per] for v in range(videos)])
 

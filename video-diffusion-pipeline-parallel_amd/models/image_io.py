@@ -13,8 +13,8 @@
   * ``GifEncoder`` / ``write_gif``: the animated GIF of ``save_gif``: frames on the device are quantised to a palette each
     and LZW-coded there by the kernels of ``csrc/gif.hip``; the blocks of the file around them are written here.
   * ``PngEncoder`` / ``png_file`` / ``write_apng``: the lossless frames (a directory or a ``%03d.png`` pattern) and an
-    animated PNG: frames on the device are filtered and deflated there by the kernels of ``csrc/png.hip``; signature, chunks
-    and their CRC-32 (over compressed bytes the host has anyway) are written here.
+    animated PNG: frames on the device are filtered and deflated there by the kernels of ``csrc/png.hip``, and so are
+    signature, chunks and their CRC-32 (``csrc/crc32.hip``); ``png_file`` / ``write_apng`` build the same files here.
   * ``WebpEncoder`` / ``webp_file`` / ``write_webp``: lossless WebP stills and one animated WebP, full colour and playable
     in a browser: frames on the device become VP8L bitstreams there by the kernels of ``csrc/webp.hip``; the RIFF container
     has no checksum, so the host only wraps bytes.
@@ -404,6 +404,16 @@ def write_apng(path, streams, width: int, height: int, fps=7) -> bytes:
     return blob
 
 
+def _apng_delay(fps) -> Fraction:
+    """``write_apng``'s delay for the device route, which takes the two numbers: ``1 / fps`` s as a fraction of two 16-bit
+    numbers (``write_apng`` itself stays the self-contained statement the device files are held to)."""
+    delay = (1 / Fraction(_check_fps(fps))).limit_denominator(65535)
+    if not 0 < delay.numerator <= 65535:
+        raise ValueError(f"a delay of 1 / {fps} s does not fit the frame control chunk")
+    return delay
+
+
+PNG_ASSEMBLE = "device"             # chunks and CRC-32 on the device ("host": png_file / write_apng around the streams); profiles/png_timing.txt
 PNG_STRIP_ROWS = 16                  # the fastest of 4 / 8 / 16 / 32 rows within 1 % of one strip per frame (profiles/png_timing.txt)
 
 
@@ -415,11 +425,20 @@ class PngEncoder:
     independent sequences; at 576 x 1024 strips of 16 rows cost 0.11 % in size over one strip per frame and are the fastest
     measured (profiles/png_timing.txt).  Filtered, stream, length and scratch
     buffers are kept per frame count; the stream buffer holds ``sp_png_stream_bytes`` per frame (the size no input can exceed),
-    of which only the used bytes are ever copied to the host."""
+    of which only the used bytes are ever copied to the host.
 
-    def __init__(self, device, height: int, width: int, strip_rows: int = PNG_STRIP_ROWS) -> None:
+    ``assemble="device"`` (the default) also puts the files together there (``sp_png_wrap``: chunks, the CRC-32 of each, an
+    animation's frames at the exclusive sum of their lengths), so that ``encode`` / ``encode_apng`` only copy finished files
+    (``enqueue_files`` / ``collect_files``, ``enqueue_apng`` / ``collect_apng``); ``assemble="host"`` copies the streams and
+    wraps them with ``png_file`` / ``write_apng`` (``zlib.crc32``).  The bytes are the same; ``enqueue`` / ``collect_streams``
+    / ``collect`` are the host route's pieces under either setting."""
+
+    def __init__(self, device, height: int, width: int, strip_rows: int = PNG_STRIP_ROWS, assemble: str = PNG_ASSEMBLE) -> None:
         self.device = common.hip_device(device, "PngEncoder")
         self.height, self.width = int(height), int(width)
+        if assemble not in ("device", "host"):
+            raise ValueError(f"assemble must be 'device' or 'host'; got {assemble!r}")
+        self.assemble = assemble
         if isinstance(strip_rows, bool) or not isinstance(strip_rows, (int, np.integer)) or strip_rows < 1:
             raise ValueError(f"strip_rows must be a positive integer; got {strip_rows!r}")
         self.strip_rows = int(strip_rows)
@@ -459,14 +478,54 @@ class PngEncoder:
         """The PNG files of an ``enqueue`` whose work has finished."""
         return [png_file(self.height, self.width, s) for s in self.collect_streams(out, lens)]
 
-    def encode(self, frames_u8: torch.Tensor) -> list[bytes]:
+    def enqueue_files(self, frames_u8: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+        """``enqueue``, then the files around the streams on the device (``sp_png_wrap``): ``(files (F, file_cap) uint8, lengths
+        (F,) int32)``, row i the complete PNG of frame i, equal to ``png_file`` of its stream.  Views of this encoder's buffers,
+        valid until the next call with as many frames."""
         out, lens = self.enqueue(frames_u8)
+        n = out.shape[0]
+        files = self._buf("files", (n, ops.png_file_bytes(self.height, self.width, self.strip_rows)), torch.uint8)
+        file_lens = self._buf("file_len", (n,), torch.int32)
+        ws = self._buf("wrap_ws", (ops.png_wrap_ws_bytes(n, self.cap),), torch.uint8)
+        ops.png_wrap(out, lens, files, file_lens, ws, height=self.height, width=self.width)
+        return files, file_lens
+
+    def enqueue_apng(self, frames_u8: torch.Tensor, fps=7) -> tuple[torch.Tensor, torch.Tensor]:
+        """``enqueue``, then one animated PNG of the frames on the device: ``(file (apng_file_bytes,) uint8, length (F,) int32 of
+        which [0] counts)``, equal to ``write_apng`` of the streams (whose delay, ``1 / fps`` s as a fraction of two 16-bit
+        numbers, is worked out here on the host)."""
+        delay = _apng_delay(fps)
+        out, lens = self.enqueue(frames_u8)
+        n = out.shape[0]
+        file = self._buf("apng", (ops.apng_file_bytes(n, self.height, self.width, self.strip_rows),), torch.uint8)
+        file_lens = self._buf("apng_len", (n,), torch.int32)
+        ws = self._buf("wrap_ws", (ops.png_wrap_ws_bytes(n, self.cap),), torch.uint8)
+        ops.png_wrap(out, lens, file, file_lens, ws, height=self.height, width=self.width, animate=True,
+                     delay=(delay.numerator, delay.denominator))
+        return file, file_lens
+
+    def collect_files(self, files: torch.Tensor, file_lens: torch.Tensor) -> list[bytes]:
+        """The PNG files of an ``enqueue_files`` whose work has finished: the lengths come to the host first, then only the used
+        bytes; the host adds nothing to them."""
+        return [files[i, :n].cpu().numpy().tobytes() for i, n in enumerate(file_lens.cpu().tolist())]
+
+    def collect_apng(self, file: torch.Tensor, file_lens: torch.Tensor) -> bytes:
+        """The animated PNG of an ``enqueue_apng`` whose work has finished: one copy of the length, one of the used bytes."""
+        return file[:int(file_lens[:1].cpu()[0])].cpu().numpy().tobytes()
+
+    def encode(self, frames_u8: torch.Tensor) -> list[bytes]:
+        bufs = self.enqueue_files(frames_u8) if self.assemble == "device" else self.enqueue(frames_u8)
         torch.cuda.current_stream(self.device).synchronize()
-        return self.collect(out, lens)
+        return self.collect_files(*bufs) if self.assemble == "device" else self.collect(*bufs)
 
     def encode_apng(self, frames_u8: torch.Tensor, fps=7) -> bytes:
-        """One animated PNG of the frames (``write_apng`` around the same streams)."""
+        """One animated PNG of the frames: put together on the device, or under ``assemble="host"`` by ``write_apng`` around the
+        same streams; the bytes are the same."""
         _check_fps(fps)
+        if self.assemble == "device":
+            bufs = self.enqueue_apng(frames_u8, fps)
+            torch.cuda.current_stream(self.device).synchronize()
+            return self.collect_apng(*bufs)
         out, lens = self.enqueue(frames_u8)
         torch.cuda.current_stream(self.device).synchronize()
         return write_apng(None, self.collect_streams(out, lens), self.width, self.height, fps)
