@@ -475,6 +475,74 @@ int sp_jpeg_entropy(const void *coef, int n, int mcu_rows, int mcu_cols, int res
                     void *ws, size_t ws_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Pictures in: a baseline JPEG file decoded on the device from its compressed bytes (the reference opens its input with
+ * Pillow on the host: scripts/generate_video_demo.py:75 there).  Decoded: SOF0, 8-bit samples and tables, one component
+ * (grey, returned as R = G = B) or three (YCbCr, chrominance sampled 1x1, luminance 1x1, 2x1 or 2x2), one interleaved scan,
+ * any restart interval or none.  The host walks the markers and hands over the header's numbers and tables (a "plan", host
+ * memory) and the entropy-coded segment (device memory); a copy of the plan in device memory goes to every call as plan_dev.
+ * Four calls, in this order on one stream; all leave at once while the status block reports an error, so a broken stream is
+ * never followed, and no call reads or writes outside its buffers, whatever the bytes are.
+ *
+ * The status block is the first 64 int32 of ws: [0] error bits (1 an 0xFF that neither 0x00 nor RSTn follows, 2 RSTn out of
+ * order, 4 number of RSTn, 8 an unassigned code / a zigzag index past 63 / a size above 11 (DC) or 10 (AC), 16 an interval
+ * whose blocks do not come to its MCUs x blocks per MCU), [1] a pass found the fixed point reached, [2] passes executed,
+ * [3] bytes of the clean stream, [4] RSTn markers, [5] subsequences, [6] subsequences of the longest interval,
+ * [10] coefficients written.
+ * ------------------------------------------------------------------------------------------- */
+size_t sp_jpeg_decode_plan_bytes(void);
+/* Host only.  fields: 17 int32 = width, height, components (1 or 3), luminance sampling h, v, restart interval (0: none),
+ * bytes of the entropy-coded segment (1..2^28-1), subseq_bits (a multiple of 32 in 32..2^20), quantisation table selector
+ * per component [3], DC table selector per component [3], AC table selector per component [3] (Huffman selectors 0 or 1).
+ * quant4x64: tables 0..3 in natural (row-major) order; bits4x16 / vals4x256: the DHT specifications of DC 0, DC 1, AC 0,
+ * AC 1; have_quant / have_huff: bit i set where table i was defined.  Writes sp_jpeg_decode_plan_bytes() bytes to plan.
+ * SP_EINVAL for numbers outside the scope above, a selector without its table, or a specification no canonical code has
+ * (which includes one that assigns an all-ones code). */
+int sp_jpeg_decode_plan(const int32_t *fields, const uint8_t *quant4x64, int have_quant, const uint8_t *bits4x16,
+                        const uint8_t *vals4x256, int have_huff, void *plan);
+/* Scratch of the four calls / bytes of the coefficients, int16 [mcu_rows][mcu_cols][blocks_per_mcu][64] (zigzag order, DC
+ * absolute; for 2x2 sampling the layout of sp_jpeg_dct_quant_u8).  0 for a pointer that is no plan. */
+size_t sp_jpeg_decode_ws_bytes(const void *plan);
+size_t sp_jpeg_decode_coef_bytes(const void *plan);
+/* 1. Unstuff and split.  Clears the status block; removes the 0x00 behind every 0xFF of coded data and the RSTn markers
+ * (flags, an exclusive scan), writes the clean bytes and the byte range of every restart interval (one interval without
+ * DRI), checks that the markers count 0..7 in order and are as many as the intervals need; then cuts every interval into
+ * subsequences of subseq_bits. */
+int sp_jpeg_decode_split(const void *plan, const void *plan_dev, const void *segment, void *ws, size_t ws_bytes, void *stream);
+/* 2. Synchronisation passes first_pass .. first_pass + passes - 1 (passes 1..4096; the first call starts at 0, a further
+ * one where the last ended).  One lane per subsequence.  Pass 0: every lane decodes from its nominal first bit in state
+ * (block 0 of the MCU, zigzag index 0) -- true of an interval's first subsequence only -- until it has stepped past its
+ * end, and records where (bit position, block of the MCU, zigzag index) and how many blocks it completed.  Pass q: lane i
+ * starts from lane i-1's record of pass q-1.  A pass that changes no record has reached the fixed point, which by induction
+ * from each interval's first lane is the serial decode; every later pass leaves at once.  A lane stops where a code plus
+ * its extra bits would pass the interval's end.  A lane that started at a wrong bit meets things no valid stream holds and
+ * has to find the true walk all the same, so it notes them in its record and goes on: an unassigned code is passed over
+ * by one bit, a size above 11 (DC) / 10 (AC) is taken as it is, an index past 63, a ZRL past the block's end or an EOBn
+ * ends the block.  The note is not part of the state the next lane starts from; at the fixed point every lane started
+ * from the true state, and a note still set is error bit 8 (stage 3 reports it).  The host reads the status block to learn whether more passes are needed
+ * (never more than the subsequences of the longest interval, plus the one that finds nothing changed). */
+int sp_jpeg_decode_sync(const void *plan, const void *plan_dev, void *ws, size_t ws_bytes, int first_pass, int passes, void *stream);
+/* 3. Coefficients; last_pass is the last pass enqueued.  Does nothing unless the fixed point is reached (status [10] stays
+ * 0).  Exclusive scan of the lanes' block counts; an interval whose chain is not exactly its MCUs x blocks per MCU sets
+ * error bit 16; the lanes walk once more and store (every store guarded by its interval's last block and by the index
+ * 0..63); then a segmented scan per component turns DC differences into values: predictors 0 at every interval start,
+ * sums in 32 bits, clamped to int16. */
+int sp_jpeg_decode_coefficients(const void *plan, const void *plan_dev, void *ws, size_t ws_bytes, int last_pass, void *coef,
+                                void *stream);
+/* 4. Pixels: coef -> rgb uint8 [h][w][3].  Per block, in integers: a coefficient times its table entry, then libjpeg's
+ * accurate inverse DCT (jidctint): constants of 13 fraction bits (0.298631336 = 2446 ... 3.072711026 = 25172), the column
+ * pass first, descaled by 11 bits (two extra bits kept), then the row pass, descaled by 18, plus 128, through libjpeg's
+ * range table (a clamp to 0..255 for values within +-512 of it).  Chrominance is upsampled with libjpeg's triangle filter
+ * at the component's own size cw x ch = ceil(w/2) x ceil(h/2 or h), edges replicated there and not at the MCU grid:
+ *   2x1: out[2i] = (3 c[i] + c[i-1] + 1) >> 2,  out[2i+1] = (3 c[i] + c[i+1] + 2) >> 2,  out[0] = c[0], out[2cw-1] = c[cw-1]
+ *   2x2: s[i] = 3 c[j][i] + c[j'][i], j' = j-1 for an even output row and j+1 for an odd one (clamped to 0..ch-1);
+ *        out[2i] = (3 s[i] + s[i-1] + 8) >> 4, out[2i+1] = (3 s[i] + s[i+1] + 7) >> 4, at the two ends (4 s[i] + 8 or 7) >> 4
+ * and where cw <= 2 samples are repeated instead, as libjpeg does.  Then JFIF's conversion in 16-bit fixed point:
+ *   R = Y + ((91881 Cr' + 32768) >> 16)        G = Y + ((-22554 Cb' - 46802 Cr' + 32768) >> 16)
+ *   B = Y + ((116130 Cb' + 32768) >> 16)       Cb' = Cb - 128, Cr' = Cr - 128, clamped to 0..255. */
+int sp_jpeg_decode_pixels(const void *plan, const void *plan_dev, void *ws, size_t ws_bytes, const void *coef, void *rgb,
+                          void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Animated GIF of uint8 frames that are in device memory (the reference's save_gif hands its frames to imageio:
  * scripts/generate_video_demo.py:212-222 there).  Two stages: a 256-colour palette and the pixels' indices per
  * frame, then the LZW-coded image data of the frame's image block.  Headers, extensions, descriptors and the trailer are

@@ -100,6 +100,14 @@ SIGNATURES = {
     "sp_jpeg_stream_bytes": (_Z, [_I, _I, _I]),
     "sp_jpeg_entropy_ws_bytes": (_Z, [_I, _I, _I, _I]),
     "sp_jpeg_entropy": (_I, [_P, _I, _I, _I, _I, _P, _Z, _P, _P, _Z, _P]),
+    "sp_jpeg_decode_plan_bytes": (_Z, []),
+    "sp_jpeg_decode_plan": (_I, [_P, _P, _I, _P, _P, _I, _P]),
+    "sp_jpeg_decode_ws_bytes": (_Z, [_P]),
+    "sp_jpeg_decode_coef_bytes": (_Z, [_P]),
+    "sp_jpeg_decode_split": (_I, [_P, _P, _P, _P, _Z, _P]),
+    "sp_jpeg_decode_sync": (_I, [_P, _P, _P, _Z, _I, _I, _P]),
+    "sp_jpeg_decode_coefficients": (_I, [_P, _P, _P, _Z, _I, _P, _P]),
+    "sp_jpeg_decode_pixels": (_I, [_P, _P, _P, _Z, _P, _P, _P]),
     "sp_gif_ws_bytes": (_Z, [_I, _I, _I, _I]),
     "sp_gif_stream_bytes": (_Z, [_I, _I, _I]),
     "sp_gif_quantise_u8": (_I, [_P, _I, _I, _I, _P, _P, _P, _Z, _P]),

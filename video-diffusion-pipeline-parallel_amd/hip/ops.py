@@ -582,6 +582,80 @@ def jpeg_entropy(coef, out, out_len, ws, *, restart_mcus):
     return out, out_len
 
 
+def jpeg_decode_plan(fields, quant, have_quant: int, bits, vals, have_huff: int) -> bytes:
+    """The plan of one baseline JPEG (``sp_jpeg_decode_plan``, host only): ``fields`` 17 ints, ``quant`` 4 x 64 bytes in natural
+    order, ``bits`` 4 x 16 and ``vals`` 4 x 256 bytes (DC 0, DC 1, AC 0, AC 1), ``have_*`` the bit sets of the tables defined.
+    ``ValueError`` with the library's reason for what it refuses."""
+    if len(fields) != 17 or len(quant) != 256 or len(bits) != 64 or len(vals) != 1024:
+        raise ValueError("jpeg_decode_plan: fields holds 17 ints, quant 256, bits 64 and vals 1024 bytes")
+    f = (ctypes.c_int32 * 17)(*[int(v) for v in fields])
+    q, b, v = (ctypes.c_uint8 * 256).from_buffer_copy(bytes(quant)), (ctypes.c_uint8 * 64).from_buffer_copy(bytes(bits)), \
+        (ctypes.c_uint8 * 1024).from_buffer_copy(bytes(vals))
+    lib = load()
+    plan = ctypes.create_string_buffer(lib.sp_jpeg_decode_plan_bytes())
+    if lib.sp_jpeg_decode_plan(ctypes.addressof(f), ctypes.addressof(q), int(have_quant), ctypes.addressof(b), ctypes.addressof(v),
+                               int(have_huff), ctypes.addressof(plan)) != 0:
+        raise ValueError(last_error())
+    return plan.raw
+
+
+class JpegPlan:
+    """A plan in host memory (kept alive here) next to its copy on the device: what the four decode calls take."""
+
+    def __init__(self, plan: bytes, plan_dev: torch.Tensor) -> None:
+        self.host = ctypes.create_string_buffer(plan, len(plan))
+        _dev_buf(plan_dev, torch.uint8, "JpegPlan: plan_dev")
+        if plan_dev.numel() < len(plan):
+            raise ValueError("JpegPlan: plan_dev is shorter than the plan")
+        self.dev = plan_dev
+        self.ws_bytes = int(load().sp_jpeg_decode_ws_bytes(ctypes.addressof(self.host)))
+        self.coef_bytes = int(load().sp_jpeg_decode_coef_bytes(ctypes.addressof(self.host)))
+
+    @property
+    def ptr(self) -> int:
+        return ctypes.addressof(self.host)
+
+
+def jpeg_decode_plan_bytes() -> int:
+    return int(load().sp_jpeg_decode_plan_bytes())
+
+
+def jpeg_decode_split(plan: JpegPlan, segment, ws):
+    """Stage 1 (``sp_jpeg_decode_split``): ``segment`` uint8 device bytes of the entropy-coded segment, ``ws`` uint8 scratch of
+    ``plan.ws_bytes`` whose first 64 int32 are the status block."""
+    _dev_buf(segment, torch.uint8, "jpeg_decode_split: segment"), _dev_buf(ws, torch.uint8, "jpeg_decode_split: ws")
+    _check(load().sp_jpeg_decode_split(plan.ptr, plan.dev.data_ptr(), segment.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+           "sp_jpeg_decode_split")
+
+
+def jpeg_decode_sync(plan: JpegPlan, ws, first_pass: int, passes: int):
+    """Stage 2 (``sp_jpeg_decode_sync``): synchronisation passes ``first_pass .. first_pass + passes - 1``."""
+    _dev_buf(ws, torch.uint8, "jpeg_decode_sync: ws")
+    _check(load().sp_jpeg_decode_sync(plan.ptr, plan.dev.data_ptr(), ws.data_ptr(), ws.numel(), int(first_pass), int(passes),
+                                      _stream()), "sp_jpeg_decode_sync")
+
+
+def jpeg_decode_coefficients(plan: JpegPlan, ws, last_pass: int, coef):
+    """Stage 3 (``sp_jpeg_decode_coefficients``): ``coef`` int16 of ``plan.coef_bytes``; nothing happens before the fixed point."""
+    _dev_buf(ws, torch.uint8, "jpeg_decode_coefficients: ws"), _dev_buf(coef, torch.int16, "jpeg_decode_coefficients: coef")
+    if coef.numel() * 2 != plan.coef_bytes:
+        raise ValueError(f"jpeg_decode_coefficients: coef must hold {plan.coef_bytes} bytes; got {coef.numel() * 2}")
+    _check(load().sp_jpeg_decode_coefficients(plan.ptr, plan.dev.data_ptr(), ws.data_ptr(), ws.numel(), int(last_pass),
+                                              coef.data_ptr(), _stream()), "sp_jpeg_decode_coefficients")
+    return coef
+
+
+def jpeg_decode_pixels(plan: JpegPlan, ws, coef, rgb):
+    """Stage 4 (``sp_jpeg_decode_pixels``): ``coef`` -> ``rgb`` uint8 (h, w, 3)."""
+    _dev_buf(ws, torch.uint8, "jpeg_decode_pixels: ws"), _dev_buf(coef, torch.int16, "jpeg_decode_pixels: coef")
+    _dev_buf(rgb, torch.uint8, "jpeg_decode_pixels: rgb")
+    if coef.numel() * 2 != plan.coef_bytes or rgb.dim() != 3 or rgb.shape[2] != 3:
+        raise ValueError("jpeg_decode_pixels: coef must hold plan.coef_bytes and rgb be (h, w, 3)")
+    _check(load().sp_jpeg_decode_pixels(plan.ptr, plan.dev.data_ptr(), ws.data_ptr(), ws.numel(), coef.data_ptr(), rgb.data_ptr(),
+                                        _stream()), "sp_jpeg_decode_pixels")
+    return rgb
+
+
 def gif_ws_bytes(n: int, h: int, w: int, strip_rows: int) -> int:
     return int(load().sp_gif_ws_bytes(n, h, w, strip_rows))
 

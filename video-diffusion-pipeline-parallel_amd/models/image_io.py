@@ -19,6 +19,9 @@
     in a browser: frames on the device become VP8L bitstreams there by the kernels of ``csrc/webp.hip``; the RIFF container
     has no checksum, so the host only wraps bytes.
   * ``load_image``: the decode half of ``load_and_preprocess_image`` (Pillow; a file format is host work).
+  * ``parse_jpeg`` / ``JpegDecoder`` / ``load_image_device``: the same decode for the common baseline JPEG on the device: the
+    host walks the markers, the compressed bytes are uploaded, and the kernels of ``csrc/jpeg_decode.hip`` go from the
+    entropy-coded segment to (H, W, 3) uint8 RGB, which the front end takes as it is.
 """
 
 from __future__ import annotations
@@ -216,6 +219,286 @@ class JpegEncoder:
         out, lens = self.enqueue(frames_u8)
         torch.cuda.current_stream(self.device).synchronize()
         return self.collect(out, lens)
+
+
+class UnsupportedJpeg(ValueError):
+    """A well-formed JPEG that the device decoder does not take (the message names the cause); Pillow decodes it."""
+
+
+class JpegInfo:
+    """What ``parse_jpeg`` reads out of the marker segments of a baseline JPEG."""
+
+    __slots__ = ("width", "height", "components", "hs", "vs", "tq", "td", "ta", "quant", "dht", "restart_interval",
+                 "segment_offset", "segment_length")
+
+    def __init__(self, **kw) -> None:
+        for k in self.__slots__:
+            setattr(self, k, kw[k])
+
+    def plan_fields(self, subseq_bits: int) -> list[int]:
+        pad = lambda t: list(t) + [0] * (3 - len(t))                      # noqa: E731
+        return [self.width, self.height, self.components, self.hs, self.vs, self.restart_interval, self.segment_length,
+                int(subseq_bits)] + pad(self.tq) + pad(self.td) + pad(self.ta)
+
+    def plan_tables(self) -> tuple[bytes, int, bytes, bytes, int]:
+        """``(quant 4 x 64, have_quant, bits 4 x 16, vals 4 x 256, have_huff)`` as ``ops.jpeg_decode_plan`` takes them."""
+        quant, bits, vals, have_q, have_h = bytearray(256), bytearray(64), bytearray(1024), 0, 0
+        for tq, table in self.quant.items():
+            quant[64 * tq:64 * tq + 64] = bytes(table)
+            have_q |= 1 << tq
+        for (tc, th), (b, v) in self.dht.items():
+            slot = 2 * tc + th
+            bits[16 * slot:16 * slot + 16] = b
+            vals[256 * slot:256 * slot + len(v)] = v
+            have_h |= 1 << slot
+        return bytes(quant), have_q, bytes(bits), bytes(vals), have_h
+
+
+_SOF_NAMES = {0xC1: "extended sequential", 0xC2: "progressive", 0xC3: "lossless", 0xC5: "differential sequential",
+              0xC6: "differential progressive", 0xC7: "differential lossless", 0xC9: "arithmetic-coded sequential",
+              0xCA: "arithmetic-coded progressive", 0xCB: "arithmetic-coded lossless", 0xCD: "arithmetic-coded differential",
+              0xCE: "arithmetic-coded differential progressive", 0xCF: "arithmetic-coded differential lossless"}
+
+
+def parse_jpeg(data) -> JpegInfo:
+    """The marker walk of a JPEG file, SOI up to SOS: size, sampling, table selectors, quantisation tables (natural order), the
+    DHT specifications ``(bits16, vals)``, the restart interval, and offset and length of the entropy-coded segment, which runs
+    from behind SOS to the last EOI of the file (to the file's end without one).  No entropy-coded byte is read.
+    ``UnsupportedJpeg`` names what is outside the device decoder's scope (SOF0, 8 bit, one component or YCbCr 4:4:4 / 4:2:2 /
+    4:2:0, one interleaved scan); ``ValueError`` reports a malformed header."""
+    data = bytes(data)
+    if len(data) < 4 or data[:2] != b"\xff\xd8":
+        raise ValueError("not a JPEG file: no SOI marker at its start")
+    zz = _zigzag()
+    quant, dht, frame, restart, jfif, adobe = {}, {}, None, 0, False, None
+    at = 2
+    while True:
+        if at + 2 > len(data):
+            raise ValueError("truncated JPEG header: the file ends before SOS")
+        if data[at] != 0xFF:
+            raise ValueError(f"malformed JPEG header: byte {data[at]:#04x} at offset {at} where a marker should start")
+        while at + 1 < len(data) and data[at + 1] == 0xFF:              # fill bytes
+            at += 1
+        marker = data[at + 1]
+        at += 2
+        if marker == 0x01 or 0xD0 <= marker <= 0xD7:
+            continue
+        if marker in (0xD8, 0xD9):
+            raise ValueError(f"malformed JPEG header: marker {marker:#04x} before SOS")
+        if at + 2 > len(data):
+            raise ValueError("truncated JPEG header: the file ends inside a marker segment")
+        length = struct.unpack(">H", data[at:at + 2])[0]
+        if length < 2 or at + length > len(data):
+            raise ValueError(f"malformed JPEG header: the segment of marker {marker:#04x} at offset {at - 2} has a length past the end")
+        body = data[at + 2:at + length]
+        if marker == 0xDB:
+            k = 0
+            while k < len(body):
+                pq, tq = body[k] >> 4, body[k] & 15
+                if pq != 0:
+                    raise UnsupportedJpeg("16-bit quantisation table")
+                if tq > 3 or k + 65 > len(body):
+                    raise ValueError("malformed DQT segment")
+                table = np.zeros(64, np.uint8)
+                table[zz] = np.frombuffer(body[k + 1:k + 65], np.uint8)
+                if not table.all():
+                    raise ValueError("malformed DQT segment: a zero divisor")
+                quant[tq] = table
+                k += 65
+        elif marker == 0xC4:
+            k = 0
+            while k < len(body):
+                if k + 17 > len(body):
+                    raise ValueError("malformed DHT segment")
+                tc, th = body[k] >> 4, body[k] & 15
+                bits = body[k + 1:k + 17]
+                n = sum(bits)
+                if tc > 1 or th > 3 or n > 256 or k + 17 + n > len(body):
+                    raise ValueError("malformed DHT segment")
+                if th > 1:
+                    raise UnsupportedJpeg("Huffman table selector above 1 (not baseline)")
+                dht[(tc, th)] = (bits, body[k + 17:k + 17 + n])
+                k += 17 + n
+        elif marker == 0xC0:
+            if frame is not None:
+                raise ValueError("malformed JPEG header: two frame headers")
+            if len(body) < 6 or len(body) != 6 + 3 * body[5]:
+                raise ValueError("malformed SOF0 segment")
+            precision, height, width, nf = struct.unpack(">BHHB", body[:6])
+            if precision != 8:
+                raise UnsupportedJpeg(f"{precision}-bit samples")
+            if width == 0 or height == 0:
+                raise ValueError("malformed SOF0 segment: zero size")
+            frame = (width, height, [(body[6 + 3 * i], body[7 + 3 * i] >> 4, body[7 + 3 * i] & 15, body[8 + 3 * i]) for i in range(nf)])
+        elif marker in _SOF_NAMES:
+            raise UnsupportedJpeg(f"{_SOF_NAMES[marker]} JPEG (SOF{marker - 0xC0})")
+        elif marker == 0xDC:
+            raise UnsupportedJpeg("DNL segment")
+        elif marker == 0xDD:
+            if len(body) != 2:
+                raise ValueError("malformed DRI segment")
+            restart = struct.unpack(">H", body)[0]
+        elif marker == 0xE0 and body[:5] == b"JFIF\0":
+            jfif = True
+        elif marker == 0xEE and body[:5] == b"Adobe" and len(body) >= 12:
+            adobe = body[11]
+        elif marker == 0xDA:
+            break
+        at += length
+    if frame is None:
+        raise ValueError("malformed JPEG header: SOS before a frame header")
+    width, height, comps = frame
+    if len(comps) == 4:
+        raise UnsupportedJpeg("four components (CMYK / YCCK)")
+    if len(comps) not in (1, 3):
+        raise UnsupportedJpeg(f"{len(comps)} components")
+    ns = body[0] if body else 0
+    if len(body) != 4 + 2 * ns:
+        raise ValueError("malformed SOS segment")
+    if ns != len(comps):
+        raise UnsupportedJpeg("more than one scan (the first holds not all components)")
+    if [body[1 + 2 * i] for i in range(ns)] != [c[0] for c in comps]:
+        raise UnsupportedJpeg("the scan's components are not in the frame's order")
+    ss, se, ahal = body[1 + 2 * ns:4 + 2 * ns]
+    if (ss, se, ahal) != (0, 63, 0):
+        raise UnsupportedJpeg(f"spectral selection / successive approximation in a scan (Ss={ss}, Se={se}, Ah/Al={ahal:#04x})")
+    if len(comps) == 3:
+        if not jfif and (adobe == 0 or (adobe is None and [c[0] for c in comps] == [82, 71, 66])):
+            raise UnsupportedJpeg("three components that are RGB, not YCbCr (Adobe transform 0)")
+        if adobe == 2 and not jfif:
+            raise UnsupportedJpeg("Adobe transform 2 (YCCK)")
+        hs, vs = comps[0][1], comps[0][2]
+        if any((c[1], c[2]) != (1, 1) for c in comps[1:]) or (hs, vs) not in ((1, 1), (2, 1), (2, 2)):
+            raise UnsupportedJpeg("sampling factors " + ", ".join(f"{c[1]}x{c[2]}" for c in comps)
+                                  + " (chrominance must be 1x1, luminance 1x1, 2x1 or 2x2)")
+    else:
+        hs, vs = 1, 1
+        if (comps[0][1], comps[0][2]) != (1, 1):
+            raise UnsupportedJpeg(f"one component sampled {comps[0][1]}x{comps[0][2]}")
+    tq = tuple(c[3] for c in comps)
+    td = tuple(body[2 + 2 * i] >> 4 for i in range(ns))
+    ta = tuple(body[2 + 2 * i] & 15 for i in range(ns))
+    if any(t > 1 for t in td + ta):
+        raise UnsupportedJpeg("Huffman table selector above 1 (not baseline)")
+    if not quant or not dht:
+        raise ValueError("malformed JPEG header: a missing table (no " + ("DQT" if not quant else "DHT") + " segment before SOS)")
+    for c in range(ns):
+        if tq[c] not in quant or (0, td[c]) not in dht or (1, ta[c]) not in dht:
+            raise ValueError(f"malformed JPEG header: component {c} selects a table that is not defined (a table selector without its table)")
+    start = at + length
+    end = data.rfind(b"\xff\xd9")
+    if end < start:
+        end = len(data)
+    if end <= start:
+        raise ValueError("truncated JPEG: no entropy-coded data behind SOS")
+    return JpegInfo(width=width, height=height, components=len(comps), hs=hs, vs=vs, tq=tq, td=td, ta=ta, quant=quant, dht=dht,
+                    restart_interval=restart, segment_offset=start, segment_length=end - start)
+
+
+# the largest count of passes seen over the fixtures of tests/test_jpeg_decode_cpu.py plus 2 (profiles/jpeg_decode_parity.txt)
+JPEG_SYNC_PASSES = 51
+
+_JPEG_ERRORS = ((1, "a 0xFF in the coded data that neither 0x00 nor RSTn follows"), (2, "restart markers out of order"),
+                (4, "the number of restart markers does not fit the restart interval"),
+                (8, "an unassigned Huffman code, a coefficient index past 63 or a size category out of range"),
+                (16, "a restart interval whose blocks do not come to its MCUs"))
+
+
+class JpegDecoder:
+    """A baseline JPEG file in host memory -> (H, W, 3) uint8 RGB on the device, decoded there (``csrc/jpeg_decode.hip``).
+
+    Only the compressed bytes are uploaded, behind the plan ``parse_jpeg``'s fields become.  Every restart interval (the whole
+    scan in a file without DRI) is cut into subsequences of ``subseq_bits`` bits, one lane each; the lanes synchronise in
+    passes, and ``sync_passes`` of them are enqueued at a time: ``decode`` reads the status block once behind them and
+    enqueues further rounds only where the fixed point was not reached, so the result never depends on ``sync_passes``.
+    ``last_passes`` is the count of passes the last picture took (the one that found nothing changed included),
+    ``last_coef`` its coefficients (a view of this decoder's buffer, valid until the next call)."""
+
+    def __init__(self, device, subseq_bits: int = 1024, sync_passes: int = JPEG_SYNC_PASSES) -> None:
+        self.device = common.hip_device(device, "JpegDecoder")
+        if isinstance(subseq_bits, bool) or not isinstance(subseq_bits, (int, np.integer)) or subseq_bits < 32 or subseq_bits % 32:
+            raise ValueError(f"subseq_bits must be a multiple of 32, at least 32; got {subseq_bits!r}")
+        if isinstance(sync_passes, bool) or not isinstance(sync_passes, (int, np.integer)) or not 1 <= sync_passes <= 4096:
+            raise ValueError(f"sync_passes must be an integer in 1..4096; got {sync_passes!r}")
+        self.subseq_bits, self.sync_passes = int(subseq_bits), int(sync_passes)
+        self.last_passes, self.last_coef, self.last_status, self.last_info = 0, None, None, None
+        self._scratch: dict = {}
+        self._job = None
+
+    def _buf(self, name: str, nbytes: int, dtype=torch.uint8) -> torch.Tensor:
+        key = (name, nbytes, dtype)
+        if key not in self._scratch:
+            self._scratch = {k: v for k, v in self._scratch.items() if k[0] != name}      # one buffer per name: pictures differ in size
+            self._scratch[key] = torch.empty(nbytes // torch.empty((), dtype=dtype).element_size(), dtype=dtype, device=self.device)
+        return self._scratch[key]
+
+    def _round(self, first_pass: int) -> None:
+        plan, ws, coef, rgb = self._job[:4]
+        ops.jpeg_decode_sync(plan, ws, first_pass, self.sync_passes)
+        ops.jpeg_decode_coefficients(plan, ws, first_pass + self.sync_passes - 1, coef)
+        ops.jpeg_decode_pixels(plan, ws, coef, rgb)
+        self._job[4] = first_pass + self.sync_passes
+
+    def enqueue(self, data) -> torch.Tensor:
+        """Parse, upload, and enqueue the four stages with one round of passes on the current stream.  Returns the (H, W, 3)
+        uint8 tensor the picture is written to; whether it was is known only to ``finish`` (``decode`` = ``enqueue`` + ``finish``)."""
+        data = bytes(data)
+        info = parse_jpeg(data)
+        plan_host = ops.jpeg_decode_plan(info.plan_fields(self.subseq_bits), *info.plan_tables())
+        blob = bytearray(plan_host) + data[info.segment_offset:info.segment_offset + info.segment_length]
+        up = torch.frombuffer(blob, dtype=torch.uint8).to(self.device, non_blocking=True)
+        plan = ops.JpegPlan(plan_host, up[:len(plan_host)])
+        ws = self._buf("ws", plan.ws_bytes)
+        coef = self._buf("coef", plan.coef_bytes, torch.int16)
+        rgb = torch.empty((info.height, info.width, 3), dtype=torch.uint8, device=self.device)
+        self._job = [plan, ws, coef, rgb, 0, up]
+        self.last_info = info
+        ops.jpeg_decode_split(plan, up[len(plan_host):], ws)
+        self._round(0)
+        return rgb
+
+    def finish(self) -> torch.Tensor:
+        """Read the status block of the picture enqueued last (this waits for the stream), enqueue further rounds of passes while
+        the fixed point is not reached, and return the picture.  ``ValueError`` where the status block reports an error."""
+        if self._job is None:
+            raise RuntimeError("JpegDecoder.finish: nothing was enqueued")
+        plan, ws, coef, rgb = self._job[:4]
+        while True:
+            st = ws[:256].view(torch.int32).cpu().tolist()
+            self.last_status, self.last_passes = st, st[2]
+            if st[0]:
+                self._job = None
+                raise ValueError("JpegDecoder: broken entropy-coded segment: " + "; ".join(m for b, m in _JPEG_ERRORS if st[0] & b))
+            if st[10]:
+                break
+            if self._job[4] > st[6] + 1:
+                done, self._job = self._job[4], None
+                raise RuntimeError(f"JpegDecoder: no fixed point after {done} passes over {st[6]} subsequences")
+            self._round(self._job[4])
+        info = self.last_info
+        mcu_cols, mcu_rows = -(-info.width // (8 * info.hs)), -(-info.height // (8 * info.vs))
+        self.last_coef = coef.view(mcu_rows, mcu_cols, 1 if info.components == 1 else info.hs * info.vs + 2, 64)
+        self._job = None
+        return rgb
+
+    def decode(self, data) -> torch.Tensor:
+        self.enqueue(data)
+        return self.finish()
+
+
+def load_image_device(path: str, device) -> torch.Tensor:
+    """A picture file -> (H, W, 3) uint8 RGB on ``device``: a JPEG that ``parse_jpeg`` accepts is decoded there from its
+    compressed bytes (``JpegDecoder``); every other file is decoded by Pillow (``load_image``) and uploaded."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    if data[:2] == b"\xff\xd8":
+        try:
+            parse_jpeg(data)
+        except ValueError:                                            # UnsupportedJpeg too: Pillow's file, and Pillow's message
+            pass
+        else:
+            return JpegDecoder(device).decode(data)
+    return torch.from_numpy(load_image(path)).to(common.hip_device(device, "load_image_device"))
 
 
 def _jpeg_host(frame: np.ndarray, quality: int) -> bytes:

@@ -18,6 +18,10 @@ or a directory of PNGs, and ``.apng``, one lossless animated PNG at ``--fps``: P
 too (``image_io.PngEncoder``) -- and ``.webp``, lossless WebP in full colour that a browser plays: one animated file at
 ``--fps``, or with a ``%03d.webp`` pattern one still per frame, transformed and entropy-coded on the GPU
 (``image_io.WebpEncoder``)).  The frames go to ``save_frames`` as the device tensor they are.
+
+``--input-decode device`` decodes a baseline JPEG picture on the GPU from its compressed bytes (``image_io.load_image_device``:
+only plan and entropy-coded segment are uploaded; files outside the device decoder's scope still go through Pillow); the
+default, ``host``, is Pillow's decode and the upload of the pixels, as before.
 """
 
 from __future__ import annotations
@@ -39,6 +43,8 @@ def parse_args(argv=None) -> argparse.Namespace:
     p = argparse.ArgumentParser(description="Generate video frames from an image (SVD step pipeline)")
     p.add_argument("--input-image", type=str, required=True, help="picture file (anything Pillow decodes)")
     p.add_argument("--output", type=str, required=True, help=".avi (Motion-JPEG video), .gif, .apng (lossless animated PNG), .webp (lossless animated WebP), .npy, a %%03d.jpg, %%03d.png or %%03d.webp pattern, or a directory for PNG frames")
+    p.add_argument("--input-decode", type=str, default="host", choices=["host", "device"],
+                   help="host: Pillow decodes the picture; device: a baseline JPEG is decoded on the GPU from its compressed bytes (other files still go through Pillow)")
     p.add_argument("--height", type=int, default=576)
     p.add_argument("--width", type=int, default=1024)
     p.add_argument("--num-frames", type=int, default=14)
@@ -118,7 +124,7 @@ def _build_engines(args, timesteps, device):
 
 def main(argv=None) -> None:
     from ..models.edge_stages import encode_image_u8
-    from ..models.image_io import ImageFrontEnd, load_image, save_frames
+    from ..models.image_io import ImageFrontEnd, load_image, load_image_device, save_frames
     from ..models.svd_unet import StableVideoUNet
 
     args = parse_args(argv)
@@ -128,7 +134,8 @@ def main(argv=None) -> None:
     local_rank = int(os.environ.get("LOCAL_RANK", rank))
     device = torch.device(f"cuda:{local_rank}")
     torch.cuda.set_device(device)
-    image = load_image(args.input_image)                 # before the process group: a missing file fails alone
+    # before the process group: a missing file fails alone
+    image = load_image_device(args.input_image, device) if args.input_decode == "device" else load_image(args.input_image)
     # one process started without torchrun: nothing is ever sent, the group only has to exist (Gloo, rendezvous in a file)
     alone = world == 1 and args.init_method is None and "MASTER_ADDR" not in os.environ
     backend = resolve_backend(None if args.backend == "auto" else args.backend, simulator=alone and args.backend == "auto")
