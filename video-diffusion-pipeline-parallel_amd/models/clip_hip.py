@@ -166,6 +166,20 @@ class CLIPVisionHIP:
         ops.ln_stats(x, st, rows=x.shape[0], c=x.shape[1], eps=layer.ln_eps)
         return st
 
+    def _run_layer(self, L, x, b, seq):
+        """One pre-LayerNorm encoder layer on the hidden state ``x`` [b*seq][C] -> the next hidden state."""
+        sp = self.spec
+        c, heads = sp.hidden_size, sp.num_attention_heads
+        m, hd = b * seq, c // heads
+        qkv = self._gemm(L["qkv"], x, m, ln_stats=self._ln_stats(L["qkv"], x))
+        o = self._buf(m, c)
+        ops.attn_small(qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:], o, ldq=3 * c, ldk=3 * c, ldv=3 * c, ldo=c, batch=b,
+                       seq=seq, heads=heads, head_dim=hd, scale=1.0 / math.sqrt(hd))
+        x = self._gemm(L["out"], o, m, res1=x, r1scale=1.0)
+        f = self._gemm(L["fc1"], x, m, ln_stats=self._ln_stats(L["fc1"], x))
+        ops.gelu(f, f, quick=sp.hidden_act == "quick_gelu")
+        return self._gemm(L["fc2"], f, m, res1=x, r1scale=1.0)
+
     def __call__(self, pixel_values):
         """pixel_values: fp16 (B, 3, image_size, image_size), already resized / normalised by the CLIPImageProcessor
         (ref generate_video_demo.py:108-109).  Returns ``image_embeds`` fp16 (B, projection_dim)."""
@@ -175,8 +189,8 @@ class CLIPVisionHIP:
             raise ValueError(f"pixel_values must be (B, 3, {sp.image_size}, {sp.image_size}); got {tuple(pixel_values.shape)}")
         if pixel_values.dtype != torch.float16 or pixel_values.device != self.device or not pixel_values.is_contiguous():
             raise TypeError("pixel_values must be a contiguous float16 tensor on this encoder's device")
-        b, c, heads = pixel_values.shape[0], sp.hidden_size, sp.num_attention_heads
-        npatch, seq, hd = self.n_patches, self.n_patches + 1, c // heads
+        b, c = pixel_values.shape[0], sp.hidden_size
+        npatch, seq = self.n_patches, self.n_patches + 1
         m = b * seq
         patches = self._buf(b * npatch, self.kpad)
         ops.patchify(pixel_values, patches, batch=b, h=sp.image_size, w=sp.image_size, patch=sp.patch_size, kpad=self.kpad)
@@ -187,16 +201,8 @@ class CLIPVisionHIP:
                      cin=self.kpad, bias2=self.pos_patches, bias2_rows=1)
         x = self._buf(m, c)
         ops.layernorm(emb, self.pre_ln.g, self.pre_ln.b, x, rows=m, c=c, eps=self.pre_ln.eps)
-        scale = 1.0 / math.sqrt(hd)
         for L in self.layers:
-            qkv = self._gemm(L["qkv"], x, m, ln_stats=self._ln_stats(L["qkv"], x))
-            o = self._buf(m, c)
-            ops.attn_small(qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:], o, ldq=3 * c, ldk=3 * c, ldv=3 * c, ldo=c, batch=b,
-                           seq=seq, heads=heads, head_dim=hd, scale=scale)
-            x = self._gemm(L["out"], o, m, res1=x, r1scale=1.0)
-            f = self._gemm(L["fc1"], x, m, ln_stats=self._ln_stats(L["fc1"], x))
-            ops.gelu(f, f, quick=sp.hidden_act == "quick_gelu")
-            x = self._gemm(L["fc2"], f, m, res1=x, r1scale=1.0)
+            x = self._run_layer(L, x, b, seq)
         # pooled = post_layernorm(last_hidden_state[:, 0]); image_embeds = visual_projection(pooled)
         pooled = self._buf(b, c)
         for i in range(b):
