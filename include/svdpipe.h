@@ -328,6 +328,20 @@ int sp_euler_step_f16(const void *latent, const void *eps_cond, const void *eps_
 int sp_euler_step_rows_f16(const void *latent, const void *eps_cond, const void *eps_uncond,
                            int64_t ld_eps, const float *guidance, int64_t ld_guidance, void *out, float sigma,
                            float sigma_next, int b, int frames, int h, int w, void *stream);
+/* DPM-Solver++(2M) update (csrc/solver.hip), the second-order multistep sampler with one UNet evaluation per step.  The
+ * solver's history rides in the latent: state and out_state are fp16 (B,8,F,H,W), channels 0-3 the sample x, channels
+ * 4-7 the previous step's denoised estimate D_prev.  Per element, fp32 math on fp16 storage:
+ *   e  = eps_u + g[b,f]*(eps_c - eps_u)   evaluated in fp16 exactly as sp_euler_step_rows_f16 does; e = eps_c if !eps_uncond
+ *   D  = x/(sigma^2+1) - e*sigma/sqrt(sigma^2+1)          (v-prediction: the c_skip / c_out of the Euler update)
+ *   x' = a*x + b*(c1*D - c2*D_prev)  -> out_state[:, 0:4];     D -> out_state[:, 4:8]
+ * a = sigma'/sigma, b = 1 - a, c2 = h/(2*h_last), c1 = 1 + c2 (models/solver_schedule.py); c1 = 1, c2 = 0 at the first and
+ * the last step, where x' = a*x + b*D is algebraically the Euler step.  With c2 == 0 channels 4-7 of state are NOT read
+ * (step 0's are don't-care).  eps rows, guidance rows and ld_guidance as for sp_euler_step_rows_f16.  Refused: sigma <= 0,
+ * a outside [0, 1), c2 < 0, out_state overlapping state unless it IS state (in place). */
+int sp_dpmpp2m_step_rows_f16(const void *state, const void *eps_cond, const void *eps_uncond,
+                             int64_t ld_eps, const float *guidance, int64_t ld_guidance, void *out_state,
+                             float sigma, float a, float b, float c1, float c2,
+                             int batch, int frames, int h, int w, void *stream);
 /* channel concat of two NHWC tensors (torch.cat([hidden, skip], dim=1) in the up blocks) */
 int sp_concat_channels_f16(const void *a, int ca, const void *b, int cb, void *out, int64_t rows,
                            void *stream);

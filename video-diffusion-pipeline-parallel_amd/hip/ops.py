@@ -900,6 +900,21 @@ def euler_step(latent, eps_cond, eps_uncond, guidance, out, *, ld_eps, sigma, si
     return out
 
 
+def dpmpp2m_step(state, eps_cond, eps_uncond, guidance, out_state, *, ld_eps, sigma, a, b, c1, c2, batch, frames, h, w,
+                 ld_guidance=0):
+    """DPM-Solver++(2M) update of the 8-channel ``state`` (B,8,F,H,W: sample ++ previous denoised estimate) into
+    ``out_state`` (may be ``state`` itself); ``guidance`` / ``ld_guidance`` as for ``euler_step``
+    (``sp_dpmpp2m_step_rows_f16``)."""
+    for name, t in (("state", state), ("out_state", out_state)):
+        if _f16(t, name).shape != (batch, 8, frames, h, w) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous ({batch}, 8, {frames}, {h}, {w}) tensor; got {tuple(t.shape)}, "
+                             f"strides {tuple(t.stride())}")
+    _check(load().sp_dpmpp2m_step_rows_f16(state.data_ptr(), eps_cond.data_ptr(), _ptr(eps_uncond), ld_eps, _ptr(guidance),
+                                           int(ld_guidance), out_state.data_ptr(), sigma, a, b, c1, c2, batch, frames, h, w,
+                                           _stream()), "sp_dpmpp2m_step_rows_f16")
+    return out_state
+
+
 def concat_channels(a, ca, b, cb, out, rows):
     with _Timed("concat", 0.0, 2 * 2.0 * rows * (ca + cb)):
         _check(load().sp_concat_channels_f16(a.data_ptr(), ca, b.data_ptr(), cb, out.data_ptr(), rows, _stream()),

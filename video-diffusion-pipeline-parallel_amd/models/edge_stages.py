@@ -151,12 +151,20 @@ class FrameEmitter:
     files (lossless) for each of its B videos; the files are finished on the device (chunks and CRC-32 too) and the fetch only
     copies them.  ``output="webp"`` mirrors ``"gif"`` with ``image_io.WebpEncoder``: per sample one ``bytes`` (a complete
     animated lossless WebP at ``gif_fps`` frames per second) for each of its B videos.
+
+    ``latent_view`` (a callable, default None): applied to a finished latent before it is decoded, for pipelines whose
+    carried tensor holds more than the sample -- ``StableVideoUNet(sampler="dpmpp_2m").sample_of`` takes the four sample
+    channels out of the 8-channel solver state.
     """
 
     def __init__(self, decoder: TemporalDecoderHIP, stage, num_frames: int, *, decode_chunk_size: int = 14,
                  spread: bool = True, keep: str = "all", check_finite: bool = False, output: str = "float32",
-                 jpeg_quality: int = 90, gif_fps=7) -> None:
+                 jpeg_quality: int = 90, gif_fps=7, latent_view=None) -> None:
         from ..pipeline.step_assignment import ring_finish_rank
+
+        if latent_view is not None and not callable(latent_view):
+            raise ValueError("latent_view must be a callable (finished latent -> the (B,4,F,H,W) latents to decode) or None")
+        self.latent_view = latent_view
 
         if keep not in ("all", "last", "none"):
             raise ValueError("keep must be 'all', 'last' or 'none'")
@@ -204,6 +212,8 @@ class FrameEmitter:
         latent.record_stream(self.stream)
         with torch.cuda.stream(self.stream):
             self.stream.wait_event(ready)
+            if self.latent_view is not None:          # (a view shares the finished latent's storage, recorded above)
+                latent = self.latent_view(latent)
             if self.output in ("jpeg", "gif", "png", "webp"):
                 self._collect_jpeg()           # before this decode is queued: the encoder's buffers are free again after it
             decode = self.decoder.decode_latents if self.output == "float32" else self.decoder.decode_latents_uint8

@@ -25,7 +25,7 @@ from dataclasses import dataclass
 import torch
 import torch.nn as nn
 
-from . import euler_schedule
+from . import euler_schedule, solver_schedule
 from .unet_hip import SVDUNetHIP
 from .unet_spec import UNetConfig, random_state_dict
 
@@ -87,11 +87,22 @@ class StableVideoUNet(nn.Module):
         dtype: torch.dtype = torch.float16,
         num_train_timesteps: int = 1000,
         batched_cfg: bool = False,
+        sampler: str = "euler",
     ) -> None:
         """``batched_cfg`` (extension): run the unconditional and conditional passes of
         classifier-free guidance as ONE batch-2 UNet forward instead of two sequential passes
-        (ref ``svd_unet.py:384-411`` runs them one after the other)."""
+        (ref ``svd_unet.py:384-411`` runs them one after the other).
+
+        ``sampler`` (extension; the reference hard-codes Euler, ``svd_unet.py:427-439``): ``"euler"``, or ``"dpmpp_2m"`` for
+        DPM-Solver++(2M), second order with still one UNet evaluation per step.  Its history -- the previous step's
+        denoised estimate -- rides in the latent: ``forward`` then takes and returns (B,8,F,H,W), channels 0-3 the sample,
+        channels 4-7 the estimate (``init_state`` / ``sample_of``), the model keeps no state between calls, and the
+        steps are called in index order (0, 1, 2, ...)."""
         super().__init__()
+        if sampler not in solver_schedule.SAMPLERS:
+            raise ValueError(f"sampler must be one of {solver_schedule.SAMPLERS}; got {sampler!r}")
+        self.sampler = sampler
+        self.state_channels = 8 if sampler == "dpmpp_2m" else 4
         self.batched_cfg = batched_cfg
         self._use_graphs = os.environ.get("VDPP_GRAPHS", "0") == "1"
         self._graphs: dict = {}          # (calling stream, step, latent shape) -> (graph, static_in, static_out)
@@ -128,6 +139,25 @@ class StableVideoUNet(nn.Module):
         self._sigma_host = [float(s) for s in sig]
         self._t_dev = self.scheduler_timesteps.to(self.unet.device)   # device table, indexed per step
         self._init_noise_sigma = float((sig[0] ** 2 + 1) ** 0.5)
+        self._solver_coef = solver_schedule.dpmpp_2m_coefficients(sig) if self.sampler == "dpmpp_2m" else None
+
+    # ------------------------------------------------------------------ sampler state
+    def init_state(self, noise: torch.Tensor) -> torch.Tensor:
+        """The tensor ``forward`` steps, from the initial noise (B,4,F,H,W): the noise itself for Euler; for
+        ``dpmpp_2m`` (B,8,F,H,W) with the noise in channels 0-3 and zeros in the history channels (step 0 does not read
+        them)."""
+        if self.state_channels == 4:
+            return noise
+        if noise.dim() != 5 or noise.shape[1] != 4:
+            raise ValueError(f"noise must be (B, 4, F, H, W); got {tuple(noise.shape)}")
+        state = noise.new_zeros((noise.shape[0], 8) + tuple(noise.shape[2:]))
+        state[:, :4] = noise
+        return state
+
+    def sample_of(self, state: torch.Tensor) -> torch.Tensor:
+        """The sample (B,4,F,H,W) inside a stepped tensor: the tensor itself for Euler, a view of channels 0-3 for
+        ``dpmpp_2m``."""
+        return state if self.state_channels == 4 else state[:, :4]
 
     @property
     def init_noise_sigma(self) -> float:
@@ -149,6 +179,7 @@ class StableVideoUNet(nn.Module):
         enable_sliced_attention: bool = False,
         attention_slice_size: int | str = "auto",
         device="cuda",
+        sampler: str = "euler",
         **kwargs,
     ) -> "StableVideoUNet":
         """Load ``<model_id>/unet/diffusion_pytorch_model*.safetensors`` from a LOCAL directory.
@@ -197,18 +228,18 @@ class StableVideoUNet(nn.Module):
             )
         if timesteps is None:
             timesteps = cls._default_timestep_schedule(num_steps=25)
-        return cls(unet=SVDUNetHIP(cfg, sd, device), timesteps=timesteps, dtype=torch_dtype)
+        return cls(unet=SVDUNetHIP(cfg, sd, device), timesteps=timesteps, dtype=torch_dtype, sampler=sampler)
 
     @classmethod
     def from_random_init(cls, timesteps: Sequence[int], *, config: UNetConfig | None = None, seed: int = 0,
                          device="cuda", fp8_attention: bool | None = None,
-                         long_attention: bool | None = None) -> "StableVideoUNet":
+                         long_attention: bool | None = None, sampler: str = "euler") -> "StableVideoUNet":
         """Random weights of the exact SVD architecture (benchmarks / tests; no checkpoint needed)."""
         cfg = config or UNetConfig.svd()
         sd = random_state_dict(cfg, seed=seed, device=device, dtype=torch.float16)
         unet = SVDUNetHIP(cfg, sd, device, fp8_attention=fp8_attention, long_attention=long_attention)
         del sd
-        return cls(unet=unet, timesteps=timesteps)
+        return cls(unet=unet, timesteps=timesteps, sampler=sampler)
 
     def enable_graphs(self, enabled: bool = True) -> None:
         """Replay each diffusion step from a captured HIP graph (one graph per step index and latent shape).
@@ -371,8 +402,9 @@ class StableVideoUNet(nn.Module):
 
     @torch.inference_mode()
     def forward(self, latent: torch.Tensor, step: int, conditioning: VideoConditioning | None = None) -> torch.Tensor:
-        """One Euler step of ``latent`` (B,4,F,H,W).  ``conditioning`` (``prepare_conditioning``): what this call is
-        conditioned on; None = the model's own (``set_conditioning``)."""
+        """One Euler step of ``latent`` (B,4,F,H,W), or with ``sampler="dpmpp_2m"`` one DPM-Solver++(2M) step of the
+        (B,8,F,H,W) state (``init_state``).  ``conditioning`` (``prepare_conditioning``): what this call is conditioned on;
+        None = the model's own (``set_conditioning``)."""
         from ..hip import ops
 
         cond = self._cond if conditioning is None else conditioning
@@ -396,11 +428,18 @@ class StableVideoUNet(nn.Module):
         """The kernels take raw pointers and the latent's (B, F, H, W): a conditioning tensor of another shape would be
         read out of bounds (the reference fails in ``torch.cat`` / on broadcast, ``svd_unet.py:385-411``)."""
         cond = self._cond if cond is None else cond
-        if latent.dim() != 5 or latent.shape[1] != 4:
+        if self.state_channels == 8:
+            if latent.dim() == 5 and latent.shape[1] == 4:
+                raise ValueError(f"sampler='dpmpp_2m' steps a (B, 8, F, H, W) state (sample ++ previous denoised estimate); "
+                                 f"got the bare sample {tuple(latent.shape)}: wrap the noise in model.init_state()")
+            if latent.dim() != 5 or latent.shape[1] != 8:
+                raise ValueError(f"latent must be (B, 8, F, H, W) with sampler='dpmpp_2m'; got {tuple(latent.shape)}")
+        elif latent.dim() != 5 or latent.shape[1] != 4:
             raise ValueError(f"latent must be (B, 4, F, H, W); got {tuple(latent.shape)}")
-        if tuple(cond.image_latents.shape) != tuple(latent.shape):
+        sample_shape = (latent.shape[0], 4) + tuple(latent.shape[2:])
+        if tuple(cond.image_latents.shape) != sample_shape:
             raise ValueError(f"image_latents {tuple(cond.image_latents.shape)} do not match the latent "
-                             f"{tuple(latent.shape)} (set_conditioning was called for another batch / frame count / size)")
+                             f"{sample_shape} (set_conditioning was called for another batch / frame count / size)")
         emb = cond.image_embeddings
         if emb.dim() != 3 or emb.shape[0] != latent.shape[0] or emb.shape[1] != 1 \
                 or emb.shape[2] != self.unet.cfg.cross_attention_dim:
@@ -464,6 +503,8 @@ class StableVideoUNet(nn.Module):
         from ..hip import ops
 
         cond = self._cond if cond is None else cond
+        if self.sampler == "dpmpp_2m":
+            return self._forward_dpmpp_2m(latent, step, cond)
         b, _, f, h, w = latent.shape
         sigma, sigma_next = self._sigma_host[step], self._sigma_host[step + 1]
         in_scale = 1.0 / math.sqrt(sigma * sigma + 1.0)
@@ -492,4 +533,33 @@ class StableVideoUNet(nn.Module):
         ops.euler_step(latent, eps_c, eps_u, cond.guidance32 if eps_u is not None else None, out,
                        ld_eps=eps_c.shape[1], sigma=sigma, sigma_next=sigma_next, b=b, frames=f, h=h, w=w,
                        ld_guidance=cond.guidance_ld)
+        return out
+
+    def _forward_dpmpp_2m(self, state: torch.Tensor, step: int, cond: VideoConditioning) -> torch.Tensor:
+        """One DPM-Solver++(2M) step of ``state`` (B,8,F,H,W).  The UNet passes are those of the Euler step without its
+        tail: ``conv_out`` stores its four eps channels and ``sp_dpmpp2m_step_rows_f16`` follows with this step's
+        coefficients (host constants, so a captured graph of the step holds them)."""
+        from ..hip import ops
+
+        b, _, f, h, w = state.shape
+        sigma = self._sigma_host[step]
+        in_scale = 1.0 / math.sqrt(sigma * sigma + 1.0)
+        a, b_, c1, c2 = self._solver_coef[step]
+        x = state[:, :4].contiguous()                     # (a view for one video; else a copy of the four sample planes)
+        ids = cond.added_ids32
+        eps_u = None
+        if cond.guided and self.batched_cfg:
+            both = self._unet_pass(torch.cat([x, x], dim=0),
+                                   torch.cat([cond.uncond_image_latents, cond.image_latents], dim=0),
+                                   torch.cat([cond.uncond_embeddings, cond.image_embeddings], dim=0), in_scale, step,
+                                   added_ids32=ids if ids.dim() == 1 else torch.cat([ids, ids], dim=0))
+            half = both.shape[0] // 2
+            eps_u, eps_c = both[:half], both[half:]
+        else:
+            if cond.guided:
+                eps_u = self._unet_pass(x, cond.uncond_image_latents, cond.uncond_embeddings, in_scale, step, added_ids32=ids)
+            eps_c = self._unet_pass(x, cond.image_latents, cond.image_embeddings, in_scale, step, added_ids32=ids)
+        out = torch.empty_like(state)
+        ops.dpmpp2m_step(state, eps_c, eps_u, cond.guidance32 if eps_u is not None else None, out, ld_eps=eps_c.shape[1],
+                         sigma=sigma, a=a, b=b_, c1=c1, c2=c2, batch=b, frames=f, h=h, w=w, ld_guidance=cond.guidance_ld)
         return out

@@ -49,6 +49,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--width", type=int, default=1024)
     p.add_argument("--num-frames", type=int, default=14)
     p.add_argument("--total-steps", type=int, default=25)
+    p.add_argument("--sampler", type=str, default="euler", choices=["euler", "dpmpp_2m"],
+                   help="euler: the reference's first-order update; dpmpp_2m: DPM-Solver++(2M), second order at one UNet "
+                        "evaluation per step (its history travels in the latent; the steps run in index order)")
     p.add_argument("--fps", type=int, default=7)
     p.add_argument("--jpeg-quality", type=int, default=90, help="quality (1-100) of .avi / .jpg frames")
     p.add_argument("--motion-bucket-id", type=int, default=127)
@@ -110,16 +113,23 @@ def _build_engines(args, timesteps, device):
         ucfg = UNetConfig.tiny(64) if args.tiny else UNetConfig.svd()
         spec = CLIPVisionSpec.tiny(ucfg.cross_attention_dim) if args.tiny else CLIPVisionSpec.svd()
         vcfg = VAEDecoderConfig.tiny(64) if args.tiny else VAEDecoderConfig.svd()
-        model = StableVideoUNet.from_random_init(timesteps, config=ucfg, seed=args.seed, device=device)
+        model = StableVideoUNet.from_random_init(timesteps, config=ucfg, seed=args.seed, device=device, sampler=args.sampler)
         clip = CLIPVisionHIP(spec, clip_random_state_dict(spec, seed=args.seed + 1, device=device), device)
         enc = ImageEncoderHIP(vcfg, random_encoder_state_dict(vcfg, seed=args.seed + 2, device=device), device)
         return model, clip, enc, lambda: TemporalDecoderHIP(vcfg, random_state_dict(vcfg, seed=args.seed + 3, device=device),
                                                             device)
     from ..models.edge_stages import load_edge_engines
 
-    model = StableVideoUNet.from_pretrained(args.model_id, timesteps=timesteps, device=device)
+    model = StableVideoUNet.from_pretrained(args.model_id, timesteps=timesteps, device=device, sampler=args.sampler)
     clip, enc, dec = load_edge_engines(args.model_id, device)
     return model, clip, enc, lambda: dec
+
+
+def _step_order(sampler: str, total_steps: int) -> list:
+    """The ``step`` values the pipeline hands to the model, in order.  Euler keeps the reference modes' descending list
+    (``production.py:88``: the value is passed verbatim); a multistep solver needs the previous
+    step's estimate and walks the sigma table in index order."""
+    return list(range(total_steps)) if sampler == "dpmpp_2m" else list(range(total_steps - 1, -1, -1))
 
 
 def main(argv=None) -> None:
@@ -156,20 +166,22 @@ def main(argv=None) -> None:
                                    noise_aug_strength=args.noise_aug_strength, guidance_scale=args.guidance_scale,
                                    num_frames=args.num_frames)
             shape = torch.Size((1, 4, args.num_frames, args.height // 8, args.width // 8))
-            spec = LatentSpec(shape=shape, dtype=torch.float16, device=device)
+            # what a stage boundary carries: the sample, and with dpmpp_2m the solver's history behind it (8 channels)
+            carried = torch.Size((1, model.state_channels) + tuple(shape[2:]))
+            spec = LatentSpec(shape=carried, dtype=torch.float16, device=device)
 
             def supplier(i: int) -> torch.Tensor:
                 torch.manual_seed(args.seed + i)
-                return torch.randn(shape, device=device, dtype=torch.float16) * model.init_noise_sigma
+                return model.init_state(torch.randn(shape, device=device, dtype=torch.float16) * model.init_noise_sigma)
 
             outs = run_pipeline_latents(model, total_steps=args.total_steps,
-                                        timesteps=list(range(args.total_steps - 1, -1, -1)), world_size=world,
+                                        timesteps=_step_order(args.sampler, args.total_steps), world_size=world,
                                         rank=rank, latent_spec=spec, num_samples=args.num_samples,
                                         input_supplier=supplier if rank == 0 else None, balanced=args.balanced)
             if outs:
                 decoder = make_decoder()
                 for i, latents in enumerate(outs):
-                    frames = decoder.decode_latents_uint8(latents.contiguous(), args.num_frames,
+                    frames = decoder.decode_latents_uint8(model.sample_of(latents).contiguous(), args.num_frames,
                                                           decode_chunk_size=args.decode_chunk_size)
                     # the device tensor goes in as it is: .avi / .jpg frames are compressed where they are
                     files = save_frames(frames[0], sample_output_path(args.output, i, args.num_samples), args.fps,

@@ -22,6 +22,9 @@ LOGGER = logging.getLogger(__name__)
 def parse_args(argv=None) -> argparse.Namespace:
     p = argparse.ArgumentParser(description="Pipeline production mode (SVD)")
     p.add_argument("--total-steps", type=int, default=28)
+    p.add_argument("--sampler", type=str, default="euler", choices=["euler", "dpmpp_2m"],
+                   help="euler: the reference's first-order update; dpmpp_2m: DPM-Solver++(2M), second order at one UNet "
+                        "evaluation per step (its history travels in the latent; the steps run in index order)")
     p.add_argument("--num-samples", type=int, default=1)
     p.add_argument("--latent-frames", type=int, default=14)
     p.add_argument("--latent-height", type=int, default=72)
@@ -57,18 +60,21 @@ def main(argv=None) -> None:
     init_distributed(backend=backend, rank=rank, world_size=world, init_method=args.init_method)
 
     timesteps = StableVideoUNet._default_timestep_schedule(args.total_steps)
-    model = (StableVideoUNet.from_random_init(timesteps, device=device) if args.random_init
-             else StableVideoUNet.from_pretrained(args.model_id, timesteps=timesteps, device=device))
+    model = (StableVideoUNet.from_random_init(timesteps, device=device, sampler=args.sampler) if args.random_init
+             else StableVideoUNet.from_pretrained(args.model_id, timesteps=timesteps, device=device, sampler=args.sampler))
     torch.manual_seed(args.seed)
     model.set_dummy_conditioning(1, args.latent_frames, args.latent_height, args.latent_width, device,
                                  fps=args.fps, motion_bucket_id=args.motion_bucket_id,
                                  noise_aug_strength=args.noise_aug_strength, guidance_scale=args.guidance_scale)
     shape = torch.Size((1, 4, args.latent_frames, args.latent_height, args.latent_width))
-    spec = LatentSpec(shape=shape, dtype=torch.float16, device=device)
+    # what a stage boundary carries: the sample, and with dpmpp_2m the solver's history behind it (8 channels)
+    spec = LatentSpec(shape=torch.Size((1, model.state_channels) + tuple(shape[2:])), dtype=torch.float16, device=device)
+    # Euler keeps the reference's descending list (ref production.py:88); a multistep solver walks the table in index order
+    order = list(range(args.total_steps)) if args.sampler == "dpmpp_2m" else list(range(args.total_steps - 1, -1, -1))
 
     def supplier(i: int) -> torch.Tensor:
         torch.manual_seed(args.seed + i)
-        return torch.randn(shape, device=device, dtype=torch.float16) * model.init_noise_sigma
+        return model.init_state(torch.randn(shape, device=device, dtype=torch.float16) * model.init_noise_sigma)
 
     conditioning_supplier = None
     if args.sample_motion_buckets:
@@ -85,15 +91,14 @@ def main(argv=None) -> None:
 
     try:
         with torch.no_grad():
-            outs = run_pipeline_latents(model, total_steps=args.total_steps,
-                                        timesteps=list(range(args.total_steps - 1, -1, -1)), world_size=world,
+            outs = run_pipeline_latents(model, total_steps=args.total_steps, timesteps=order, world_size=world,
                                         rank=rank, latent_spec=spec, num_samples=args.num_samples,
                                         input_supplier=supplier if rank == 0 else None, balanced=args.balanced,
                                         conditioning_supplier=conditioning_supplier)
         if outs:
             torch.cuda.synchronize(device)
             for i, o in enumerate(outs):
-                LOGGER.info("sample %d final latent norm: %s", i, o.float().norm().item())
+                LOGGER.info("sample %d final latent norm: %s", i, model.sample_of(o).float().norm().item())
     finally:
         finalize_distributed()
 
