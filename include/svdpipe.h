@@ -286,8 +286,8 @@ int sp_attn_temporal_f16(const void *q, const void *k, const void *v, void *o, i
                          int64_t ldk, int64_t ldv, int64_t ldo, int batch, int frames, int64_t hw,
                          int heads, float scale, const void *zero_page, void *stream);
 /* sp_attn_spatial_f16 for LONG rows (csrc/attention_long.hip): same arguments, same results to fp16 rounding.
- * One wave per SIMD with two query blocks; after a warm-up over the workgroup's own tokens and tile 0 (ordinary
- * online softmax) each row's reference is frozen at the maximum seen so far and the remaining K/V tiles run without
+ * Two query blocks per wave, one or two waves per SIMD (sp_attn_long_set_occupancy below); after a warm-up over the
+ * workgroup's own tokens and tile 0 (ordinary online softmax) each row's reference is frozen at the maximum seen so far and the remaining K/V tiles run without
  * row maximum or rescale.  A later score more than 16 (log2 units) above that reference overflows fp16, is detected
  * through the row sum, and the 256-row block is recomputed by sp_attn_spatial_f16's kernel inside the same call, so
  * accuracy never depends on the data (only the time does).  Applies to seq >= 4096 with seq % 256 == 0; every other
@@ -298,6 +298,15 @@ int64_t sp_attn_long_ws_bytes(int batch, int seq, int heads);
 int sp_attn_spatial_long_f16(const void *q, const void *k, const void *v, void *o, int64_t ldq, int64_t ldk,
                              int64_t ldv, int64_t ldo, int batch, int seq, int heads, float scale,
                              const void *zero_page, void *workspace, int64_t workspace_bytes, void *stream);
+/* Test / micro-benchmark hook (no counterpart in the reference): the frozen-reference kernel exists in two
+ * instantiations with identical arithmetic and bit-identical results, "attn_long_kernel<2, 1>" (one wave per SIMD, one
+ * workgroup per CU) and "attn_long_kernel<2, 2>" (256 registers per wave, two workgroups per CU).  occ = 1 or 2 pins
+ * the one sp_attn_spatial_long_f16 launches, 0 restores the library's default.  Process-wide, not thread-safe: set it
+ * before the calls it should affect. */
+int sp_attn_long_set_occupancy(int occ);
+/* Name of the kernel the calling thread's last sp_attn_spatial_long_f16 launched first: one of the two above, or
+ * "attn_spatial_kernel" for a shape it passed on (static string). */
+const char *sp_attn_long_last_kernel(void);
 /* fp8 (OCP e4m3fn) MFMA variant of sp_attn_spatial_f16 for BASELINE config 5 ("fp8 MFMA attention path"; the
  * reference has no fp8 path of its own, its attention is diffusers/xformers behind svd_unet.py:142-199).
  * Same arguments and fp16 inputs/outputs; q/k/v are quantised per call into `workspace` (Q8, K8 row-major,

@@ -4,7 +4,8 @@ them in flight on two HIP streams): the arms alternate for ROUNDS rounds, best a
 usage: ab_forward.py [--lib exp] [--rounds 5] [--steps 6] ARM ARM ...
 ARM = comma-separated settings: env:NAME=VALUE (process environment, e.g. env:SP_GEMM_DBG=256 with --lib exp) or
       unet:ATTR=0|1|INT (attribute of the SVDUNetHIP engine, e.g. unet:fold_groupnorm=0, unet:FF_CHUNK_BYTES=176160768) or
-      route:R=BM (sp_gemm_set_route(R, BM, 0) for the whole forward, e.g. route:2=0 = ping-pong kernels only); "base" = nothing."""
+      route:R=BM (sp_gemm_set_route(R, BM, 0) for the whole forward, e.g. route:2=0 = ping-pong kernels only) or
+      occ:long=N (sp_attn_long_set_occupancy(N): the long-row attention kernel with one or two workgroups per CU); "base" = nothing."""
 import argparse, os, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -38,6 +39,7 @@ def apply(arm):
     for name in [n for n in os.environ if n.startswith("SP_GEMM_")]:
         del os.environ[name]
     hip.load().sp_gemm_set_route(0, 0, 0)
+    hip.load().sp_attn_long_set_occupancy(0)
     if arm == "base":
         return
     for item in arm.split(","):
@@ -47,6 +49,8 @@ def apply(arm):
             os.environ[name] = val
         elif kind == "route":
             hip.load().sp_gemm_set_route(int(name), int(val), 0)
+        elif kind == "occ":
+            hip.load().sp_attn_long_set_occupancy(int(val))
         elif kind == "unet":
             defaults.setdefault(name, getattr(model.unet, name))
             setattr(model.unet, name, bool(int(val)) if val in ("0", "1") else int(val))

@@ -45,6 +45,15 @@
 // every access with alias scopes, the waitcnt pass then knows that the K reads may alias the LDS-DMA in flight and puts
 // s_waitcnt vmcnt(0) at the top of every tile (measured: 2.15 ms instead of 1.5 ms).
 // Host contract: seq a multiple of 256 and >= 4096; everything else goes to attention.hip's kernel.
+//
+// Two instantiations, attn_long_kernel<QB, OCC>.  <2, 1> is the kernel as described above, 256 VGPRs + 25 AGPRs, one
+// workgroup per CU.  <2, 2> is the hardware's own answer to "a lone wave stands still whenever its next instruction
+// waits": the same tile, the same arithmetic and bit-identical results in 256 registers, so that two workgroups (2 x 48 KB
+// of LDS) share a CU and each SIMD has a second wave to issue from.  The steady tile always fitted; the registers came
+// out of the hipcc-scheduled warm-up (its two query blocks run one after the other, V fragments read per block) and out
+// of values that were held across the whole kernel for its last few instructions (they are derived again there).
+// Measured: -10 % kernel time at 28 and 14 x 9,216 x 5, -2.2 % per forward (profiles/attn_long_occupancy_*.txt); it is
+// what sp_attn_spatial_long_f16 launches unless sp_attn_long_set_occupancy(1) asks for the other one.
 #include "common.h"
 
 namespace {
@@ -60,9 +69,20 @@ __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_ex
 // gave up on data where under 1 % of the rows flag, which then cost ~1.1x instead of ~1.0x; with a fraction, scattered
 // failures below 6 % are recomputed block by block and everything else keeps the fast path.
 constexpr unsigned LONG_BAIL_MIN = 64, LONG_BAIL_MAX = 512;   // (512: half of the first round's 1,024 waves on 256 CUs)
+// Two workgroups per CU (OCC = 2) make the first round 512 workgroups = 2,048 waves, and a wave learns that it overflowed
+// from its row sums, i.e. at its end: left alone, all 2,048 would run to the end on data that fails everywhere -- twice
+// the work thrown away, and a flagged-waves word of 2,048 where one round of 256 CUs x 4 waves + the threshold is the
+// bound the tests hold it to.  So that instantiation does not wait for the end: every LONG_LOOK steady tiles a workgroup
+// looks at its row sums (an overflow is sticky: inf and NaN stay) and at the flagged-waves word, and gives its block up
+// as soon as one of its waves has overflowed or the call has reached the threshold.  The threshold stays 512, now a
+// quarter of the round: on all-failing data the waves that overflow inside the first looks reach it, and the others
+// leave at their next look without counting themselves -- the round throws away about half of its 512 workgroups' work,
+// as much as 256 whole ones did.  32 tiles: four looks in a 144-tile row, each one barrier, five LDS words and, in wave
+// 0, one global read; with nothing flagged no cost shows in the A/B (profiles/attn_long_occupancy_ab.txt).
+constexpr int LONG_LOOK = 32;
 
-template <int QB>
-__global__ __launch_bounds__(256, 1) void attn_long_kernel(
+template <int QB, int OCC>
+__global__ __launch_bounds__(256, OCC) void attn_long_kernel(
     const f16 *__restrict__ q, const f16 *__restrict__ k, const f16 *__restrict__ v, f16 *__restrict__ o,
     int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int seq, int heads, float scale_log2e,
     unsigned *__restrict__ flags) {
@@ -70,7 +90,8 @@ __global__ __launch_bounds__(256, 1) void attn_long_kernel(
   constexpr int K_BYTES = KV * 128, STAGE = 2 * K_BYTES, RING = 3;
   constexpr int OWN = 2 * QB;                // K/V tiles that hold this workgroup's own tokens
   constexpr int WARM = OWN + 1;              // + tile 0
-  __shared__ __attribute__((aligned(16))) char smem[RING * STAGE];
+  // (two workgroups per CU: five more words behind the ring for the looks between steady tiles, see LONG_LOOK)
+  __shared__ __attribute__((aligned(16))) char smem[RING * STAGE + (OCC > 1 ? 32 : 0)];
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -216,6 +237,64 @@ __global__ __launch_bounds__(256, 1) void attn_long_kernel(
     const char *sk = smem + buf * STAGE;
     const char *sv = sk + K_BYTES;
 
+    if constexpr (OCC > 1) {
+      // Two waves per SIMD leave each 256 registers, VGPRs and AGPRs together.  The interleaved form below keeps the
+      // scores and the packed probabilities of two blocks at once (~280 registers); here a tile's query blocks run one
+      // after the other, so one set of each is live.  A block's arithmetic does not depend on the other block: every
+      // value is produced by the same operations in the same order as below, only their placement in time differs.
+#pragma unroll
+      for (int qb = 0; qb < QB; ++qb) {
+        f32x16 sc[2];
+        qk(qb, sk, sc);
+        u32x2 vr[2][8];
+        {                                      // V fragments, per block: behind the block's score MFMAs
+          const unsigned va[2] = {(unsigned)(uintptr_t)(const __attribute__((address_space(3))) char *)(sv + vlane0),
+                                  (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char *)(sv + vlane1)};
+#pragma unroll
+          for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+              asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(vr[dt][j]) : "v"(va[dt]), "n"(j * 8 * 128) : "memory");
+          asm volatile("s_waitcnt lgkmcnt(0)"
+                       : "+v"(vr[0][0]), "+v"(vr[0][1]), "+v"(vr[0][2]), "+v"(vr[0][3]), "+v"(vr[0][4]), "+v"(vr[0][5]),
+                         "+v"(vr[0][6]), "+v"(vr[0][7]), "+v"(vr[1][0]), "+v"(vr[1][1]), "+v"(vr[1][2]), "+v"(vr[1][3]),
+                         "+v"(vr[1][4]), "+v"(vr[1][5]), "+v"(vr[1][6]), "+v"(vr[1][7])::"memory");
+        }
+        float mt = fmaxf(fmaxf(sc[0][0], sc[0][1]), sc[0][2]);
+#pragma unroll
+        for (int e = 3; e < 31; e += 2) mt = fmaxf(fmaxf(mt, sc[e >> 4][e & 15]), sc[(e + 1) >> 4][(e + 1) & 15]);
+        mt = fmaxf(mt, sc[1][15]);
+        float ma = mt, mb = mt;
+        asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(ma), "+v"(mb));
+        mt = fmaxf(ma, mb);
+        const float delta = i == 0 ? mt : fmaxf(mt, 0.f);
+        if (__builtin_amdgcn_ballot_w64(delta != 0.f) != 0) {
+          const float alpha = i == 0 ? 1.f : fast_exp2(-delta);
+          lacc[qb][0] *= alpha;
+#pragma unroll
+          for (int e = 0; e < 16; ++e) { oacc[qb][0][e] *= alpha; oacc[qb][1][e] *= alpha; }
+#pragma unroll
+          for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) sc[kt][e] -= delta;
+          m_run[qb] += delta;
+#pragma unroll
+          for (int e = 0; e < 16; ++e) negm[qb][e] = -m_run[qb];
+        }
+        u32x4 pc[2][2];
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+          for (int e = 0; e < 16; e += 2) {
+            const f32x2 p = {fast_exp2(sc[kt][e]), fast_exp2(sc[kt][e + 1])};
+            pc[kt][e >> 3][(e & 7) >> 1] = __builtin_bit_cast(unsigned, __builtin_convertvector(p, f16x2));
+          }
+        pv(qb, pc, vr);
+      }
+      if (i + 2 < ntiles) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      return;
+    }
     f32x16 sacc[2][2];                       // scores of the block in its softmax / of the next block
     u32x4 pw[2][2][2];                       // packed probabilities of the block in its softmax / of the previous block
     qk(0, sk, sacc[0]);
@@ -464,6 +543,10 @@ __global__ __launch_bounds__(256, 1) void attn_long_kernel(
   for (int qb = 0; qb < QB; ++qb)
 #pragma unroll
     for (int s = 0; s < 4; ++s) asm volatile("" : "+v"(qf[qb][s]));
+  if constexpr (OCC > 1) {                   // derived again (lane count, not thread id) instead of held through the warm-up
+    const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    kswz = ((ln & 31) >> 1) & 7; hq = ln >> 5;
+  }
   asm volatile("" : "+v"(koff[0]), "+v"(koff[1]), "+v"(vlane0), "+v"(vlane1), "+v"(kofl[0]), "+v"(kofl[1]), "+v"(vofl[0]),
                "+v"(vofl[1]), "+v"(lsel), "+v"(kswz), "+v"(hq));
   read_k(buf);
@@ -471,7 +554,54 @@ __global__ __launch_bounds__(256, 1) void attn_long_kernel(
   const unsigned long long tc0 = __builtin_amdgcn_s_memtime(), tw0 = wall_clock64();
 #endif
   steady_setup(WARM, buf);
-  for (int i = WARM; i < ntiles; ++i) steady2(i);
+  if constexpr (OCC > 1) {
+    // Two workgroups per CU: every LONG_LOOK tiles the workgroup looks at its own row sums and at the flagged-waves word
+    // (see LONG_BAIL_MAX).  A wave whose sums are no longer finite says so in its word behind the ring, thread 0 puts the
+    // flagged-waves count beside them, and after one barrier all four waves read the same five words and take the same
+    // way: if any wave overflowed, or the call has reached its bail-out threshold, the workgroup stops here -- its block
+    // goes to the second pass whatever it would still compute.  Only waves that overflowed themselves count themselves
+    // (below), once.  The words are written 32 tiles (32 barriers) after they were last read.
+    volatile __attribute__((address_space(3))) unsigned *const look =
+        (volatile __attribute__((address_space(3))) unsigned *)(__attribute__((address_space(3))) char *)(smem + RING * STAGE);
+    bool quit = false;
+    for (int i = WARM; i < ntiles && !quit;) {
+      const int stop = i + LONG_LOOK < ntiles ? i + LONG_LOOK : ntiles;
+      for (; i < stop; ++i) steady2(i);
+      if (i < ntiles) {
+        bool bad = false;
+#pragma unroll
+        for (int qb = 0; qb < QB; ++qb) bad = bad || !(lacc[qb][0] < 3.0e38f);
+        const bool wave_bad = __builtin_amdgcn_ballot_w64(bad) != 0;
+        const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        if (ln == 0) {
+          look[wave] = wave_bad ? 1u : 0u;
+          if (wave == 0)
+            look[4] = __hip_atomic_load(flags + (int64_t)gridDim.x * gridDim.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        const unsigned any_bad = look[0] | look[1] | look[2] | look[3], seen = look[4];
+        const unsigned total_waves = gridDim.x * gridDim.y * 4u;
+        const unsigned frac = total_waves / 16u;
+        const unsigned bail = frac < LONG_BAIL_MIN ? LONG_BAIL_MIN : (frac > LONG_BAIL_MAX ? LONG_BAIL_MAX : frac);
+        quit = __builtin_amdgcn_readfirstlane(any_bad != 0 || seen >= bail);
+      }
+    }
+    if (quit) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // LDS-DMA pieces on their way
+      bool bad = false;
+#pragma unroll
+      for (int qb = 0; qb < QB; ++qb) bad = bad || !(lacc[qb][0] < 3.0e38f);
+      const bool wave_bad = __builtin_amdgcn_ballot_w64(bad) != 0;      // (all lanes vote: in front of the lane-0 branch)
+      const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+      if (ln == 0 && (wave == 0 || wave_bad)) flags[(int64_t)bh * gridDim.x + blockIdx.x] = 1u;
+      if (ln == 0 && wave_bad)
+        __hip_atomic_fetch_add(flags + (int64_t)gridDim.x * gridDim.y, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      return;
+    }
+  } else {
+    for (int i = WARM; i < ntiles; ++i) steady2(i);
+  }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the re-fetched last tile (steady2) is still on its way into LDS
 
 #ifdef LONG_TRACE
@@ -481,11 +611,18 @@ __global__ __launch_bounds__(256, 1) void attn_long_kernel(
 #endif
   // a probability that overflowed fp16 reached the row sum as inf (or NaN): this workgroup's rows are done again by
   // attention.hip's kernel (host entry below); what is stored here for them is overwritten
+  // (two waves per SIMD: the lane's position is derived again here, from the lane count instead of the thread id, so
+  // that neither the id nor the 64-bit row index of the Q loads has to live across the whole kernel for this tail)
+  int lane_t = lane, r_t = r, h_t = h;
+  if constexpr (OCC > 1) {
+    lane_t = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    r_t = lane_t & 31; h_t = lane_t >> 5;
+  }
   {
     bool bad = false;
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb) bad = bad || !(lacc[qb][0] < 3.0e38f);
-    if (__builtin_amdgcn_ballot_w64(bad) != 0 && lane == 0) {
+    if (__builtin_amdgcn_ballot_w64(bad) != 0 && lane_t == 0) {
       flags[(int64_t)bh * gridDim.x + blockIdx.x] = 1u;
       __hip_atomic_fetch_add(flags + (int64_t)gridDim.x * gridDim.y, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -495,7 +632,7 @@ __global__ __launch_bounds__(256, 1) void attn_long_kernel(
 #pragma unroll
   for (int qb = 0; qb < QB; ++qb) {
     const float inv = 1.0f / lacc[qb][0];
-    f16 *op = o + (row0 + q0 + qb * 32 + r) * ldo + hd * 64 + 4 * h;
+    f16 *op = o + (row0 + q0 + qb * 32 + r_t) * ldo + hd * 64 + 4 * h_t;
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
@@ -511,6 +648,10 @@ __global__ __launch_bounds__(256, 1) void attn_long_kernel(
 }  // namespace
 
 constexpr int LONG_QB = 2;
+// Waves per SIMD of the instantiation the host entry launches unless sp_attn_long_set_occupancy says otherwise.
+constexpr int LONG_OCC_DEFAULT = 2;           // (profiles/attn_long_occupancy_forward_ab.txt)
+static int g_long_occ = 0;                     // 0 = LONG_OCC_DEFAULT (sp_attn_long_set_occupancy)
+static thread_local const char *g_long_last = "";
 constexpr int LONG_ROWS = 128 * LONG_QB;       // query rows per workgroup = rows per flag word
 
 // attention.hip: sp_attn_spatial_f16's launcher; with `only_flagged`, 128-row workgroups whose 256-row block has a zero
@@ -526,6 +667,16 @@ extern "C" int64_t sp_attn_long_ws_bytes(int batch, int seq, int heads) {
   return ((int64_t)batch * heads * ((seq + LONG_ROWS - 1) / LONG_ROWS) + 1) * (int64_t)sizeof(unsigned);
 }
 
+// Test / micro-benchmark hook: which instantiation of the frozen-reference kernel sp_attn_spatial_long_f16 launches.
+// 0 = the library's default, 1 = attn_long_kernel<2, 1> (one workgroup per CU), 2 = attn_long_kernel<2, 2> (two).
+extern "C" int sp_attn_long_set_occupancy(int occ) {
+  SP_REQUIRE(occ >= 0 && occ <= 2, "sp_attn_long_set_occupancy: occ %d (0 default, 1 or 2 waves per SIMD)", occ);
+  g_long_occ = occ;
+  return SP_OK;
+}
+// what the calling thread's last sp_attn_spatial_long_f16 launched first
+extern "C" const char *sp_attn_long_last_kernel(void) { return g_long_last; }
+
 // Spatial self-attention, same contract as sp_attn_spatial_f16 and the same results to fp16 rounding, through the
 // frozen-reference kernel where it applies (seq >= 4096 and a multiple of 256) and through sp_attn_spatial_f16's kernel
 // otherwise.  `workspace` (>= sp_attn_long_ws_bytes, 4-byte aligned, private to this call until it completes on
@@ -535,9 +686,11 @@ extern "C" int sp_attn_spatial_long_f16(const void *q, const void *k, const void
                                         const void *zero_page, void *workspace, int64_t workspace_bytes, void *stream) {
   SP_REQUIRE(q && k && v && o && zero_page, "sp_attn_spatial_long_f16: null pointer");
   SP_REQUIRE(batch > 0 && seq > 0 && heads > 0, "sp_attn_spatial_long_f16: batch/seq/heads must be positive");
-  if (!(seq >= 4096 && seq % LONG_ROWS == 0))
+  if (!(seq >= 4096 && seq % LONG_ROWS == 0)) {
+    g_long_last = "attn_spatial_kernel";
     return sp_attn_spatial_launch(q, k, v, o, ldq, ldk, ldv, ldo, batch, seq, heads, scale, zero_page, nullptr, stream,
                                   "sp_attn_spatial_long_f16");
+  }
   SP_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 4 == 0,
              "sp_attn_spatial_long_f16: strides must be multiples of 8");
   SP_REQUIRE((int64_t)batch * heads <= 65535, "sp_attn_spatial_long_f16: batch*heads too large");
@@ -556,9 +709,17 @@ extern "C" int sp_attn_spatial_long_f16(const void *q, const void *k, const void
     return SP_ELAUNCH;
   }
   SP_CLEAR_STALE_ERROR();
-  hipLaunchKernelGGL(attn_long_kernel<LONG_QB>, dim3(seq / LONG_ROWS, batch * heads), dim3(256), 0, s, (const f16 *)q,
-                     (const f16 *)k, (const f16 *)v, (f16 *)o, ldq, ldk, ldv, ldo, seq, heads, scale * 1.4426950408889634f,
-                     flags);
+  const dim3 grid(seq / LONG_ROWS, batch * heads);
+  const float scale_log2e = scale * 1.4426950408889634f;
+  if ((g_long_occ ? g_long_occ : LONG_OCC_DEFAULT) == 2) {
+    g_long_last = "attn_long_kernel<2, 2>";
+    hipLaunchKernelGGL((attn_long_kernel<LONG_QB, 2>), grid, dim3(256), 0, s, (const f16 *)q, (const f16 *)k, (const f16 *)v,
+                       (f16 *)o, ldq, ldk, ldv, ldo, seq, heads, scale_log2e, flags);
+  } else {
+    g_long_last = "attn_long_kernel<2, 1>";
+    hipLaunchKernelGGL((attn_long_kernel<LONG_QB, 1>), grid, dim3(256), 0, s, (const f16 *)q, (const f16 *)k, (const f16 *)v,
+                       (f16 *)o, ldq, ldk, ldv, ldo, seq, heads, scale_log2e, flags);
+  }
   SP_CHECK_LAUNCH("sp_attn_spatial_long_f16");
   // second look at the blocks whose reference turned out too low: the ordinary kernel, flagged blocks only
   return sp_attn_spatial_launch(q, k, v, o, ldq, ldk, ldv, ldo, batch, seq, heads, scale, zero_page, flags, stream,

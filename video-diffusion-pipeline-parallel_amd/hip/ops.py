@@ -318,6 +318,16 @@ def attn_spatial_long(q, k, v, o, workspace, *, ldq, ldk, ldv, ldo, batch, seq, 
     return o
 
 
+def attn_long_set_occupancy(occ: int) -> None:
+    """Pins the instantiation attn_spatial_long launches (1 or 2 workgroups per CU; 0 = the library's default):
+    ``sp_attn_long_set_occupancy`` in include/svdpipe.h.  Tests and micro-benchmarks only."""
+    _check(load().sp_attn_long_set_occupancy(occ), "sp_attn_long_set_occupancy")
+
+
+def attn_long_last_kernel() -> str:
+    return load().sp_attn_long_last_kernel().decode()
+
+
 def attn_fp8_ws_bytes(batch, seq, heads) -> int:
     return int(load().sp_attn_fp8_ws_bytes(batch, seq, heads))
 
