@@ -157,6 +157,15 @@ def test_lzw_stage_is_byte_exact_on_the_corners_of_the_coder():
     check_lzw(gm.noise_indices(1, 4200, 8, levels=3)[None], 16, "one long row, three levels")
 
 
+def test_lzw_stage_carries_the_bit_offsets_past_256_strips():
+    # 300 strips of one pixel row: the scan over the strips' bit counts takes a second round of 256, which starts from the
+    # first's sum
+    indices = gm.noise_indices(300, 1, 17)[None]
+    _, strips = gm.lzw_image_data(indices[0], 1)
+    assert indices.shape == (1, 300, 1) and len(strips) == 300
+    check_lzw(indices, 1, "300 strips")
+
+
 def test_stream_bound_holds_and_is_what_the_header_derives():
     from vdpp_amd.hip import ops
     entries = gm.TABLE_END - gm.FIRST_FREE

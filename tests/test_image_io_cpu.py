@@ -143,6 +143,53 @@ def test_save_frames_refuses_what_it_cannot_write(tmp_path):
         save_frames(_frames().astype(np.float32), str(tmp_path / "v.gif"))
 
 
+@pytest.fixture
+def host_encoders(monkeypatch):
+    """The four frame encoders built for 16 x 24 frames with the device check replaced: what they refuse, they refuse before
+    anything is launched."""
+    import torch
+    from vdpp_amd.models import common, image_io
+    monkeypatch.setattr(common, "hip_device", lambda device, engine: torch.device(device))
+    return [cls("cpu", 16, 24) for cls in (image_io.JpegEncoder, image_io.GifEncoder, image_io.PngEncoder, image_io.WebpEncoder)]
+
+
+def test_encoders_refuse_other_frames_with_one_message(host_encoders):
+    import torch
+    good = torch.zeros((2, 16, 24, 3), dtype=torch.uint8)
+    cases = ((good.float(), "torch.float32 (2, 16, 24, 3)"), (good[0], "torch.uint8 (16, 24, 3)"),
+             (good[:, :, :23], "torch.uint8 (2, 16, 23, 3)"), (good[:, :15], "torch.uint8 (2, 15, 24, 3)"),
+             (torch.zeros((2, 16, 24, 4), dtype=torch.uint8), "torch.uint8 (2, 16, 24, 4)"),
+             (good[:0], "torch.uint8 (0, 16, 24, 3)"), (good.numpy(), "uint8 (2, 16, 24, 3)"), ([[1, 2, 3]], "<class 'list'> ()"))
+    for enc in host_encoders:
+        for frames, got in cases:
+            with pytest.raises(ValueError) as refused:
+                enc.enqueue(frames)
+            assert str(refused.value) == f"frames must be a (F, 16, 24, 3) uint8 tensor; got {got}", type(enc).__name__
+        for name in ("encode",) + (("enqueue_files", "encode_apng") if hasattr(enc, "encode_apng") else ()) \
+                + (("encode_animation",) if hasattr(enc, "encode_animation") else ()):
+            with pytest.raises(ValueError, match="frames must be a"):
+                getattr(enc, name)(good.float())
+
+
+def test_write_apng_and_the_device_route_refuse_the_same_fps(host_encoders):
+    from vdpp_amd.models.image_io import write_apng
+    png = host_encoders[2]
+    for fps in (0, -1, 0.0, float("nan"), True, "7", None, 1e-6, 1 / 70000):
+        with pytest.raises(ValueError) as host:
+            write_apng(None, [b"x"], 24, 16, fps)
+        with pytest.raises(ValueError) as device:
+            png.enqueue_apng(None, fps)                      # (the delay is worked out before the frames are looked at)
+        if "delay" in str(device.value):
+            assert str(device.value) == f"a delay of 1 / {fps} s does not fit the frame control chunk"
+            assert str(host.value) == "write_apng: " + str(device.value)
+        else:
+            assert str(host.value) == str(device.value) == f"fps must be a positive number; got {fps!r}"
+    for fps in (7, 12.5, 1 / 3, 1 / 65535, 65535, np.float32(24)):
+        assert write_apng(None, [b"x"], 24, 16, fps)[:8] == b"\x89PNG\r\n\x1a\n"
+        with pytest.raises(ValueError, match="frames must be a"):
+            png.enqueue_apng(None, fps)
+
+
 def test_generate_mode_names_and_flags():
     from vdpp_amd.modes import generate
     assert generate.sample_output_path("out.gif", 0, 1) == "out.gif"

@@ -205,6 +205,16 @@ def test_entropy_stage_is_bit_exact_on_the_corners_of_the_coder():
     assert jm.CODES[2][0x0A][1] + 10 == 26 and jm.CODES[0][11][1] + 11 == 20       # the luminance block reaches the bound
 
 
+def test_entropy_stage_carries_the_offsets_past_256_intervals():
+    # one MCU row of 300 MCUs, an interval each: the scan over the intervals' lengths takes a second round of 256, which starts
+    # from the first's sum; RSTm runs through 0 .. 7 many times
+    coef = jm.coefficients(jm.scene_frames(1, 16, 4800, seed=31), 90)[0]
+    assert coef.shape[:3] == (1, 1, 300)
+    want, _ = jm.entropy_segment(coef[0], 1)
+    assert [want.count(bytes([0xFF, 0xD0 + m])) >= 37 for m in range(8)] == [True] * 8
+    check_entropy(coef, 1, "300 intervals")
+
+
 # ---------------------------------------------------------------------------------------------------- whole path
 def pillow_jpeg(frame, quality):
     from PIL import Image

@@ -166,6 +166,17 @@ def test_deflate_stage_is_byte_exact_on_the_corners_of_the_coder():
         check_deflate(rows_of(long_runs, 700), strip_rows, "long runs")
 
 
+def test_deflate_stage_carries_the_bit_offsets_past_256_strips():
+    # 300 strips of one row: the scan over the strips' bit counts takes a second round of 256, which starts from the first's sum
+    filtered = pm.filter_frames(pm.noise_frames(1, 300, 1, 11))
+    assert filtered.shape == (1, 300, 4)
+    want, strips = pm.deflate_stream(filtered[0], 1)
+    ends = {(s["start_bit"] + s["bits"]) % 8 for s in strips}
+    assert len(strips) == 300 and len(ends) >= 3, f"300 strips that end on mixed bit phases: {len(strips)}, {sorted(ends)}"
+    assert zlib.decompress(want) == filtered[0].tobytes()
+    check_deflate(filtered, 1, "300 strips", want=[want])
+
+
 def test_stream_bound_holds_and_is_what_the_header_derives():
     from vdpp_amd.hip import ops
     assert pm.HEADER_BITS_MAX == 3 + 14 + 19 * 3 + 288 * 14 == 4106

@@ -115,6 +115,27 @@ def test_animation_equals_write_apng_and_nothing_beyond_it_is_written(shape, kin
         assert abs(info.get("duration") - 1000.0 / FPS[-1]) < 1e-6
 
 
+def test_more_frames_than_threads_follow_one_another():
+    # 260 frames of one pixel: the scan over the chunk sizes takes a second round of 256, which starts from the first's sum,
+    # and the stills' loop a second turn
+    from vdpp_amd.models.image_io import png_file, write_apng
+    shape, kind = (260, 1, 1), "noise"
+    streams = list(streams_of(shape, kind)[2])
+    data, file_len = wrap(shape, kind, True)
+    want = write_apng(None, streams, 1, 1, 7)
+    assert want == pm.apng_file(streams, 1, 1, 7)
+    assert file_len[0] == len(want) and np.all(file_len[1:] == -1)
+    got = data[:file_len[0]].tobytes()
+    assert got == want, f"260 frames: first difference at byte {first_difference(got, want)} of {len(want)}"
+    assert np.all(data[file_len[0]:] == FILL), "260 frames: bytes beyond the file were written"
+    files, file_len = wrap(shape, kind, False)
+    for i in range(260):
+        want = png_file(1, 1, streams[i])
+        got = files[i, :file_len[i]].tobytes()
+        assert got == want, f"still {i} of 260: first difference at byte {first_difference(got, want)} of {len(want)}"
+        assert np.all(files[i, file_len[i]:] == FILL), f"still {i} of 260: bytes beyond the file were written"
+
+
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
 def test_encoder_routes_give_the_same_bytes_call_after_call(shape):
     from vdpp_amd.models.image_io import PNG_ASSEMBLE, PngEncoder

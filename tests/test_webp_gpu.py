@@ -217,6 +217,15 @@ def test_coder_stage_is_byte_exact_on_the_corners_of_the_coder():
     assert np.array_equal(decode(wm.webp_file(got[0]))[2][0], wm.untransform(0, tall[1][0], tall[2][0], 2))
 
 
+def test_coder_stage_carries_the_bit_offsets_past_256_segments():
+    # 130 strips of 4 rows: 2 + 2 * 130 = 262 segments, so the scan over their bit counts takes a second round of 256, which
+    # starts from the first's sum
+    narrow = plain(np.random.default_rng(12).integers(0, 256, (520, 1, 3)).astype(np.uint8))
+    rec = wm.encode_residual(520, 1, 0, narrow[1][0], narrow[2][0], 2, 2)[1]
+    assert len(rec["strips"]) == 130
+    check_code(*narrow, 2, 2, "262 segments")
+
+
 def test_stream_bound_holds_and_is_what_the_header_derives():
     from vdpp_amd.hip import ops
     assert wm.GROUP_HEADER_MAX == 3983 + 2 * 3647 + 8 == 11285 and wm.SUB_HEADER_MAX == 3983 + 3647 + 4 + 11 + 4 == 7649

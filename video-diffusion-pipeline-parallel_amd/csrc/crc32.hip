@@ -18,12 +18,9 @@
 //   crc32_fold_kernel : a workgroup per row multiplies every span's register up to the row's end, XORs them and complements.
 // Spans behind a row's length leave at once: the grid is sized by the pitch, which the host knows, and not by the lengths,
 // which it does not.
-#include "common.h"
+#include "codec_common.h"
 
 namespace {
-
-typedef unsigned char u8;
-typedef unsigned int u32;
 
 constexpr u32 POLY = 0xEDB88320u;
 constexpr int PIECE = 64, PIECE_WORDS = PIECE / 4, PIECE_STRIDE = PIECE_WORDS + 1;

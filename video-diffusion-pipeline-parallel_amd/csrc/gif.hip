@@ -28,13 +28,9 @@
 //                      the strip's end takes its high bits from the head of the next strip), each at j + 2 + j / 255, and the
 //                      length byte in front of every 255th.
 // Nothing here is tuned beyond its layout; profiles/gif_timing.txt has what it costs.
-#include "common.h"
+#include "codec_common.h"
 
 namespace {
-
-typedef unsigned char u8;
-typedef unsigned int u32;
-typedef unsigned long long u64;
 
 constexpr int BINS = 32 * 32 * 32;
 constexpr int SV = 33, SVN = SV * SV * SV;
@@ -47,7 +43,6 @@ constexpr int LZW_CLEAR = 256, LZW_EOI = 257, LZW_FIRST = 258, LZW_END = 4096;
 constexpr int LZW_SLOTS = 8192, LZW_CHUNK = 1024;
 constexpr int LZW_ENTRIES = LZW_END - LZW_FIRST;          // 3838 codes fill the table
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 bool gif_dims_ok(int h, int w) { return h > 0 && w > 0 && h <= 65535 && w <= 65535 && (int64_t)h * w <= MAX_PIXELS; }
 
 // ---------------------------------------------------------------------------------------------- pixels, four at a time
@@ -401,40 +396,16 @@ __global__ __launch_bounds__(256) void gif_scan_kernel(const int *__restrict__ b
                                                        int *__restrict__ data_bytes, u8 *__restrict__ out, int64_t cap,
                                                        int *__restrict__ out_len) {
   __shared__ int wave_tot[4];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int64_t f = blockIdx.x;
-  int running = 0;
-  for (int k0 = 0; k0 < strips; k0 += 256) {
-    const int k = k0 + tid;
-    const int v = k < strips ? bits[f * strips + k] : 0;
-    int incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int up = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += up;
-    }
-    __syncthreads();
-    if (lane == 63) wave_tot[wv] = incl;
-    __syncthreads();
-    int before = running;
-    for (int i = 0; i < wv; ++i) before += wave_tot[i];
-    if (k < strips) offs[f * strips + k] = before + incl - v;
-    running += wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
-  }
-  if (tid == 0) {
+  const int running = carried_exclusive_sum(
+      wave_tot, strips, 0, [&](int k) { return bits[f * strips + k]; }, [&](int k, int before) { offs[f * strips + k] = before; });
+  if (threadIdx.x == 0) {
     const int nbytes = (running + 7) >> 3, blocks = (nbytes + 254) / 255;
     data_bytes[f] = nbytes;
     out[f * cap] = 8;
     out[f * cap + 1 + nbytes + blocks] = 0;
     out_len[f] = 2 + nbytes + blocks;
   }
-}
-
-__device__ __forceinline__ u32 bits8(const u32 *__restrict__ words, int p) {
-  const int wd = p >> 5, sh = p & 31;
-  u32 v = words[wd] >> sh;
-  if (sh > 24) v |= words[wd + 1] << (32 - sh);
-  return v & 255u;
 }
 
 // grid: one workgroup of 256 per (frame, strip)

@@ -21,12 +21,9 @@
 //   jpeg_scan_kernel      : per frame, the exclusive sum of (interval length + 2 marker bytes) -> offsets, and out_len.
 //   jpeg_place_kernel     : one workgroup per interval copies it to its place in the frame's slot and appends RSTm.
 // Nothing here is tuned beyond its layout; profiles/jpeg_timing.txt has what it costs.
-#include "common.h"
+#include "codec_common.h"
 
 namespace {
-
-typedef unsigned char u8;
-typedef unsigned int u32;
 
 // ITU-T T.81 Annex K.1 (natural order)
 #define JPEG_LUMA_BASE                                                                                                       \
@@ -307,12 +304,7 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const int16_t *__restr
     const int16_t *mine = (const int16_t *)&cs[lane * BLOCK_PITCH];
     const u32 *dc_tab = tabs[comp >= 4 ? 1 : 0], *ac_tab = tabs[comp >= 4 ? 3 : 2];
     const int nbits = live ? code_block<false>(mine, pred, dc_tab, ac_tab, nullptr, 0) : 0;
-    int incl = nbits;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int up = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += up;
-    }
+    const int incl = wave_inclusive_sum(nbits);
     int total = carry_bits + __shfl(incl, 63, 64);
     for (int i = lane; i <= (total >> 5); i += 64) bits[i] = i == 0 ? carry_byte << 24 : 0u;
     __syncthreads();
@@ -346,27 +338,10 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const int16_t *__restr
 __global__ __launch_bounds__(256) void jpeg_scan_kernel(const int *__restrict__ lens, int n_int, int *__restrict__ offs,
                                                         int *__restrict__ out_len) {
   __shared__ int wave_tot[4];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int64_t f = blockIdx.x;
-  int running = 0;
-  for (int k0 = 0; k0 < n_int; k0 += 256) {
-    const int k = k0 + tid;
-    const int v = k < n_int ? lens[f * n_int + k] + 2 : 0;
-    int incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int up = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += up;
-    }
-    __syncthreads();
-    if (lane == 63) wave_tot[wv] = incl;
-    __syncthreads();
-    int before = running;
-    for (int i = 0; i < wv; ++i) before += wave_tot[i];
-    if (k < n_int) offs[f * n_int + k] = before + incl - v;
-    running += wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
-  }
-  if (tid == 0) out_len[f] = running - 2;
+  const int running = carried_exclusive_sum(
+      wave_tot, n_int, 0, [&](int k) { return lens[f * n_int + k] + 2; }, [&](int k, int before) { offs[f * n_int + k] = before; });
+  if (threadIdx.x == 0) out_len[f] = running - 2;
 }
 
 __global__ __launch_bounds__(256) void jpeg_place_kernel(const u8 *__restrict__ stage, int64_t slot_bytes,
@@ -387,7 +362,6 @@ __global__ __launch_bounds__(256) void jpeg_place_kernel(const u8 *__restrict__ 
 
 bool jpeg_dims_ok(int h, int w) { return h > 0 && w > 0 && h <= 65535 && w <= 65535; }
 int64_t jpeg_intervals(int64_t mcus, int restart_mcus) { return (mcus + restart_mcus - 1) / restart_mcus; }
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace
 

@@ -11,11 +11,11 @@
 //                        bytes ahead (the chunk has that halo): at distance k >= 1 from the run's start, j = k - 1, a token
 //                        starts where j % 258 == 0 (a match of the bytes ahead, capped at 258, if they are at least 3, else a
 //                        literal) and where j % 258 == 1 and the run ends here (the second literal of a remainder of 2).
-//                        First pass: histogram by LDS atomics and the Adler-32 partials.  Then the code: a rank sort by
-//                        (count, symbol) by all threads, the two-queue merge and the depths by one thread (at most 285 joins),
-//                        the halving loop around both; canonical codes; the run-length form of the lengths and the 19-symbol
-//                        code by the same builder; the header bits by one thread.  Second pass: bits per token, a prefix sum,
-//                        and every token ORed into an LDS image of the chunk's words, which then goes to the strip's staging
+//                        First pass: histogram by LDS atomics and the Adler-32 partials.  Then the code (codec_common.h):
+//                        a rank sort by (count, symbol) by all threads, the two-queue merge and the depths by one thread (at
+//                        most 285 joins), the halving loop around both; canonical codes; the run-length form of the lengths
+//                        and the 19-symbol code by the same builder; the header bits by one thread.  Second pass: bits per
+//                        token, a prefix sum, and every token ORed into an LDS image of the chunk's words, which then goes to the strip's staging
 //                        slot in whole words.
 //   png_scan_kernel    : per frame the exclusive sum of the strips' bit counts, the byte count, 78 9C in front, the Adler-32
 //                        folded from the strips' partials behind, out_len.
@@ -28,14 +28,9 @@
 //   png_copy_kernel    : a workgroup per 16 KiB of a stream: the stream to its place in whole words of the destination, the
 //                        CRC behind it.
 // Nothing here is tuned beyond its layout; profiles/png_timing.txt has what it costs.
-#include "common.h"
+#include "codec_common.h"
 
 namespace {
-
-typedef unsigned char u8;
-typedef unsigned short u16;
-typedef unsigned int u32;
-typedef unsigned long long u64;
 
 constexpr int MAX_PIXELS = 1 << 24;
 constexpr int NSYM = 286, NCL = 19, END_OF_BLOCK = 256;
@@ -49,7 +44,6 @@ __constant__ u16 LEN_BASE[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23
 __constant__ u8 LEN_EXTRA[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
 __constant__ u8 CL_ORDER[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 bool png_dims_ok(int h, int w) { return h > 0 && w > 0 && h <= 65535 && w <= 65535 && (int64_t)h * w <= MAX_PIXELS; }
 
 // ---------------------------------------------------------------------------------------------- filter
@@ -57,11 +51,6 @@ __device__ __forceinline__ int paeth(int a, int b, int c) {
   const int p = a + b - c, pa = abs(p - a), pb = abs(p - b), pc = abs(p - c);
   return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
 }
-__device__ __forceinline__ u32 cost(int v) {
-  v &= 255;
-  return (u32)min(v, 256 - v);
-}
-
 // grid: one workgroup of 256 per row of every frame
 __global__ __launch_bounds__(256) void png_filter_kernel(const u8 *__restrict__ frames, int h, int w, u8 *__restrict__ filtered) {
   __shared__ u32 red[4][5];
@@ -75,11 +64,11 @@ __global__ __launch_bounds__(256) void png_filter_kernel(const u8 *__restrict__ 
   u32 s[5] = {0, 0, 0, 0, 0};
   for (int i = tid; i < n; i += 256) {
     const int x = cur[i], a = i >= 3 ? cur[i - 3] : 0, b = top ? 0 : up[i], c = (top || i < 3) ? 0 : up[i - 3];
-    s[0] += cost(x);
-    s[1] += cost(x - a);
-    s[2] += cost(x - b);
-    s[3] += cost(x - ((a + b) >> 1));
-    s[4] += cost(x - paeth(a, b, c));
+    s[0] += byte_cost(x);
+    s[1] += byte_cost(x - a);
+    s[2] += byte_cost(x - b);
+    s[3] += byte_cost(x - ((a + b) >> 1));
+    s[4] += byte_cost(x - paeth(a, b, c));
   }
 #pragma unroll
   for (int k = 0; k < 5; ++k) {
@@ -107,116 +96,12 @@ __global__ __launch_bounds__(256) void png_filter_kernel(const u8 *__restrict__ 
   }
 }
 
-// ---------------------------------------------------------------------------------------------- code construction
-struct Builder {
-  u32 cnt[NSYM];
-  u16 order[NSYM];                      // sorted place -> symbol
-  u32 weight[2 * NSYM];                 // the leaves in sorted order, then the joined nodes in order of their making
-  u16 parent[2 * NSYM];
-  u16 depth[2 * NSYM];
-  u32 next_code[17];
-  int leaves, deepest;
-};
-
-// Code lengths of B.cnt[0 .. nsym) into len[0 .. nsym), by every thread of the workgroup.  B.cnt is changed.
-__device__ void build_lengths(Builder &B, int nsym, int limit, u8 *len) {
-  const int tid = threadIdx.x;
-  __syncthreads();
-  if (tid == 0) {
-    int used = 0;
-    for (int s = 0; s < nsym; ++s) used += B.cnt[s] != 0;
-    for (int s = 0; used < 2 && s < nsym; ++s)
-      if (!B.cnt[s]) { B.cnt[s] = 1; ++used; }
-  }
-  for (;;) {
-    __syncthreads();
-    for (int s = tid; s < nsym; s += 256) {
-      const u32 c = B.cnt[s];
-      len[s] = 0;
-      if (c) {
-        int r = 0;
-        for (int t = 0; t < nsym; ++t) {
-          const u32 ct = B.cnt[t];
-          r += (ct != 0 && (ct < c || (ct == c && t < s))) ? 1 : 0;
-        }
-        B.order[r] = (u16)s;
-        B.weight[r] = c;
-      }
-    }
-    __syncthreads();
-    if (tid == 0) {
-      int L = 0;
-      for (int s = 0; s < nsym; ++s) L += B.cnt[s] != 0;
-      int i = 0, j = 0;                                     // the next leaf, the next joined node
-      for (int m = 0; m < L - 1; ++m) {
-        int pick[2];
-        for (int k = 0; k < 2; ++k) {                       // (equal weights: the leaf, which is older)
-          if (i < L && (j >= m || B.weight[i] <= B.weight[L + j])) pick[k] = i++;
-          else pick[k] = L + j++;
-        }
-        B.weight[L + m] = B.weight[pick[0]] + B.weight[pick[1]];
-        B.parent[pick[0]] = (u16)(L + m);
-        B.parent[pick[1]] = (u16)(L + m);
-      }
-      B.depth[2 * L - 2] = 0;
-      for (int node = 2 * L - 3; node >= L; --node) B.depth[node] = B.depth[B.parent[node]] + 1;
-      B.leaves = L;
-      B.deepest = 0;
-    }
-    __syncthreads();
-    const int L = B.leaves;
-    int deepest = 0;
-    for (int i = tid; i < L; i += 256) {
-      const int d = B.depth[B.parent[i]] + 1;
-      len[B.order[i]] = (u8)min(d, 255);
-      deepest = max(deepest, d);
-    }
-    if (deepest) atomicMax(&B.deepest, deepest);
-    __syncthreads();
-    if (B.deepest <= limit) break;
-    for (int s = tid; s < nsym; s += 256) {
-      const u32 c = B.cnt[s];
-      B.cnt[s] = c ? (c + 1) >> 1 : 0;
-    }
-  }
-  __syncthreads();
-}
-
-// RFC 1951 3.2.2, bit-reversed for the LSB-first packing
-__device__ void canonical_codes(Builder &B, int nsym, const u8 *len, u16 *code) {
-  const int tid = threadIdx.x;
-  __syncthreads();
-  if (tid == 0) {
-    u32 count[17];
-    for (int b = 0; b < 17; ++b) count[b] = 0;
-    for (int s = 0; s < nsym; ++s) ++count[len[s]];
-    count[0] = 0;
-    u32 c = 0;
-    B.next_code[0] = 0;
-    for (int b = 1; b < 17; ++b) {
-      c = (c + count[b - 1]) << 1;
-      B.next_code[b] = c;
-    }
-  }
-  __syncthreads();
-  for (int s = tid; s < nsym; s += 256) {
-    const int n = len[s];
-    u32 c = 0;
-    if (n) {
-      c = B.next_code[n];
-      for (int t = 0; t < s; ++t) c += len[t] == n ? 1 : 0;
-      c = __brev(c) >> (32 - n);
-    }
-    code[s] = (u16)c;
-  }
-  __syncthreads();
-}
-
 // ---------------------------------------------------------------------------------------------- the strip
+// (the code construction, HuffBuilder and what works on it, is in codec_common.h)
 struct Strip {
   __align__(16) u8 buf[16 + CHUNK + HALO + 12];   // [15]: the byte before the chunk; [16 ..): the chunk and its halo
   u32 obuf[OWORDS];
-  Builder B;
+  HuffBuilder<NSYM> B;
   u32 lentab[256];                      // match length - 3 -> length code index | extra bits << 8 | extra value << 16
   u8 len[NSYM];
   u16 code[NSYM];
@@ -294,54 +179,6 @@ __device__ __forceinline__ void chunk_tokens(Strip &S, int c0, int total, int (&
   }
 }
 
-// exclusive sum of v over the workgroup; total in `all`
-__device__ __forceinline__ int block_exclusive_sum(Strip &S, int v, int &all) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  int incl = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int up = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += up;
-  }
-  __syncthreads();
-  if (lane == 63) S.wave_val[wv] = incl;
-  __syncthreads();
-  int before = 0;
-  for (int i = 0; i < wv; ++i) before += S.wave_val[i];
-  all = S.wave_val[0] + S.wave_val[1] + S.wave_val[2] + S.wave_val[3];
-  return before + incl - v;
-}
-
-// one thread: zlib's scan of len[0 .. n) appended to S.seq, counts into B.cnt
-__device__ void run_length_form(Strip &S, const u8 *len, int n) {
-  int prev = -1, count = 0, nxt = len[0];
-  int max_count = nxt == 0 ? 138 : 7, min_count = nxt == 0 ? 3 : 4;
-  auto emit = [&](int sym, int value) {
-    S.seq[S.nseq++] = (u16)(sym | (value << 5));
-    ++S.B.cnt[sym];
-  };
-  for (int i = 0; i < n; ++i) {
-    const int cur = nxt;
-    nxt = i + 1 < n ? len[i + 1] : -1;
-    if (++count < max_count && cur == nxt) continue;
-    if (count < min_count) {
-      for (int k = 0; k < count; ++k) emit(cur, 0);
-    } else if (cur != 0) {
-      if (cur != prev) { emit(cur, 0); --count; }
-      emit(16, count - 3);
-    } else if (count <= 10) {
-      emit(17, count - 3);
-    } else {
-      emit(18, count - 11);
-    }
-    count = 0;
-    prev = cur;
-    if (nxt == 0) { max_count = 138; min_count = 3; }
-    else if (cur == nxt) { max_count = 6; min_count = 3; }
-    else { max_count = 7; min_count = 4; }
-  }
-}
-
 // grid: one workgroup of 256 per (frame, strip)
 __global__ __launch_bounds__(256) void png_deflate_kernel(const u8 *__restrict__ filtered, int h, int pitch, int strip_rows, int strips,
                                                           u8 *__restrict__ stage, int64_t slot_bytes, int *__restrict__ bits_out,
@@ -406,7 +243,7 @@ __global__ __launch_bounds__(256) void png_deflate_kernel(const u8 *__restrict__
     while (S.len[nlit - 1] == 0) --nlit;                     // (>= 257: end-of-block has a code)
     S.nlit = nlit;
     S.nseq = 0;
-    run_length_form(S, S.len, nlit);
+    run_length_form(S.seq, S.nseq, S.B.cnt, S.len, nlit);
     S.seq[S.nseq++] = 1; S.seq[S.nseq++] = 1;               // the distance code: two lengths of 1, too few for a repeat
     S.B.cnt[1] += 2;
   }
@@ -414,12 +251,7 @@ __global__ __launch_bounds__(256) void png_deflate_kernel(const u8 *__restrict__
   canonical_codes(S.B, NCL, S.cl_len, S.cl_code);
   if (tid == 0) {
     int at = 0;
-    auto put = [&](u32 value, int width) {
-      if (width == 0) return;
-      S.obuf[at >> 5] |= value << (at & 31);
-      if ((at & 31) + width > 32) S.obuf[(at >> 5) + 1] |= value >> (32 - (at & 31));
-      at += width;
-    };
+    auto put = [&](u32 value, int width) { put_bits(S.obuf, at, value, width); };
     int ncl = NCL;
     while (ncl > 4 && S.cl_len[CL_ORDER[ncl - 1]] == 0) --ncl;
     put(s + 1 == strips ? 1u : 0u, 1);
@@ -465,7 +297,7 @@ __global__ __launch_bounds__(256) void png_deflate_kernel(const u8 *__restrict__
       mine += width;
     }
     int all;
-    int at = running + block_exclusive_sum(S, mine, all);
+    int at = running + block_exclusive_sum(S.wave_val, mine, all);
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
       const int width = (int)(word[i] >> 24);
@@ -490,11 +322,9 @@ __global__ __launch_bounds__(256) void png_deflate_kernel(const u8 *__restrict__
     __syncthreads();
   }
   if (tid == 0) {
-    const u32 bits = S.code[END_OF_BLOCK];
-    const int width = S.len[END_OF_BLOCK], k = (running >> 5) - wbase, sh = running & 31;
-    S.obuf[k] |= bits << sh;
-    if (sh + width > 32) S.obuf[k + 1] |= bits >> (32 - sh);
-    bits_out[bid] = running + width;
+    int at = running - 32 * wbase;                           // (obuf[0] is word wbase of the stream)
+    put_bits(S.obuf, at, S.code[END_OF_BLOCK], S.len[END_OF_BLOCK]);
+    bits_out[bid] = running + S.len[END_OF_BLOCK];
   }
   running += S.len[END_OF_BLOCK];
   __syncthreads();
@@ -508,36 +338,21 @@ __global__ __launch_bounds__(256) void png_scan_kernel(const int *__restrict__ b
                                                        u8 *__restrict__ out, int64_t cap, int *__restrict__ out_len) {
   __shared__ int wave_tot[4];
   __shared__ u64 fold_a, fold_b;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int tid = threadIdx.x;
   const int64_t f = blockIdx.x;
   const int64_t whole = (int64_t)h * pitch;
   if (tid == 0) { fold_a = 0; fold_b = 0; }
-  int running = 0;
   u64 a_sum = 0, b_sum = 0;
-  for (int k0 = 0; k0 < strips; k0 += 256) {
-    const int k = k0 + tid;
-    const int v = k < strips ? bits[f * strips + k] : 0;
-    int incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int up = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += up;
-    }
-    __syncthreads();
-    if (lane == 63) wave_tot[wv] = incl;
-    __syncthreads();
-    int before = running;
-    for (int i = 0; i < wv; ++i) before += wave_tot[i];
-    if (k < strips) {
-      offs[f * strips + k] = before + incl - v;
-      // a byte of strip k counts, beyond its place in the strip, once per byte behind the strip
-      const int64_t behind = whole - min((int64_t)h, ((int64_t)k + 1) * strip_rows) * pitch;
-      const u64 a = adler[2 * (f * strips + k)], b = adler[2 * (f * strips + k) + 1];
-      a_sum += a;
-      b_sum += b + a * (u64)(behind % ADLER);
-    }
-    running += wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
-  }
+  const int running = carried_exclusive_sum(
+      wave_tot, strips, 0, [&](int k) { return bits[f * strips + k]; },
+      [&](int k, int before) {
+        offs[f * strips + k] = before;
+        // a byte of strip k counts, beyond its place in the strip, once per byte behind the strip
+        const int64_t behind = whole - min((int64_t)h, ((int64_t)k + 1) * strip_rows) * pitch;
+        const u64 a = adler[2 * (f * strips + k)], b = adler[2 * (f * strips + k) + 1];
+        a_sum += a;
+        b_sum += b + a * (u64)(behind % ADLER);
+      });
   atomicAdd(&fold_a, a_sum);
   atomicAdd(&fold_b, b_sum);
   __syncthreads();
@@ -550,13 +365,6 @@ __global__ __launch_bounds__(256) void png_scan_kernel(const int *__restrict__ b
     dst[2 + nbytes] = (u8)(b >> 8); dst[3 + nbytes] = (u8)b; dst[4 + nbytes] = (u8)(a >> 8); dst[5 + nbytes] = (u8)a;
     out_len[f] = 2 + nbytes + 4;
   }
-}
-
-__device__ __forceinline__ u32 bits8(const u32 *__restrict__ words, int p) {
-  const int wd = p >> 5, sh = p & 31;
-  u32 v = words[wd] >> sh;
-  if (sh > 24) v |= words[wd + 1] << (32 - sh);
-  return v & 255u;
 }
 
 // grid: one workgroup of 256 per (frame, strip)
@@ -628,68 +436,57 @@ __global__ __launch_bounds__(256) void png_head_kernel(const int *__restrict__ l
                                                        int delay_num, int delay_den, u8 *files, int64_t file_cap, int *file_len,
                                                        int64_t *__restrict__ where, u32 *__restrict__ seed) {
   __shared__ int wave_tot[4];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  int running = APNG_FIXED - 12;                             // where frame 0's fcTL starts
-  for (int k0 = 0; k0 < n; k0 += 256) {
-    const int i = k0 + tid;
-    const int len = i < n ? (int)min((int64_t)max(lens[i], 0), cap) : 0;
-    if (!animate) {
-      if (i < n) {
-        u8 *p = files + i * file_cap;
-        put_front(p, h, w);
-        put_head(p + 33, (u32)len, 'I', 'D', 'A', 'T');
-        seed[i] = crc_small(p + 37, 4);
-        where[i] = i * file_cap + 41;
-        put_iend(p + 41 + len + 4);
-        file_len[i] = len + STILL_EXTRA;
-      }
-      continue;
+  const int tid = threadIdx.x;
+  const auto len_of = [&](int i) { return (int)min((int64_t)max(lens[i], 0), cap); };
+  if (!animate) {                                            // (the whole workgroup)
+    for (int i = tid; i < n; i += 256) {
+      const int len = len_of(i);
+      u8 *p = files + i * file_cap;
+      put_front(p, h, w);
+      put_head(p + 33, (u32)len, 'I', 'D', 'A', 'T');
+      seed[i] = crc_small(p + 37, 4);
+      where[i] = i * file_cap + 41;
+      put_iend(p + 41 + len + 4);
+      file_len[i] = len + STILL_EXTRA;
     }
-    const int v = i < n ? APNG_FRAME + len + (i ? 4 : 0) : 0;
-    int incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int up = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += up;
-    }
-    __syncthreads();
-    if (lane == 63) wave_tot[wv] = incl;
-    __syncthreads();
-    int before = running;
-    for (int k = 0; k < wv; ++k) before += wave_tot[k];
-    if (i < n) {
-      u8 *p = files + before + incl - v;
-      if (i == 0) {
-        put_front(files, h, w);
-        put_head(files + 33, 8, 'a', 'c', 'T', 'L');
-        put_be32(files + 41, (u32)n);
-        put_be32(files + 45, 0);                             // num_plays: for ever
-        seal(files + 33, 8);
-      }
-      put_head(p, 26, 'f', 'c', 'T', 'L');
-      put_be32(p + 8, i ? 2u * i - 1 : 0u);
-      put_be32(p + 12, (u32)w);
-      put_be32(p + 16, (u32)h);
-      put_be32(p + 20, 0);
-      put_be32(p + 24, 0);
-      put_be16(p + 28, (u32)delay_num);
-      put_be16(p + 30, (u32)delay_den);
-      p[32] = 0; p[33] = 0;                                  // dispose none, blend source
-      seal(p, 26);
-      p += 38;
-      if (i == 0) put_head(p, (u32)len, 'I', 'D', 'A', 'T');
-      else {
-        put_head(p, (u32)len + 4, 'f', 'd', 'A', 'T');
-        put_be32(p + 8, 2u * i);
-      }
-      seed[i] = crc_small(p + 4, i ? 8 : 4);
-      where[i] = (p - files) + (i ? 12 : 8);
-    }
-    running += wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+    return;
   }
-  if (animate && tid == 0) {
-    put_iend(files + running);
-    file_len[0] = running + 12;
+  // frame i's fcTL and the head of its IDAT / fdAT at `at`
+  const auto put_frame = [&](int i, int at) {
+    const int len = len_of(i);
+    u8 *p = files + at;
+    if (i == 0) {
+      put_front(files, h, w);
+      put_head(files + 33, 8, 'a', 'c', 'T', 'L');
+      put_be32(files + 41, (u32)n);
+      put_be32(files + 45, 0);                               // num_plays: for ever
+      seal(files + 33, 8);
+    }
+    put_head(p, 26, 'f', 'c', 'T', 'L');
+    put_be32(p + 8, i ? 2u * i - 1 : 0u);
+    put_be32(p + 12, (u32)w);
+    put_be32(p + 16, (u32)h);
+    put_be32(p + 20, 0);
+    put_be32(p + 24, 0);
+    put_be16(p + 28, (u32)delay_num);
+    put_be16(p + 30, (u32)delay_den);
+    p[32] = 0; p[33] = 0;                                    // dispose none, blend source
+    seal(p, 26);
+    p += 38;
+    if (i == 0) put_head(p, (u32)len, 'I', 'D', 'A', 'T');
+    else {
+      put_head(p, (u32)len + 4, 'f', 'd', 'A', 'T');
+      put_be32(p + 8, 2u * i);
+    }
+    seed[i] = crc_small(p + 4, i ? 8 : 4);
+    where[i] = (p - files) + (i ? 12 : 8);
+  };
+  // frame 0's fcTL starts behind acTL; the frames follow one another
+  const int end = carried_exclusive_sum(
+      wave_tot, n, APNG_FIXED - 12, [&](int i) { return APNG_FRAME + len_of(i) + (i ? 4 : 0); }, put_frame);
+  if (tid == 0) {
+    put_iend(files + end);
+    file_len[0] = end + 12;
   }
 }
 

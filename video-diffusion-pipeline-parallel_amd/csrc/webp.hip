@@ -12,9 +12,8 @@
 //                           passes through LDS twice in chunks of 2048 pixels, 8 consecutive pixels per thread; the token at a
 //                           position follows from the start of its run of equal pixels exactly as in png_deflate_kernel, with
 //                           copies of up to 4096 pixels.  First pass: the histograms of green (with the length symbols), red
-//                           and blue by LDS atomics.  Then each code: the simple form, or png.hip's builder (restated here,
-//                           so that the PNG path stays byte-exact by construction), the run-length form of its lengths and
-//                           the 19-symbol code.  Second pass: bits per token, a prefix sum, and every token ORed into an LDS
+//                           and blue by LDS atomics.  Then each code: the simple form, or png.hip's builder (codec_common.h
+//                           holds it for both), the run-length form of its lengths and the 19-symbol code.  Second pass: bits per token, a prefix sum, and every token ORed into an LDS
 //                           image of the chunk's words.  The code header and the pixel bits go to separate staging segments.
 //   webp_head_kernel      : two workgroups per frame with the same coder: the header, the transforms and the mode image; the
 //                           main image's first bits and the entropy image that gives block row g the code group g.
@@ -24,14 +23,9 @@
 //                           following segments as it takes).
 // No workgroup waits for another inside a kernel; the launches are joined by stream order.  Nothing here is tuned beyond its
 // layout; profiles/webp_timing.txt has what it costs.
-#include "common.h"
+#include "codec_common.h"
 
 namespace {
-
-typedef unsigned char u8;
-typedef unsigned short u16;
-typedef unsigned int u32;
-typedef unsigned long long u64;
 
 constexpr int MAX_PIXELS = 1 << 24, MAX_SIDE = 16384;
 constexpr int NSYM = 280, NCL = 19;                          // green's alphabet: 256 literals and 24 length prefixes
@@ -48,15 +42,9 @@ constexpr int OWORDS = (PREAMBLE_BITS_MAX + GROUP_HEADER_MAX + CHUNK * MAIN_PIXE
 
 __constant__ u8 CL_ORDER[19] = {17, 18, 0, 1, 2, 3, 4, 5, 16, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15};
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 bool webp_dims_ok(int h, int w) { return h > 0 && w > 0 && h <= MAX_SIDE && w <= MAX_SIDE && (int64_t)h * w <= MAX_PIXELS; }
 bool webp_bits_ok(int pred_bits, int group_bits) {
   return pred_bits >= 2 && pred_bits <= 9 && (group_bits == 0 || (group_bits >= 2 && group_bits <= 9));
-}
-
-__device__ __forceinline__ u32 cost(int v) {
-  v &= 255;
-  return (u32)min(v, 256 - v);
 }
 
 // ---------------------------------------------------------------------------------------------- subtract green?
@@ -69,8 +57,8 @@ __global__ __launch_bounds__(256) void webp_cost_kernel(const u8 *__restrict__ f
   u32 with = 0, plain = 0;
   for (int x = 1 + tid; x < w; x += 256) {
     const int r0 = cur[3 * x - 3], g0 = cur[3 * x - 2], b0 = cur[3 * x - 1], r1 = cur[3 * x], g1 = cur[3 * x + 1], b1 = cur[3 * x + 2];
-    plain += cost(r1 - r0) + cost(b1 - b0);
-    with += cost((r1 - g1) - (r0 - g0)) + cost((b1 - g1) - (b0 - g0));
+    plain += byte_cost(r1 - r0) + byte_cost(b1 - b0);
+    with += byte_cost((r1 - g1) - (r0 - g0)) + byte_cost((b1 - g1) - (b0 - g0));
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
@@ -159,7 +147,7 @@ __global__ __launch_bounds__(256) void webp_transform_kernel(const u8 *__restric
         for (int c = 0; c < 24; c += 8) {
           const int v = (X >> c) & 255, l = (L >> c) & 255, t = (T >> c) & 255, tl = (TL >> c) & 255, tr = (TR >> c) & 255;
 #pragma unroll
-          for (int m = 0; m < 14; ++m) s[m] += cost(v - predict_channel(m, l, t, tl, tr, pick_left));
+          for (int m = 0; m < 14; ++m) s[m] += byte_cost(v - predict_channel(m, l, t, tl, tr, pick_left));
         }
         TL = L; T = X; TR = N;
       }
@@ -208,117 +196,12 @@ __global__ __launch_bounds__(256) void webp_transform_kernel(const u8 *__restric
   }
 }
 
-// ---------------------------------------------------------------------------------------------- code construction
-// (png.hip's builder, restated: the same tree, the same ties, the same halving loop)
-struct Builder {
-  u32 cnt[NSYM];
-  u16 order[NSYM];                      // sorted place -> symbol
-  u32 weight[2 * NSYM];                 // the leaves in sorted order, then the joined nodes in order of their making
-  u16 parent[2 * NSYM];
-  u16 depth[2 * NSYM];
-  u32 next_code[17];
-  int leaves, deepest;
-};
-
-// Code lengths of B.cnt[0 .. nsym) into len[0 .. nsym), by every thread of the workgroup.  B.cnt is changed.
-__device__ void build_lengths(Builder &B, int nsym, int limit, u8 *len) {
-  const int tid = threadIdx.x;
-  __syncthreads();
-  if (tid == 0) {
-    int used = 0;
-    for (int s = 0; s < nsym; ++s) used += B.cnt[s] != 0;
-    for (int s = 0; used < 2 && s < nsym; ++s)
-      if (!B.cnt[s]) { B.cnt[s] = 1; ++used; }
-  }
-  for (int round = 0; round < 32; ++round) {                 // (a count is 1 after at most 25 halvings, and then the depth is bounded by the symbols)
-    __syncthreads();
-    for (int s = tid; s < nsym; s += 256) {
-      const u32 c = B.cnt[s];
-      len[s] = 0;
-      if (c) {
-        int r = 0;
-        for (int t = 0; t < nsym; ++t) {
-          const u32 ct = B.cnt[t];
-          r += (ct != 0 && (ct < c || (ct == c && t < s))) ? 1 : 0;
-        }
-        B.order[r] = (u16)s;
-        B.weight[r] = c;
-      }
-    }
-    __syncthreads();
-    if (tid == 0) {
-      int L = 0;
-      for (int s = 0; s < nsym; ++s) L += B.cnt[s] != 0;
-      int i = 0, j = 0;                                     // the next leaf, the next joined node
-      for (int m = 0; m < L - 1; ++m) {
-        int pick[2];
-        for (int k = 0; k < 2; ++k) {                       // (equal weights: the leaf, which is older)
-          if (i < L && (j >= m || B.weight[i] <= B.weight[L + j])) pick[k] = i++;
-          else pick[k] = L + j++;
-        }
-        B.weight[L + m] = B.weight[pick[0]] + B.weight[pick[1]];
-        B.parent[pick[0]] = (u16)(L + m);
-        B.parent[pick[1]] = (u16)(L + m);
-      }
-      B.depth[2 * L - 2] = 0;
-      for (int node = 2 * L - 3; node >= L; --node) B.depth[node] = B.depth[B.parent[node]] + 1;
-      B.leaves = L;
-      B.deepest = 0;
-    }
-    __syncthreads();
-    const int L = B.leaves;
-    int deepest = 0;
-    for (int i = tid; i < L; i += 256) {
-      const int d = B.depth[B.parent[i]] + 1;
-      len[B.order[i]] = (u8)min(d, 255);
-      deepest = max(deepest, d);
-    }
-    if (deepest) atomicMax(&B.deepest, deepest);
-    __syncthreads();
-    if (B.deepest <= limit) break;
-    for (int s = tid; s < nsym; s += 256) {
-      const u32 c = B.cnt[s];
-      B.cnt[s] = c ? (c + 1) >> 1 : 0;
-    }
-  }
-  __syncthreads();
-}
-
-// canonical codes, bit-reversed for the LSB-first packing
-__device__ void canonical_codes(Builder &B, int nsym, const u8 *len, u16 *code) {
-  const int tid = threadIdx.x;
-  __syncthreads();
-  if (tid == 0) {
-    u32 count[17];
-    for (int b = 0; b < 17; ++b) count[b] = 0;
-    for (int s = 0; s < nsym; ++s) ++count[len[s]];
-    count[0] = 0;
-    u32 c = 0;
-    B.next_code[0] = 0;
-    for (int b = 1; b < 17; ++b) {
-      c = (c + count[b - 1]) << 1;
-      B.next_code[b] = c;
-    }
-  }
-  __syncthreads();
-  for (int s = tid; s < nsym; s += 256) {
-    const int n = len[s];
-    u32 c = 0;
-    if (n) {
-      c = B.next_code[n];
-      for (int t = 0; t < s; ++t) c += len[t] == n ? 1 : 0;
-      c = __brev(c) >> (32 - n);
-    }
-    code[s] = (u16)c;
-  }
-  __syncthreads();
-}
-
 // ---------------------------------------------------------------------------------------------- the coder of one image
+// (the code construction, HuffBuilder and what works on it, is in codec_common.h: the builder deflate has)
 struct Strip {
   u32 buf[CHUNK + 4];                   // [0]: the pixel before the chunk; [1 ..): the chunk and two pixels behind it
   u32 obuf[OWORDS];
-  Builder B;
+  HuffBuilder<NSYM> B;
   u32 hist_g[NSYM], hist_r[256], hist_b[256];
   u8 len_g[NSYM], len_r[256], len_b[256];
   u16 code_g[NSYM], code_r[256], code_b[256];
@@ -347,14 +230,8 @@ struct GroupSrc {
   }
 };
 
-// one thread
-__device__ __forceinline__ void put_bits(Strip &S, u32 value, int width) {
-  if (width == 0) return;
-  const int at = S.at;
-  S.obuf[at >> 5] |= value << (at & 31);
-  if ((at & 31) + width > 32) S.obuf[(at >> 5) + 1] |= value >> (32 - (at & 31));
-  S.at = at + width;
-}
+// one thread: behind the S.at bits in S.obuf
+__device__ __forceinline__ void put_bits(Strip &S, u32 value, int width) { ::put_bits(S.obuf, S.at, value, width); }
 
 // the prefix symbol of a copy's length: symbol | extra bits << 8 | extra value << 16
 __device__ __forceinline__ u32 length_prefix(int length) {
@@ -428,55 +305,6 @@ __device__ __forceinline__ void chunk_tokens(Strip &S, const Src &src, int c0, i
   }
 }
 
-// exclusive sum of v over the workgroup; total in `all`
-__device__ __forceinline__ int block_exclusive_sum(Strip &S, int v, int &all) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  int incl = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int up = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += up;
-  }
-  __syncthreads();
-  if (lane == 63) S.wave_val[wv] = incl;
-  __syncthreads();
-  int before = 0;
-  for (int i = 0; i < wv; ++i) before += S.wave_val[i];
-  all = S.wave_val[0] + S.wave_val[1] + S.wave_val[2] + S.wave_val[3];
-  return before + incl - v;
-}
-
-// one thread: zlib's scan of len[0 .. n) into S.seq, counts into B.cnt.  A 16 always follows its own length, so "the last
-// non-zero length" that it repeats in this format is the same value as deflate's "the previous length".
-__device__ void run_length_form(Strip &S, const u8 *len, int n) {
-  int prev = -1, count = 0, nxt = len[0];
-  int max_count = nxt == 0 ? 138 : 7, min_count = nxt == 0 ? 3 : 4;
-  auto emit = [&](int sym, int value) {
-    S.seq[S.nseq++] = (u16)(sym | (value << 5));
-    ++S.B.cnt[sym];
-  };
-  for (int i = 0; i < n; ++i) {
-    const int cur = nxt;
-    nxt = i + 1 < n ? len[i + 1] : -1;
-    if (++count < max_count && cur == nxt) continue;
-    if (count < min_count) {
-      for (int k = 0; k < count; ++k) emit(cur, 0);
-    } else if (cur != 0) {
-      if (cur != prev) { emit(cur, 0); --count; }
-      emit(16, count - 3);
-    } else if (count <= 10) {
-      emit(17, count - 3);
-    } else {
-      emit(18, count - 11);
-    }
-    count = 0;
-    prev = cur;
-    if (nxt == 0) { max_count = 138; min_count = 3; }
-    else if (cur == nxt) { max_count = 6; min_count = 3; }
-    else { max_count = 7; min_count = 4; }
-  }
-}
-
 // one thread: the simple form of a code with the one symbol `sym`
 __device__ __forceinline__ void put_simple_code(Strip &S, int sym) {
   put_bits(S, 1, 1);
@@ -510,7 +338,7 @@ __device__ void write_prefix_code(Strip &S, const u32 *hist, int nsym, u8 *len, 
   __syncthreads();
   if (tid == 0) {
     S.nseq = 0;
-    run_length_form(S, len, nsym);
+    run_length_form(S.seq, S.nseq, S.B.cnt, len, nsym);
   }
   build_lengths(S.B, NCL, 7, S.cl_len);
   canonical_codes(S.B, NCL, S.cl_len, S.cl_code);
@@ -618,7 +446,7 @@ __device__ int code_image(Strip &S, const Src &src, int total, int alpha, bool s
       mine += width;
     }
     int all;
-    int at = running + block_exclusive_sum(S, mine, all);
+    int at = running + block_exclusive_sum(S.wave_val, mine, all);
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
       const int width = wid[i];
@@ -763,34 +591,10 @@ __global__ __launch_bounds__(256) void webp_head_kernel(const u8 *__restrict__ m
 __global__ __launch_bounds__(256) void webp_scan_kernel(const int *__restrict__ bits, int segs, int *__restrict__ offs,
                                                         int *__restrict__ out_len) {
   __shared__ int wave_tot[4];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int64_t f = blockIdx.x;
-  int running = 0;
-  for (int k0 = 0; k0 < segs; k0 += 256) {
-    const int k = k0 + tid;
-    const int v = k < segs ? bits[f * segs + k] : 0;
-    int incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int up = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += up;
-    }
-    __syncthreads();
-    if (lane == 63) wave_tot[wv] = incl;
-    __syncthreads();
-    int before = running;
-    for (int i = 0; i < wv; ++i) before += wave_tot[i];
-    if (k < segs) offs[f * segs + k] = before + incl - v;
-    running += wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
-  }
-  if (tid == 0) out_len[f] = (running + 7) >> 3;
-}
-
-__device__ __forceinline__ u32 bits8(const u32 *__restrict__ words, int p) {
-  const int wd = p >> 5, sh = p & 31;
-  u32 v = words[wd] >> sh;
-  if (sh > 24) v |= words[wd + 1] << (32 - sh);
-  return v & 255u;
+  const int running = carried_exclusive_sum(
+      wave_tot, segs, 0, [&](int k) { return bits[f * segs + k]; }, [&](int k, int before) { offs[f * segs + k] = before; });
+  if (threadIdx.x == 0) out_len[f] = (running + 7) >> 3;
 }
 
 // grid: one workgroup of 256 per (frame, segment)

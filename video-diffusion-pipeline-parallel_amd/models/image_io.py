@@ -173,20 +173,13 @@ def jpeg_header(height: int, width: int, quality: int, restart_mcus: int) -> byt
     return b"".join(out)
 
 
-class JpegEncoder:
-    """(F, H, W, 3) uint8 frames on the device -> one baseline JPEG (4:2:0) per frame, compressed on the device.
+class _FrameEncoder:
+    """What the encoders of (F, H, W, 3) uint8 frames share: device and frame size, scratch kept per name and shape, the
+    check of the frames, the copy of the used bytes, and the call that waits for them."""
 
-    ``restart_mcus`` (default: one MCU row) is the restart interval: intervals are coded concurrently.  Coefficient, stream,
-    length and scratch buffers are kept per frame count; the stream buffer holds ``sp_jpeg_stream_bytes`` per frame (the size
-    no input can exceed), of which only the used bytes are ever copied to the host."""
-
-    def __init__(self, device, height: int, width: int, quality: int = 90, restart_mcus: int | None = None) -> None:
-        self.device = common.hip_device(device, "JpegEncoder")
-        self.height, self.width, self.quality = int(height), int(width), _check_quality(quality)
-        self.mcu_rows, self.mcu_cols = ops.jpeg_mcu_grid(self.height, self.width)
-        self.restart_mcus = int(restart_mcus) if restart_mcus is not None else min(self.mcu_cols, 65535)
-        self.header = jpeg_header(self.height, self.width, self.quality, self.restart_mcus)
-        self.cap = ops.jpeg_stream_bytes(self.height, self.width, self.restart_mcus)
+    def __init__(self, device, height: int, width: int) -> None:
+        self.device = common.hip_device(device, type(self).__name__)
+        self.height, self.width = int(height), int(width)
         self._scratch: dict = {}
 
     def _buf(self, name: str, shape, dtype) -> torch.Tensor:
@@ -195,14 +188,45 @@ class JpegEncoder:
             self._scratch[key] = torch.empty(shape, dtype=dtype, device=self.device)
         return self._scratch[key]
 
-    def enqueue(self, frames_u8: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
-        """Run the two stages on the current stream and return ``(streams (F, cap) uint8, lengths (F,) int32)``: views of
-        this encoder's buffers, valid until the next call with as many frames."""
+    def _check_frames(self, frames_u8) -> int:
+        """The count of frames, or ``ValueError`` for anything but a (F, height, width, 3) uint8 tensor with F > 0."""
         if (not isinstance(frames_u8, torch.Tensor) or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4
                 or tuple(frames_u8.shape[1:]) != (self.height, self.width, 3) or frames_u8.shape[0] == 0):
             raise ValueError(f"frames must be a (F, {self.height}, {self.width}, 3) uint8 tensor; got "
                              f"{getattr(frames_u8, 'dtype', type(frames_u8))} {tuple(getattr(frames_u8, 'shape', ()))}")
-        n = frames_u8.shape[0]
+        return frames_u8.shape[0]
+
+    @staticmethod
+    def _used_rows(out: torch.Tensor, lens: torch.Tensor) -> list[bytes]:
+        """Row i of ``out`` up to ``lens[i]``: the lengths come to the host in one copy, then only the used bytes."""
+        return [out[i, :n].cpu().numpy().tobytes() for i, n in enumerate(lens.cpu().tolist())]
+
+    def _finished(self, enqueue, collect, *args):
+        """``collect`` of what ``enqueue(*args)`` returned, once the current stream has done the work."""
+        bufs = enqueue(*args)
+        torch.cuda.current_stream(self.device).synchronize()
+        return collect(*bufs)
+
+
+class JpegEncoder(_FrameEncoder):
+    """(F, H, W, 3) uint8 frames on the device -> one baseline JPEG (4:2:0) per frame, compressed on the device.
+
+    ``restart_mcus`` (default: one MCU row) is the restart interval: intervals are coded concurrently.  Coefficient, stream,
+    length and scratch buffers are kept per frame count; the stream buffer holds ``sp_jpeg_stream_bytes`` per frame (the size
+    no input can exceed), of which only the used bytes are ever copied to the host."""
+
+    def __init__(self, device, height: int, width: int, quality: int = 90, restart_mcus: int | None = None) -> None:
+        super().__init__(device, height, width)
+        self.quality = _check_quality(quality)
+        self.mcu_rows, self.mcu_cols = ops.jpeg_mcu_grid(self.height, self.width)
+        self.restart_mcus = int(restart_mcus) if restart_mcus is not None else min(self.mcu_cols, 65535)
+        self.header = jpeg_header(self.height, self.width, self.quality, self.restart_mcus)
+        self.cap = ops.jpeg_stream_bytes(self.height, self.width, self.restart_mcus)
+
+    def enqueue(self, frames_u8: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+        """Run the two stages on the current stream and return ``(streams (F, cap) uint8, lengths (F,) int32)``: views of
+        this encoder's buffers, valid until the next call with as many frames."""
+        n = self._check_frames(frames_u8)
         coef = self._buf("coef", (n, self.mcu_rows, self.mcu_cols, 6, 64), torch.int16)
         out = self._buf("stream", (n, self.cap), torch.uint8)
         lens = self._buf("len", (n,), torch.int32)
@@ -213,12 +237,10 @@ class JpegEncoder:
 
     def collect(self, out: torch.Tensor, lens: torch.Tensor) -> list[bytes]:
         """The files of an ``enqueue`` whose work has finished: the lengths come to the host first, then only the used bytes."""
-        return [self.header + out[i, :n].cpu().numpy().tobytes() + b"\xff\xd9" for i, n in enumerate(lens.cpu().tolist())]
+        return [self.header + s + b"\xff\xd9" for s in self._used_rows(out, lens)]
 
     def encode(self, frames_u8: torch.Tensor) -> list[bytes]:
-        out, lens = self.enqueue(frames_u8)
-        torch.cuda.current_stream(self.device).synchronize()
-        return self.collect(out, lens)
+        return self._finished(self.enqueue, self.collect, frames_u8)
 
 
 class UnsupportedJpeg(ValueError):
@@ -501,15 +523,28 @@ def load_image_device(path: str, device) -> torch.Tensor:
     return torch.from_numpy(load_image(path)).to(common.hip_device(device, "load_image_device"))
 
 
-def _jpeg_host(frame: np.ndarray, quality: int) -> bytes:
-    """Pillow's encode of one frame in host memory (4:2:0), for arrays that never were on a GPU."""
+def _pillow_bytes(frame: np.ndarray, format: str, **options) -> bytes:
+    """Pillow's encode of one frame in host memory, for arrays that never were on a GPU."""
     import io
 
     from PIL import Image
 
     buf = io.BytesIO()
-    Image.fromarray(frame).save(buf, format="JPEG", quality=quality, subsampling=2)
+    Image.fromarray(frame).save(buf, format=format, **options)
     return buf.getvalue()
+
+
+def _write(path: str, data: bytes) -> None:
+    with open(path, "wb") as fh:
+        fh.write(data)
+
+
+def _write_numbered(pattern: str, count: int, datas) -> list[str]:
+    """``datas`` (an iterable of ``count`` files' bytes) to ``pattern % 0 ..``; the names."""
+    files = [pattern % i for i in range(count)]
+    for name, data in zip(files, datas):
+        _write(name, data)
+    return files
 
 
 def _chunk(fourcc: bytes, payload: bytes) -> bytes:
@@ -547,8 +582,7 @@ def write_avi(path: str, jpegs: list[bytes], width: int, height: int, fps: int) 
         at += len(movi[-1])
     body = b"AVI " + _chunk(b"LIST", hdrl) + _chunk(b"LIST", b"".join(movi)) + _chunk(b"idx1", b"".join(index))
     assert 8 + len(body) == total
-    with open(path, "wb") as fh:
-        fh.write(b"RIFF" + struct.pack("<I", len(body)) + body)
+    _write(path, b"RIFF" + struct.pack("<I", len(body)) + body)
 
 
 def _check_fps(fps) -> float:
@@ -581,12 +615,11 @@ def write_gif(path, palettes, datas, width: int, height: int, fps=7) -> bytes:
     out.append(b"\x3b")
     blob = b"".join(out)
     if path is not None:
-        with open(path, "wb") as fh:
-            fh.write(blob)
+        _write(path, blob)
     return blob
 
 
-class GifEncoder:
+class GifEncoder(_FrameEncoder):
     """(F, H, W, 3) uint8 frames on the device -> one animated GIF, quantised and LZW-coded on the device (``csrc/gif.hip``).
 
     Every frame has a palette of its own (median cut over a 32^3 histogram, no dithering) and is coded in strips of
@@ -596,30 +629,19 @@ class GifEncoder:
     the used bytes are ever copied to the host."""
 
     def __init__(self, device, height: int, width: int, strip_rows: int = 8, fps=7) -> None:
-        self.device = common.hip_device(device, "GifEncoder")
-        self.height, self.width, self.fps = int(height), int(width), _check_fps(fps)
+        super().__init__(device, height, width)
+        self.fps = _check_fps(fps)
         if not isinstance(strip_rows, (int, np.integer)) or strip_rows < 1:
             raise ValueError(f"strip_rows must be a positive integer; got {strip_rows!r}")
         self.strip_rows = int(strip_rows)
         self.cap = ops.gif_stream_bytes(self.height, self.width, self.strip_rows)
         if self.cap == 0:
             raise ValueError(f"a GIF frame is 1..65535 pixels on a side and at most 2^24 in all; got {height}x{width}")
-        self._scratch: dict = {}
-
-    def _buf(self, name: str, shape, dtype) -> torch.Tensor:
-        key = (name, shape)
-        if key not in self._scratch:
-            self._scratch[key] = torch.empty(shape, dtype=dtype, device=self.device)
-        return self._scratch[key]
 
     def enqueue(self, frames_u8: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """Run the two stages on the current stream and return ``(palettes (F, 256, 3) uint8, streams (F, cap) uint8, lengths
         (F,) int32)``: views of this encoder's buffers, valid until the next call with as many frames."""
-        if (not isinstance(frames_u8, torch.Tensor) or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4
-                or tuple(frames_u8.shape[1:]) != (self.height, self.width, 3) or frames_u8.shape[0] == 0):
-            raise ValueError(f"frames must be a (F, {self.height}, {self.width}, 3) uint8 tensor; got "
-                             f"{getattr(frames_u8, 'dtype', type(frames_u8))} {tuple(getattr(frames_u8, 'shape', ()))}")
-        n = frames_u8.shape[0]
+        n = self._check_frames(frames_u8)
         palettes = self._buf("palette", (n, 256, 3), torch.uint8)
         indices = self._buf("index", (n, self.height, self.width), torch.uint8)
         out = self._buf("stream", (n, self.cap), torch.uint8)
@@ -632,13 +654,10 @@ class GifEncoder:
     def collect(self, palettes: torch.Tensor, out: torch.Tensor, lens: torch.Tensor) -> bytes:
         """The file of an ``enqueue`` whose work has finished: the lengths come to the host first, then only the used bytes."""
         tables = palettes.cpu().numpy()
-        datas = [out[i, :n].cpu().numpy().tobytes() for i, n in enumerate(lens.cpu().tolist())]
-        return write_gif(None, list(tables), datas, self.width, self.height, self.fps)
+        return write_gif(None, list(tables), self._used_rows(out, lens), self.width, self.height, self.fps)
 
     def encode(self, frames_u8: torch.Tensor) -> bytes:
-        bufs = self.enqueue(frames_u8)
-        torch.cuda.current_stream(self.device).synchronize()
-        return self.collect(*bufs)
+        return self._finished(self.enqueue, self.collect, frames_u8)
 
 
 PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
@@ -667,9 +686,7 @@ def write_apng(path, streams, width: int, height: int, fps=7) -> bytes:
     others; then IEND.  A viewer that knows no APNG shows frame 0."""
     if len(streams) == 0:
         raise ValueError("write_apng: no frames")
-    delay = (1 / Fraction(_check_fps(fps))).limit_denominator(65535)
-    if not 0 < delay.numerator <= 65535:
-        raise ValueError(f"write_apng: a delay of 1 / {fps} s does not fit the frame control chunk")
+    delay = _apng_delay(fps, "write_apng: ")
     out, seq = [PNG_SIGNATURE, _png_ihdr(height, width), _png_chunk(b"acTL", struct.pack(">II", len(streams), 0))], 0
     for i, stream in enumerate(streams):
         out.append(_png_chunk(b"fcTL", struct.pack(">IIIIIHHBB", seq, width, height, 0, 0, delay.numerator, delay.denominator, 0, 0)))
@@ -682,17 +699,16 @@ def write_apng(path, streams, width: int, height: int, fps=7) -> bytes:
     out.append(_png_chunk(b"IEND", b""))
     blob = b"".join(out)
     if path is not None:
-        with open(path, "wb") as fh:
-            fh.write(blob)
+        _write(path, blob)
     return blob
 
 
-def _apng_delay(fps) -> Fraction:
-    """``write_apng``'s delay for the device route, which takes the two numbers: ``1 / fps`` s as a fraction of two 16-bit
-    numbers (``write_apng`` itself stays the self-contained statement the device files are held to)."""
+def _apng_delay(fps, who: str = "") -> Fraction:
+    """The delay of an fcTL, for ``write_apng`` and for the device route, which takes the two numbers: ``1 / fps`` s as a
+    fraction of two 16-bit numbers.  ``who`` goes in front of the refusal."""
     delay = (1 / Fraction(_check_fps(fps))).limit_denominator(65535)
     if not 0 < delay.numerator <= 65535:
-        raise ValueError(f"a delay of 1 / {fps} s does not fit the frame control chunk")
+        raise ValueError(f"{who}a delay of 1 / {fps} s does not fit the frame control chunk")
     return delay
 
 
@@ -700,7 +716,7 @@ PNG_ASSEMBLE = "device"             # chunks and CRC-32 on the device ("host": p
 PNG_STRIP_ROWS = 16                  # the fastest of 4 / 8 / 16 / 32 rows within 1 % of one strip per frame (profiles/png_timing.txt)
 
 
-class PngEncoder:
+class PngEncoder(_FrameEncoder):
     """(F, H, W, 3) uint8 frames on the device -> one PNG file per frame, filtered and deflated on the device (``csrc/png.hip``).
 
     Every row takes the filter with the least sum of min(b, 256 - b); a frame is coded in strips of ``strip_rows`` rows, each
@@ -717,8 +733,7 @@ class PngEncoder:
     / ``collect`` are the host route's pieces under either setting."""
 
     def __init__(self, device, height: int, width: int, strip_rows: int = PNG_STRIP_ROWS, assemble: str = PNG_ASSEMBLE) -> None:
-        self.device = common.hip_device(device, "PngEncoder")
-        self.height, self.width = int(height), int(width)
+        super().__init__(device, height, width)
         if assemble not in ("device", "host"):
             raise ValueError(f"assemble must be 'device' or 'host'; got {assemble!r}")
         self.assemble = assemble
@@ -728,22 +743,11 @@ class PngEncoder:
         self.cap = ops.png_stream_bytes(self.height, self.width, self.strip_rows)
         if self.cap == 0:
             raise ValueError(f"a frame for the PNG kernels is 1..65535 pixels on a side and at most 2^24 in all; got {height}x{width}")
-        self._scratch: dict = {}
-
-    def _buf(self, name: str, shape, dtype) -> torch.Tensor:
-        key = (name, shape)
-        if key not in self._scratch:
-            self._scratch[key] = torch.empty(shape, dtype=dtype, device=self.device)
-        return self._scratch[key]
 
     def enqueue(self, frames_u8: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
         """Run the two stages on the current stream and return ``(streams (F, cap) uint8, lengths (F,) int32)``: views of
         this encoder's buffers, valid until the next call with as many frames."""
-        if (not isinstance(frames_u8, torch.Tensor) or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4
-                or tuple(frames_u8.shape[1:]) != (self.height, self.width, 3) or frames_u8.shape[0] == 0):
-            raise ValueError(f"frames must be a (F, {self.height}, {self.width}, 3) uint8 tensor; got "
-                             f"{getattr(frames_u8, 'dtype', type(frames_u8))} {tuple(getattr(frames_u8, 'shape', ()))}")
-        n = frames_u8.shape[0]
+        n = self._check_frames(frames_u8)
         filtered = self._buf("filtered", (n, self.height, 1 + 3 * self.width), torch.uint8)
         out = self._buf("stream", (n, self.cap), torch.uint8)
         lens = self._buf("len", (n,), torch.int32)
@@ -755,7 +759,7 @@ class PngEncoder:
     def collect_streams(self, out: torch.Tensor, lens: torch.Tensor) -> list[bytes]:
         """The zlib streams of an ``enqueue`` whose work has finished: the lengths come to the host first, then only the used
         bytes."""
-        return [out[i, :n].cpu().numpy().tobytes() for i, n in enumerate(lens.cpu().tolist())]
+        return self._used_rows(out, lens)
 
     def collect(self, out: torch.Tensor, lens: torch.Tensor) -> list[bytes]:
         """The PNG files of an ``enqueue`` whose work has finished."""
@@ -790,28 +794,24 @@ class PngEncoder:
     def collect_files(self, files: torch.Tensor, file_lens: torch.Tensor) -> list[bytes]:
         """The PNG files of an ``enqueue_files`` whose work has finished: the lengths come to the host first, then only the used
         bytes; the host adds nothing to them."""
-        return [files[i, :n].cpu().numpy().tobytes() for i, n in enumerate(file_lens.cpu().tolist())]
+        return self._used_rows(files, file_lens)
 
     def collect_apng(self, file: torch.Tensor, file_lens: torch.Tensor) -> bytes:
         """The animated PNG of an ``enqueue_apng`` whose work has finished: one copy of the length, one of the used bytes."""
         return file[:int(file_lens[:1].cpu()[0])].cpu().numpy().tobytes()
 
     def encode(self, frames_u8: torch.Tensor) -> list[bytes]:
-        bufs = self.enqueue_files(frames_u8) if self.assemble == "device" else self.enqueue(frames_u8)
-        torch.cuda.current_stream(self.device).synchronize()
-        return self.collect_files(*bufs) if self.assemble == "device" else self.collect(*bufs)
+        if self.assemble == "device":
+            return self._finished(self.enqueue_files, self.collect_files, frames_u8)
+        return self._finished(self.enqueue, self.collect, frames_u8)
 
     def encode_apng(self, frames_u8: torch.Tensor, fps=7) -> bytes:
         """One animated PNG of the frames: put together on the device, or under ``assemble="host"`` by ``write_apng`` around the
         same streams; the bytes are the same."""
         _check_fps(fps)
         if self.assemble == "device":
-            bufs = self.enqueue_apng(frames_u8, fps)
-            torch.cuda.current_stream(self.device).synchronize()
-            return self.collect_apng(*bufs)
-        out, lens = self.enqueue(frames_u8)
-        torch.cuda.current_stream(self.device).synchronize()
-        return write_apng(None, self.collect_streams(out, lens), self.width, self.height, fps)
+            return self._finished(self.enqueue_apng, self.collect_apng, frames_u8, fps)
+        return write_apng(None, self._finished(self.enqueue, self.collect_streams, frames_u8), self.width, self.height, fps)
 
 
 def _riff_chunk(kind: bytes, payload: bytes) -> list[bytes]:
@@ -854,8 +854,7 @@ def write_webp(path, streams, width: int, height: int, fps=7) -> bytes:
         out += [b"ANMF", struct.pack("<I", len(frame_head) + sum(len(p) for p in inner)), frame_head] + inner
     blob = _riff_file(out)
     if path is not None:
-        with open(path, "wb") as fh:
-            fh.write(blob)
+        _write(path, blob)
     return blob
 
 
@@ -873,7 +872,7 @@ def _check_webp_bits(pred_bits, group_bits) -> tuple[int, int]:
     return int(pred_bits), int(group_bits)
 
 
-class WebpEncoder:
+class WebpEncoder(_FrameEncoder):
     """(F, H, W, 3) uint8 frames on the device -> one lossless WebP per frame or one animated WebP, transformed and entropy-coded
     on the device (``csrc/webp.hip``).
 
@@ -890,28 +889,16 @@ class WebpEncoder:
     ever copied to the host."""
 
     def __init__(self, device, height: int, width: int, pred_bits: int = WEBP_PRED_BITS, group_bits: int = WEBP_GROUP_BITS) -> None:
-        self.device = common.hip_device(device, "WebpEncoder")
-        self.height, self.width = int(height), int(width)
+        super().__init__(device, height, width)
         self.pred_bits, self.group_bits = _check_webp_bits(pred_bits, group_bits)
         self.cap = ops.webp_stream_bytes(self.height, self.width, self.pred_bits, self.group_bits)
         if self.cap == 0:
             raise ValueError(f"a frame for the WebP kernels is 1..16384 pixels on a side and at most 2^24 in all; got {height}x{width}")
-        self._scratch: dict = {}
-
-    def _buf(self, name: str, shape, dtype) -> torch.Tensor:
-        key = (name, shape)
-        if key not in self._scratch:
-            self._scratch[key] = torch.empty(shape, dtype=dtype, device=self.device)
-        return self._scratch[key]
 
     def enqueue(self, frames_u8: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
         """Run the two stages on the current stream and return ``(streams (F, cap) uint8, lengths (F,) int32)``: views of
         this encoder's buffers, valid until the next call with as many frames."""
-        if (not isinstance(frames_u8, torch.Tensor) or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4
-                or tuple(frames_u8.shape[1:]) != (self.height, self.width, 3) or frames_u8.shape[0] == 0):
-            raise ValueError(f"frames must be a (F, {self.height}, {self.width}, 3) uint8 tensor; got "
-                             f"{getattr(frames_u8, 'dtype', type(frames_u8))} {tuple(getattr(frames_u8, 'shape', ()))}")
-        n, block = frames_u8.shape[0], 1 << self.pred_bits
+        n, block = self._check_frames(frames_u8), 1 << self.pred_bits
         residual = self._buf("residual", (n, self.height, self.width, 4), torch.uint8)
         modes = self._buf("modes", (n, -(-self.height // block), -(-self.width // block)), torch.uint8)
         flags = self._buf("flags", (n,), torch.int32)
@@ -925,23 +912,19 @@ class WebpEncoder:
     def collect_streams(self, out: torch.Tensor, lens: torch.Tensor) -> list[bytes]:
         """The VP8L streams of an ``enqueue`` whose work has finished: the lengths come to the host first, then only the used
         bytes."""
-        return [out[i, :n].cpu().numpy().tobytes() for i, n in enumerate(lens.cpu().tolist())]
+        return self._used_rows(out, lens)
 
     def collect(self, out: torch.Tensor, lens: torch.Tensor) -> list[bytes]:
         """The still ``.webp`` files of an ``enqueue`` whose work has finished."""
         return [webp_file(s) for s in self.collect_streams(out, lens)]
 
     def encode(self, frames_u8: torch.Tensor) -> list[bytes]:
-        out, lens = self.enqueue(frames_u8)
-        torch.cuda.current_stream(self.device).synchronize()
-        return self.collect(out, lens)
+        return self._finished(self.enqueue, self.collect, frames_u8)
 
     def encode_animation(self, frames_u8: torch.Tensor, fps=7) -> bytes:
         """One animated WebP of the frames (``write_webp`` around the same streams)."""
         _check_fps(fps)
-        out, lens = self.enqueue(frames_u8)
-        torch.cuda.current_stream(self.device).synchronize()
-        return write_webp(None, self.collect_streams(out, lens), self.width, self.height, fps)
+        return write_webp(None, self._finished(self.enqueue, self.collect_streams, frames_u8), self.width, self.height, fps)
 
 
 def _jpeg_frames(frames_u8, quality: int) -> tuple[list[bytes], int, int]:
@@ -952,7 +935,7 @@ def _jpeg_frames(frames_u8, quality: int) -> tuple[list[bytes], int, int]:
         _, h, w, _ = frames_u8.shape
         return JpegEncoder(frames_u8.device, h, w, quality).encode(frames_u8), h, w
     a = _frames_array(frames_u8)
-    return [_jpeg_host(f, quality) for f in a], a.shape[1], a.shape[2]
+    return [_pillow_bytes(f, "JPEG", quality=quality, subsampling=2) for f in a], a.shape[1], a.shape[2]      # 4:2:0
 
 
 def _frames_array(frames_u8) -> np.ndarray:
@@ -1007,11 +990,7 @@ def save_frames(frames_u8, path: str, fps: int = 7, quality: int = 90) -> list[s
         if ext == ".avi":
             write_avi(path, jpegs, w, h, fps)
             return [path]
-        files = [path % i for i in range(len(jpegs))]
-        for name, data in zip(files, jpegs):
-            with open(name, "wb") as fh:
-                fh.write(data)
-        return files
+        return _write_numbered(path, len(jpegs), jpegs)
     if ext == ".npy":
         np.save(path, a)
         return [path]
@@ -1019,37 +998,23 @@ def save_frames(frames_u8, path: str, fps: int = 7, quality: int = 90) -> list[s
         if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or 0 in frames_u8.shape:
             raise ValueError(f"frames must be (F, H, W, 3) uint8; got {frames_u8.dtype} {tuple(frames_u8.shape)}")
         _check_fps(fps)
-        data = GifEncoder(frames_u8.device, frames_u8.shape[1], frames_u8.shape[2], fps=fps).encode(frames_u8)
-        with open(path, "wb") as fh:
-            fh.write(data)
+        _write(path, GifEncoder(frames_u8.device, frames_u8.shape[1], frames_u8.shape[2], fps=fps).encode(frames_u8))
         return [path]
     if on_gpu and ext in (".png", ".apng", ""):
         enc = PngEncoder(frames_u8.device, frames_u8.shape[1], frames_u8.shape[2])
         if ext == ".apng":
-            data = enc.encode_apng(frames_u8, fps)
-            with open(path, "wb") as fh:
-                fh.write(data)
+            _write(path, enc.encode_apng(frames_u8, fps))
             return [path]
         if ext == "":
             os.makedirs(path, exist_ok=True)
         pattern = path if ext == ".png" else os.path.join(path, "%03d.png")
-        files = [pattern % i for i in range(frames_u8.shape[0])]
-        for name, data in zip(files, enc.encode(frames_u8)):
-            with open(name, "wb") as fh:
-                fh.write(data)
-        return files
+        return _write_numbered(pattern, frames_u8.shape[0], enc.encode(frames_u8))
     if ext == ".webp" and on_gpu:
         enc = WebpEncoder(frames_u8.device, frames_u8.shape[1], frames_u8.shape[2])
         if "%" not in path:
-            data = enc.encode_animation(frames_u8, fps)
-            with open(path, "wb") as fh:
-                fh.write(data)
+            _write(path, enc.encode_animation(frames_u8, fps))
             return [path]
-        files = [path % i for i in range(frames_u8.shape[0])]
-        for name, data in zip(files, enc.encode(frames_u8)):
-            with open(name, "wb") as fh:
-                fh.write(data)
-        return files
+        return _write_numbered(path, frames_u8.shape[0], enc.encode(frames_u8))
     from PIL import Image
 
     if ext == ".webp":
@@ -1058,10 +1023,7 @@ def save_frames(frames_u8, path: str, fps: int = 7, quality: int = 90) -> list[s
             ims = [Image.fromarray(f) for f in a]
             ims[0].save(path, format="WEBP", save_all=True, append_images=ims[1:], lossless=True, loop=0, duration=ms)
             return [path]
-        files = [path % i for i in range(len(a))]
-        for name, f in zip(files, a):
-            Image.fromarray(f).save(name, format="WEBP", lossless=True)
-        return files
+        return _write_numbered(path, len(a), (_pillow_bytes(f, "WEBP", lossless=True) for f in a))
     if ext == ".apng":
         _check_fps(fps)
         ims = [Image.fromarray(f) for f in a]
@@ -1083,8 +1045,4 @@ def save_frames(frames_u8, path: str, fps: int = 7, quality: int = 90) -> list[s
     else:
         raise ValueError(f"'{path}': unknown output format {ext!r} (.avi, .gif, .apng, .webp, .npy, %03d.jpg / %03d.png / "
                          f"%03d.webp pattern or a directory)")
-    files = []
-    for i, f in enumerate(a):
-        files.append(pattern % i)
-        Image.fromarray(f).save(files[-1])
-    return files
+    return _write_numbered(pattern, len(a), (_pillow_bytes(f, "PNG") for f in a))
