@@ -5,7 +5,10 @@
 * ``draw(rng, gen, route, legal_only)``  a seeded generator over all fields (and, with ``legal_only=False``, near-misses
   that break one rule at a time),
 * ``make_tensors`` / ``to_struct``  operands for a drawn descriptor (every operand a column slice of a wider buffer whose
-  slack is NaN) and the ctypes mirror of it.
+  slack is NaN) and the ctypes mirror of it,
+* ``exact_eligible`` / ``make_exact_tensors`` / ``exact_case`` / ``exact_draws``  the same buffers filled with small non-zero
+  integers, on the first rung of a value ladder on which the fp64 reference is exactly what an fp16 store holds: a kernel
+  must then match it bit for bit in any order of summation (tests/test_gemm_exact_gpu.py).
 
 A descriptor is a dict keyed by the struct's field names; pointer fields hold an address (0 = NULL; ``draw`` hands out
 aligned fake ones), keys that start with ``_`` are notes of the generator (value ranges, column offsets) and not fields.
@@ -206,13 +209,17 @@ def euler_update(d, eps16, latent, uncond=None, guidance=None):
     return x + (x - x0) / sigma * (sigma_next - sigma)
 
 
-def reference(d, t) -> dict:
+def reference(d, t, fold_formula=False, x=None) -> dict:
     """fp64 results of a legal descriptor: ``d`` [m][stored columns] before the rounding to fp16, and the side outputs the
     descriptor asks for (``ln_out``, ``gn_part``, ``euler_out``).  ``t``: CPU tensors by field name, each the view the
-    pointer addresses (first row / column = the pointer), weights [groups][n][K]."""
+    pointer addresses (first row / column = the pointer), weights [groups][n][K].  ``fold_formula``: a folded LayerNorm as
+    the header writes it from its two inputs, ``rstd[m] * (acc - mean[m] * colsum[n])``, whatever ``ln_stats`` and
+    ``ln_colsum`` hold (the exact operands hand it integers), not as ``F.layer_norm`` of the rows.  ``x``: the [m][K] operand
+    matrix in place of ``gather_rows`` (tests/test_exact_patterns_cpu.py plants its mutants there)."""
     m, n = d["m"], d["n"]
-    x = gather_rows(d, t["a"], t.get("a2") if d["a2"] else None)
-    if d["ln_stats"]:
+    if x is None:
+        x = gather_rows(d, t["a"], t.get("a2") if d["a2"] else None)
+    if d["ln_stats"] and not fold_formula:
         x = F.layer_norm(x, (d["cin"],), eps=d["_ln_eps"])
     w = t["w"].double()
     if d["w_group_rows"]:
@@ -220,6 +227,15 @@ def reference(d, t) -> dict:
         acc = torch.cat([x[g * r:(g + 1) * r] @ w[g].t() for g in range((m + r - 1) // r)], dim=0)
     else:
         acc = x @ w[0].t()
+    if d["ln_stats"] and fold_formula:
+        st = t["ln_stats"].double()
+        acc = st[:m, 1:2] * (acc - st[:m, 0:1] * t["ln_colsum"].double())
+    return epilogue(d, t, acc)
+
+
+def epilogue(d, t, acc) -> dict:
+    """What ``reference`` does behind the contraction (and the fold): fp64 ``acc`` [m][n] -> its result dict."""
+    m, n = d["m"], d["n"]
     if d["bias"]:
         acc = acc + t["bias"].double()
     if d["bias2"]:
@@ -636,47 +652,124 @@ def _sliced(rows, ld, off, width, fill, dtype, values):
     return buf, view
 
 
-def make_tensors(d, gen=None):
+class _Gaussian:
+    """The fuzz's value ranges, drawn in the order make_tensors always drew them (a seed keeps its operands)."""
+
+    def __init__(self, d, g):
+        self.d, self.g = d, g
+
+    def a(self, rows, cin):
+        a = torch.randn(rows, cin, generator=self.g)
+        if self.d["ln_stats"]:
+            a = a * 1.7 + 3.0 * torch.randn(rows, 1, generator=self.g)
+        return a
+
+    def w(self, groups, n, k):
+        return torch.randn(groups, n, k, generator=self.g) / math.sqrt(k)
+
+    def a2(self, rows, cin2):
+        return torch.randn(rows, cin2, generator=self.g)
+
+    def bias(self, n):
+        return torch.randn(n, generator=self.g)
+
+    def bias2(self, rows, n):
+        return torch.randn(rows, n, generator=self.g)
+
+    def res(self, rows, cols):
+        return torch.randn(rows, cols, generator=self.g)
+
+    def ln(self, a, w):
+        return row_stats(a.double(), self.d["_ln_eps"]).float(), w[0].float().sum(1)
+
+
+RUNGS = [(3, 2, 1), (2, 1, 1), (1, 1, 1), (1, 1, 4), (1, 1, 16), (1, 1, 64)]     # (|a| <=, |w| <=, 1 / density of W)
+EXACT_LIMIT = 1 << 24
+
+
+def _ints(g, shape, top):
+    """Non-zero integers in [-top, top], fp32."""
+    mag = torch.randint(1, top + 1, shape, generator=g)
+    return (mag * (2 * torch.randint(0, 2, shape, generator=g) - 1)).float()
+
+
+class _Integers:
+    """Non-zero integers on a rung of RUNGS.  A thinned W keeps, for every k, the columns n = off[k] mod (1 / density): every
+    operand element still meets a non-zero weight in every span of 1 / density <= 64 output columns, so no term is invisible."""
+
+    def __init__(self, d, g, rung):
+        self.d, self.g = d, g
+        self.amax, self.wmax, self.thin = RUNGS[rung]
+
+    def a(self, rows, cin):
+        return _ints(self.g, (rows, cin), self.amax)
+
+    def w(self, groups, n, k):
+        w = _ints(self.g, (groups, n, k), self.wmax)
+        if self.thin > 1:
+            off = torch.randint(0, self.thin, (groups, 1, k), generator=self.g)
+            w = w * (torch.arange(n)[None, :, None] % self.thin == off)
+        return w
+
+    def a2(self, rows, cin2):
+        return _ints(self.g, (rows, cin2), self.amax)
+
+    def bias(self, n):
+        return _ints(self.g, (n,), 8)
+
+    def bias2(self, rows, n):
+        return _ints(self.g, (rows, n), 8)
+
+    def res(self, rows, cols):
+        return _ints(self.g, (rows, cols), 8)
+
+    def ln(self, a, w):
+        """Integer means, power-of-two rstd, the weight's own (integer) row sums."""
+        rows = a.shape[0]
+        mean = torch.randint(-3, 4, (rows,), generator=self.g).float()
+        rstd = torch.tensor([0.5, 1.0, 2.0])[torch.randint(0, 3, (rows,), generator=self.g)]
+        return torch.stack([mean, rstd], dim=1), w[0].float().sum(1)
+
+
+def make_tensors(d, gen=None, values=None):
     """CPU operands of a legal descriptor: ``bufs`` (name -> the wide buffer, slack = NaN) and ``views`` (name -> what the
     descriptor's pointer addresses, for reference()).  Value ranges follow the existing kernel tests (unit-variance
-    activations, weights / sqrt(K), folded-LayerNorm rows with a common offset of up to ~3 standard deviations)."""
+    activations, weights / sqrt(K), folded-LayerNorm rows with a common offset of up to ~3 standard deviations);
+    ``values`` (make_exact_tensors) replaces the ranges and nothing else."""
     g = gen if gen is not None else torch.Generator().manual_seed(d["_seed"])
+    v = values if values is not None else _Gaussian(d, g)
     nan = float("nan")
     m, n, cin, mode = d["m"], d["n"], d["cin"], d["mode"]
     off = d["_off"]
     bufs, views = {}, {}
     rows_in = d["n_img"] * d["hin"] * d["win"] if mode == CONV3X3 else m
-    a = torch.randn(rows_in, cin, generator=g)
-    if d["ln_stats"]:
-        a = a * 1.7 + 3.0 * torch.randn(rows_in, 1, generator=g)
+    a = v.a(rows_in, cin)
     bufs["a"], views["a"] = _sliced(rows_in, d["lda"], off["a"], cin, nan, torch.float16, a.half())
     k = TAPS[mode] * cin + d["cin2"]
     groups = d.get("_groups", 1) if d["w_group_rows"] else 1
     stride = d["w_group_stride"] if d["w_group_rows"] else n * k
     wbuf = torch.full((groups * stride,), nan, dtype=torch.float16)
-    w = (torch.randn(groups, n, k, generator=g) / math.sqrt(k)).half()
+    w = v.w(groups, n, k).half()
     for i in range(groups):
         wbuf[i * stride:i * stride + n * k] = w[i].reshape(-1)
     bufs["w"], views["w"] = wbuf, w
     if d["a2"]:
-        bufs["a2"], views["a2"] = _sliced(m, d["lda2"], off["a2"], d["cin2"], nan, torch.float16,
-                                          torch.randn(m, d["cin2"], generator=g).half())
+        bufs["a2"], views["a2"] = _sliced(m, d["lda2"], off["a2"], d["cin2"], nan, torch.float16, v.a2(m, d["cin2"]).half())
     if d["bias"]:
-        bufs["bias"] = views["bias"] = torch.randn(n, generator=g)
+        bufs["bias"] = views["bias"] = v.bias(n)
     if d["bias2"]:
         rows = d["bias2_rows"] if d["bias2_rows"] > 0 else m
         nb = (m + rows - 1) // rows
-        bufs["bias2"], views["bias2"] = _sliced(nb, d["ldb2"] or n, off.get("bias2", 0), n, nan, torch.float32,
-                                                torch.randn(nb, n, generator=g))
+        bufs["bias2"], views["bias2"] = _sliced(nb, d["ldb2"] or n, off.get("bias2", 0), n, nan, torch.float32, v.bias2(nb, n))
     st = stored(d)
     for r in ("res1", "res2"):
         if d[r]:
             ld = d["ld" + r[0] + r[-1]]
-            bufs[r], views[r] = _sliced(m, ld, off[r], st, nan, torch.float16, torch.randn(m, st, generator=g).half())
+            bufs[r], views[r] = _sliced(m, ld, off[r], st, nan, torch.float16, v.res(m, st).half())
     if d["ln_stats"]:
-        x = views["a"][:, :cin].double()
-        bufs["ln_stats"] = views["ln_stats"] = row_stats(x, d["_ln_eps"]).float()
-        bufs["ln_colsum"] = views["ln_colsum"] = w[0].float().sum(1)
+        stats, colsum = v.ln(views["a"][:, :cin], w)
+        bufs["ln_stats"] = views["ln_stats"] = stats
+        bufs["ln_colsum"] = views["ln_colsum"] = colsum
     if d["euler_out"]:
         b = m // (d["euler_frames"] * d["euler_hw"])
         scale = max(1.0, d["euler_sigma"])
@@ -691,6 +784,131 @@ def make_tensors(d, gen=None):
                 gs[i * gl:i * gl + d["euler_frames"]] = torch.linspace(1.0, 1.5 + i, d["euler_frames"])
             bufs["euler_guidance"] = views["euler_guidance"] = gs
     return bufs, views
+
+
+# ------------------------------------------------------------------------------------------------ exact operands
+def exact_eligible(d) -> bool:
+    """Whether integer operands make the header's arithmetic exact in fp32.  Not GEGLU (a gelu) and not the Euler tail
+    (non-dyadic sigmas, fp16 guidance arithmetic).  A folded LayerNorm IS: ``ln_stats`` and ``ln_colsum`` are inputs, and
+    all three kernels evaluate ``(acc - mean * colsum) * rstd + bias`` in fp32 (gemm.hip, gemm_pp.hip and gemm_ps.hip
+    epilogues); with integer means and column sums and a power-of-two rstd every step, fused or not, is an integer below
+    2^24 times a power of two.  ``ln_out`` is a side output with its own tolerance and does not touch ``d``."""
+    return not d["geglu"] and not d["euler_out"]
+
+
+def make_exact_tensors(d, rung):
+    """``make_tensors`` with non-zero integers on rung ``rung`` of RUNGS for A, a2 and W, integers in [-8, 8] for the biases
+    and residuals, and integer / power-of-two LayerNorm statistics; buffers, offsets, NaN slack and weight groups as ever."""
+    assert exact_eligible(d)
+    g = torch.Generator().manual_seed(d["_seed"] + 7919 * (rung + 1))
+    return make_tensors(d, g, _Integers(d, g, rung))
+
+
+def exact_unit(d) -> float:
+    """The grid of the stored values: the largest power of two that divides oscale and the residual scales in use."""
+    def low(s):
+        f = abs(float(s))
+        u = 1.0
+        while f != math.floor(f):
+            f, u = f * 2.0, u / 2.0
+        while f % 2.0 == 0.0:
+            f, u = f / 2.0, u * 2.0
+        return u
+    return min([low(d["oscale"])] + [low(d[s]) for r, s in (("res1", "r1scale"), ("res2", "r2scale")) if d[r]])
+
+
+def exact_case(d):
+    """(rung, bufs, views, reference) at the first rung of RUNGS on which
+    * reference(d)["d"] equals its own .half(): the stored fp16 is the integer result itself;
+    * sum |a||w| (with a fold: + |mean||colsum|), the biases and the residuals stay below 2^24 for every output, so that
+      every partial sum of any order is exact in fp32;
+    * with gn_part, every half tile's column sum of |v| and of v^2 stays below 2^24 in units of the output grid.
+    Conditions on the inputs alone.  A draw without a rung is an error of the generator."""
+    k = TAPS[d["mode"]] * d["cin"] + d["cin2"]
+    for rung, (amax, wmax, _thin) in enumerate(RUNGS):
+        bufs, views = make_exact_tensors(d, rung)
+        ref = reference(d, views, fold_formula=True)
+        v = ref["d"]
+        if not torch.equal(v.half().double(), v):
+            continue
+        terms = k * amax * wmax                                   # sum |a||w|
+        if d["ln_stats"]:
+            terms = 2 * (terms + 3 * k * wmax)                    # |mean| <= 3, |colsum| <= K |w|, rstd <= 2
+        assert (terms + 16) * max(1.0, d["oscale"]) + 16 < EXACT_LIMIT        # + biases, residuals (each <= 8)
+        if d["gn_part"]:
+            u = v / exact_unit(d)
+            assert torch.equal(u, u.round())
+            s = half_tile_sums(u.abs())
+            if float(s[..., 0].max()) >= EXACT_LIMIT or float(s[..., 1].max()) >= EXACT_LIMIT:
+                continue
+        return rung, bufs, views, ref
+    raise AssertionError(f"no rung of the value ladder makes this draw exact: {d}")
+
+
+def exact_rung(d) -> int:
+    return exact_case(d)[0]
+
+
+EXACT_DRAWS_PER_ROUTE = 12
+EXACT_MNK = 1e9
+
+
+def exact_seed(route, bm):
+    return 9000 + 10 * route + bm
+
+
+def exact_small(route, bm) -> bool:
+    """Routes whose family serves m <= 1,024 (all but the persistent-stream ones, which want many rows)."""
+    return route != 3
+
+
+def stream_shaped(d, bm) -> bool:
+    """A draw that a forced persistent-stream route keeps (the header's list for sp_gemm_set_route(3): plain rows, whole
+    column tiles, K >= 256, every column stored, none of the options that pin the 256-row ping-pong tiles, bias2 rows that
+    no tile straddles, an even m with a folded LayerNorm)."""
+    bn = {128: 320, -192: 192}.get(bm, 256)
+    rows = {128: 128, -192: 256}.get(bm, bm)
+    return (d["mode"] == LINEAR and d["n"] % bn == 0 and d["cin"] >= 256 and not d["n_store"] and not d["gn_part"] and not d["a2"]
+            and not d["ln_out"] and not d["w_group_rows"] and not (d["ln_stats"] and d["m"] % 2)
+            and not (d["bias2"] and 0 < d["bias2_rows"] < d["m"] and d["bias2_rows"] % rows))
+
+
+def exact_draws(route, bm, count=EXACT_DRAWS_PER_ROUTE):
+    """The exact tests' own seeded series: eligible draws with m * n * K <= 1e9 (the cost is the fp64 reference).  On the
+    persistent-stream routes at most 5 of the 12 are shapes that the family hands to another kernel."""
+    import random
+    seed = exact_seed(route, bm)
+    rng, gen = random.Random(seed), torch.Generator().manual_seed(seed)
+    out, other = [], 0
+    while len(out) < count:
+        d = draw(rng, gen, (route, bm), small=exact_small(route, bm))
+        if not exact_eligible(d) or d["m"] * d["n"] * (TAPS[d["mode"]] * d["cin"] + d["cin2"]) > EXACT_MNK:
+            continue
+        if route == 3 and not stream_shaped(d, bm):
+            other += 1
+            if other > 5:
+                continue
+        out.append(d)
+    return out
+
+
+# Geometries the draws do not reach by name (every route's small-tile or ping-pong kernel takes them).
+EXACT_FIXED = {
+    # a 3 x 3 convolution at stride 2 over odd images: the last output row and column read pixel row hin - 1 and padding
+    "conv_stride2_odd": dict(mode=CONV3X3, n_img=3, hin=7, win=5, hout=4, wout=3, stride=2, m=36, n=256, cin=64, lda=72, ldd=272,
+                             _off={"a": 8, "d": 8}, _seed=101),
+    # two frames of five pixels: every row is a first or a last frame, an outer tap is padding in every row
+    "temporal_two_frames": dict(mode=TEMPORAL3, frames=2, hw=5, m=30, n=256, cin=128, lda=128, ldd=256, res1=FAKE["res1"], ldr1=256,
+                                r1scale=0.5, _off={"a": 0, "d": 0, "res1": 0}, _seed=102),
+}
+
+
+def exact_fixed(name) -> dict:
+    d = blank()
+    d.update({p: FAKE[p] for p in ("a", "w", "d", "zero_page", "bias")})
+    d.update(_broken=None, **EXACT_FIXED[name])
+    assert legal(d) == (True, None) and exact_eligible(d), legal(d)
+    return d
 
 
 def to_struct(d, pointers=None):

@@ -4,7 +4,9 @@ output rows guarded on both sides (any write outside [0, m) x [0, n_store) fails
 usage: fuzz_gemm.py [cases] [seed] [route] [bm]   (route / bm: sp_gemm_set_route, as in tests/test_fuzz_gpu.py;
 route 4 = split-K: few-row shapes with N % 256 == 0 drawn more often and a workspace handed to every call)
        fuzz_gemm.py --descriptor ROUTE BM INDEX   replays one draw of the whole-descriptor fuzz
-       (tests/test_gemm_descriptor_fuzz_gpu.py; the generator and the fp64 reference are tests/gemm_model.py)"""
+       (tests/test_gemm_descriptor_fuzz_gpu.py; the generator and the fp64 reference are tests/gemm_model.py)
+       fuzz_gemm.py --descriptor ROUTE BM INDEX --exact   replays one draw of the bit-exact series on integer operands
+       (tests/test_gemm_exact_gpu.py)"""
 import math, os, random, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -128,20 +130,25 @@ def one(rng, g, stream_shapes=False, splitk=False):
     return e
 
 
-def replay_descriptor(route, bm, index):
+def replay_descriptor(route, bm, index, exact=False):
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import gemm_model
     import test_gemm_descriptor_fuzz_gpu as fz
-    d = gemm_model.route_draws(route, bm, index + 1)[index]
+    d = (gemm_model.exact_draws if exact else gemm_model.route_draws)(route, bm, index + 1)[index]
     print({k: v for k, v in d.items() if v and k not in gemm_model.POINTERS})
     with (ops.gemm_route(3, bm=256, bn=192) if bm == -192 else ops.gemm_route(route, bm=bm)):
+        if exact:
+            import test_gemm_exact_gpu as ex
+            rung, kernel = ex.run_exact(d, ops.load(), ops.zero_page(torch.device(DEV)))
+            print(f"ok: {kernel}, bit-exact on rung {rung} {gemm_model.RUNGS[rung]}")
+            return
         glob, block, kernel = fz.run_draw(d, ops.load(), ops.zero_page(torch.device(DEV)))
     print(f"ok: {kernel}, global rel_l2 {glob:.2e}, worst 64x64 block {block:.2e}")
 
 
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--descriptor":
-        return replay_descriptor(int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]))
+        return replay_descriptor(int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), exact="--exact" in sys.argv[5:])
     cases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
     route = int(sys.argv[3]) if len(sys.argv) > 3 else 0
