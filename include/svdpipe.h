@@ -351,6 +351,32 @@ int sp_dpmpp2m_step_rows_f16(const void *state, const void *eps_cond, const void
                              int64_t ld_eps, const float *guidance, int64_t ld_guidance, void *out_state,
                              float sigma, float a, float b, float c1, float c2,
                              int batch, int frames, int h, int w, void *stream);
+/* Long videos: the two sampler tails behind overlapping frame windows (csrc/window.hip).  A latent
+ * of frames_total frames is cut into n_win = (frames_total - window)/stride + 1 windows of `window` frames, window k covering
+ * global frames k*stride .. k*stride + window - 1 (1 <= stride <= window, (frames_total - window) % stride == 0); the UNet ran
+ * on every window and left its eps rows in ONE buffer, NHWC rows [n_win][B][window][H*W][ld_eps]: window k of all videos
+ * starts at row k*B*window*H*W.  weights is the normalised fp32 table [n_win][window] of models/window_plan.py (over the
+ * windows covering a global frame it sums to 1).  Per element of global frame f = k*stride + p:
+ *   e_k = eps_u + g[b,p]*(eps_c - eps_u)   per window, in fp16, rounding for rounding as sp_euler_step_rows_f16; e_k = eps_c
+ *                                          if !eps_uncond.  Guidance follows the POSITION p in the window (guidance is
+ *                                          [window] with ld_guidance 0, or [B][ld_guidance >= window]), not the global frame
+ *   e   = sum over the covering k, ascending, of weights[k][p]*e_k     fp32 fmaf from 0, never rounded to fp16
+ * and the update is that of the single-window function with e in place of its eps: latent/out (B,4,frames_total,H,W) for
+ * Euler, state/out_state (B,8,frames_total,H,W) for DPM-Solver++(2M) (D -> channels 4-7; with c2 == 0 channels 4-7 of state
+ * are not read).  With n_win == 1 (weights 1.0) the bytes are those of sp_euler_step_rows_f16 / sp_dpmpp2m_step_rows_f16.
+ * Every element of the input is read before the thread that owns it stores: out may be the input itself.  Refused, without
+ * launching: null pointers (weights included), stride outside [1, window], window > frames_total, a total that is not window
+ * plus whole strides, n_win other than the plan's, ld_guidance in (0, window), out overlapping the input unless it IS the
+ * input, and everything the single-window functions refuse. */
+int sp_euler_step_windows_f16(const void *latent, const void *eps_cond, const void *eps_uncond,
+                              int64_t ld_eps, const float *guidance, int64_t ld_guidance, void *out, float sigma,
+                              float sigma_next, int b, int frames_total, int h, int w,
+                              int window, int stride, int n_win, const float *weights /*[n_win][window]*/, void *stream);
+int sp_dpmpp2m_step_windows_f16(const void *state, const void *eps_cond, const void *eps_uncond,
+                                int64_t ld_eps, const float *guidance, int64_t ld_guidance, void *out_state,
+                                float sigma, float a, float b, float c1, float c2,
+                                int batch, int frames_total, int h, int w,
+                                int window, int stride, int n_win, const float *weights /*[n_win][window]*/, void *stream);
 /* channel concat of two NHWC tensors (torch.cat([hidden, skip], dim=1) in the up blocks) */
 int sp_concat_channels_f16(const void *a, int ca, const void *b, int cb, void *out, int64_t rows,
                            void *stream);
@@ -763,9 +789,10 @@ int sp_webp_code(const void *residual, const void *modes, const void *flags, int
 /* ---------------------------------------------------------------------------------------------
  * Measurement aid (bench.py `roofline.clock_ghz_live`; the reference has no counterpart -- its benchmark reads no clocks,
  * /root/reference/src/modes/benchmark.py:170-262).  One time stamp in stream order: `blocks` one-wave workgroups each write
- * four u64 words to out[block][4]: the id of the XCD the workgroup ran on (HW_REG_XCC_ID), the shader-clock counter
- * (s_memtime), the constant 100 MHz counter (s_memrealtime), and 1.  Two stamps taken on the same XCD before and after a
- * stretch of work give the shader clock held in between: GHz = 0.1 * (shader ticks) / (100-MHz ticks).
+ * four u64 words to out[block][4]: the id of the place the workgroup ran on (bits 3:0 the XCD, HW_REG_XCC_ID; bits 11:4 the
+ * CU within it, HW_REG_HW_ID's CU, array and shader engine), the shader-clock counter (s_memtime), the constant 100 MHz
+ * counter (s_memrealtime), and 1.  Two stamps taken on the same CU before and after a stretch of work give the shader clock
+ * held in between: GHz = 0.1 * (shader ticks) / (100-MHz ticks); the counters of two CUs need not share an origin.
  * ------------------------------------------------------------------------------------------- */
 int sp_clock_stamp(void *out, int blocks, void *stream);
 

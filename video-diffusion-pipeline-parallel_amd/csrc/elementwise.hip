@@ -259,14 +259,18 @@ extern "C" int sp_sinusoid_f16(const float *values, void *out, int count, int di
 // ---------------------------------------------------------------------------------------------------------------------
 // Measurement aid (bench.py `roofline.clock_ghz_live`): a time stamp of both counters a wave can read -- the shader-clock
 // counter (s_memtime) and the constant 100 MHz counter (s_memrealtime) -- from `blocks` one-wave workgroups, each with the
-// id of the XCD it ran on (the shader-clock counters of different XCDs are not assumed to share an origin).  Two stamps on
-// the same XCD, one before and one after a stretch of work, give the shader clock the chip held in between:
-// 0.1 GHz x (shader ticks) / (100 MHz ticks).  No persistent kernel: a stamp is a ~2 us launch in stream order.
+// id of the place it ran on: the XCD in bits 3:0, the CU within it (shader engine, array, CU) in bits 11:4.  The shader-clock
+// counters of different CUs are not assumed to share an origin, not even within one XCD (profiles/clock_stamp_per_cu.txt: up to 3e8
+// ticks between the workgroups of one stamp on one XCD, and the dispatcher starts each launch on other CUs than the last).
+// Two stamps on the same CU, one before and one after a stretch of work, give the shader clock the chip held in between:
+// 0.1 GHz x (shader ticks) / (100 MHz ticks); enough workgroups per stamp (the caller's choice) put some on every CU.  No
+// persistent kernel: a stamp is a 3 us launch in stream order, at 64 workgroups as at 1,024.
 namespace {
 __global__ void clock_stamp_kernel(unsigned long long *out) {
   if (threadIdx.x != 0) return;
   unsigned long long *o = out + (size_t)blockIdx.x * 4;
-  o[0] = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 20);     // HW_REG_XCC_ID, bits 3:0
+  o[0] = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 20)      // HW_REG_XCC_ID, bits 3:0
+         | (unsigned long long)__builtin_amdgcn_s_getreg((8 - 1) << 11 | 8 << 6 | 4) << 4;   // HW_REG_HW_ID: CU, SH, SE (15:8)
   o[1] = __builtin_amdgcn_s_memtime();
   o[2] = wall_clock64();
   o[3] = 1;

@@ -79,6 +79,8 @@ SIGNATURES = {
     "sp_euler_step_f16": (_I, [_P, _P, _P, _L, _P, _P, _F, _F, _I, _I, _I, _I, _P]),
     "sp_euler_step_rows_f16": (_I, [_P, _P, _P, _L, _P, _L, _P, _F, _F, _I, _I, _I, _I, _P]),
     "sp_dpmpp2m_step_rows_f16": (_I, [_P, _P, _P, _L, _P, _L, _P, _F, _F, _F, _F, _F, _I, _I, _I, _I, _P]),
+    "sp_euler_step_windows_f16": (_I, [_P, _P, _P, _L, _P, _L, _P, _F, _F, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "sp_dpmpp2m_step_windows_f16": (_I, [_P, _P, _P, _L, _P, _L, _P, _F, _F, _F, _F, _F, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "sp_concat_channels_f16": (_I, [_P, _I, _P, _I, _P, _L, _P]),
     "sp_add_rowvec_f16": (_I, [_P, _P, _P, _L, _I, _P]),
     "sp_softmax_rows_f16": (_I, [_P, _L, _L, _I, _P]),

@@ -866,11 +866,13 @@ def webp_code(residual, modes, flags, out, out_len, ws, *, pred_bits, group_bits
 
 class ClockStamps:
     """Stamps of the shader-clock counter against the constant 100 MHz counter, taken in stream order between other work
-    (``sp_clock_stamp``; bench.py ``roofline.clock_ghz_live``).  ``stamp()`` enqueues one on the current stream (a ~2 us
-    launch of 64 one-wave workgroups, each noting the XCD it ran on); ``ghz()`` (after a synchronise) pairs the first and the
-    last stamp XCD by XCD and returns (GHz, seconds between the stamps, XCDs seen in both) -- the shader clock the chip held
-    over that stretch -- or None with fewer than two stamps."""
-    BLOCKS = 64
+    (``sp_clock_stamp``; bench.py ``roofline.clock_ghz_live``).  ``stamp()`` enqueues one on the current stream (a 3 us
+    launch of 1,024 one-wave workgroups, four a CU on average, each noting where it ran: the XCD in bits 3:0 of its id, the CU above
+    them); ``ghz()`` (after a synchronise) pairs the first and the last stamp CU by CU -- the counters of two CUs need not
+    share an origin, not even within one XCD, and a launch of fewer workgroups than CUs lands on other CUs every time --
+    takes each XCD's median CU and returns (GHz, seconds between the stamps, XCDs seen in both) -- the shader clock the
+    chip held over that stretch -- or None with fewer than two stamps or no CU in both.  Measured: profiles/clock_stamp_per_cu.txt."""
+    BLOCKS = 1024
 
     def __init__(self, device, capacity):
         import torch
@@ -888,16 +890,17 @@ class ClockStamps:
         b = self.buf[:self.n].cpu()
         real = b[:, :, 2].double().mean(dim=1)                 # when each stamp ran (its workgroups: within microseconds)
         first, last = b[int(real.argmin())], b[int(real.argmax())]
-        ratios, secs = [], []
-        for x in sorted(set(first[:, 0].tolist()) & set(last[:, 0].tolist())):
-            f, l = first[first[:, 0] == x][0], last[last[:, 0] == x][0]
-            dr = int(l[2] - f[2])
+        per_xcd = {}
+        rows = [{r[0]: r for r in reversed(stamp.tolist())} for stamp in (first, last)]      # a CU's first workgroup
+        for place in sorted(rows[0].keys() & rows[1].keys()):
+            f, l = rows[0][place], rows[1][place]
+            dr = l[2] - f[2]
             if dr > 0:
-                ratios.append(0.1 * int(l[1] - f[1]) / dr)
-                secs.append(dr / 1e8)
-        if not ratios:
+                per_xcd.setdefault(place & 15, []).append((0.1 * (l[1] - f[1]) / dr, dr / 1e8))
+        if not per_xcd:
             return None
-        return sum(ratios) / len(ratios), sum(secs) / len(secs), len(ratios)
+        mid = [sorted(pairs)[len(pairs) // 2] for pairs in per_xcd.values()]
+        return sum(r for r, _ in mid) / len(mid), sum(s for _, s in mid) / len(mid), len(mid)
 
 
 def euler_step(latent, eps_cond, eps_uncond, guidance, out, *, ld_eps, sigma, sigma_next, b, frames, h, w,
@@ -922,6 +925,49 @@ def dpmpp2m_step(state, eps_cond, eps_uncond, guidance, out_state, *, ld_eps, si
     _check(load().sp_dpmpp2m_step_rows_f16(state.data_ptr(), eps_cond.data_ptr(), _ptr(eps_uncond), ld_eps, _ptr(guidance),
                                            int(ld_guidance), out_state.data_ptr(), sigma, a, b, c1, c2, batch, frames, h, w,
                                            _stream()), "sp_dpmpp2m_step_rows_f16")
+    return out_state
+
+
+def _window_args(name, tensors, channels, batch, frames_total, h, w, eps_cond, eps_uncond, ld_eps, window, n_win, weights):
+    """Shapes the window tails cannot see through raw pointers (``tensors``: name -> the stepped tensor and its output)."""
+    for what, t in tensors.items():
+        if _f16(t, what).shape != (batch, channels, frames_total, h, w) or not t.is_contiguous():
+            raise ValueError(f"{name}: {what} must be a contiguous ({batch}, {channels}, {frames_total}, {h}, {w}) tensor; "
+                             f"got {tuple(t.shape)}, strides {tuple(t.stride())}")
+    rows = n_win * batch * window * h * w
+    for what, t in (("eps_cond", eps_cond), ("eps_uncond", eps_uncond)):
+        if t is not None and (_f16(t, what).numel() != rows * ld_eps or not t.is_contiguous()):
+            raise ValueError(f"{name}: {what} must hold [n_win={n_win}][B={batch}][window={window}][{h * w}][ld_eps={ld_eps}] "
+                             f"contiguous values; got {tuple(t.shape)}")
+    if weights.dtype != torch.float32 or weights.numel() != n_win * window or not weights.is_contiguous():
+        raise ValueError(f"{name}: weights must be a contiguous float32 [{n_win}][{window}] table; got {weights.dtype} "
+                         f"{tuple(weights.shape)}")
+
+
+def euler_step_windows(latent, eps_cond, eps_uncond, guidance, out, *, ld_eps, sigma, sigma_next, b, frames_total, h, w,
+                       window, stride, n_win, weights, ld_guidance=0):
+    """The Euler update of ``latent`` (B,4,F_total,H,W) behind the eps rows of ``n_win`` overlapping frame windows
+    (``[n_win][B][window][H*W][ld_eps]``), blended with ``weights`` (fp32 ``[n_win][window]``, ``models.window_plan.plan``);
+    ``guidance`` is indexed by the position in the window (``sp_euler_step_windows_f16``)."""
+    _window_args("euler_step_windows", {"latent": latent, "out": out}, 4, b, frames_total, h, w, eps_cond, eps_uncond, ld_eps,
+                 window, n_win, weights)
+    _check(load().sp_euler_step_windows_f16(latent.data_ptr(), eps_cond.data_ptr(), _ptr(eps_uncond), ld_eps, _ptr(guidance),
+                                            int(ld_guidance), out.data_ptr(), sigma, sigma_next, b, frames_total, h, w,
+                                            window, stride, n_win, weights.data_ptr(), _stream()),
+           "sp_euler_step_windows_f16")
+    return out
+
+
+def dpmpp2m_step_windows(state, eps_cond, eps_uncond, guidance, out_state, *, ld_eps, sigma, a, b, c1, c2, batch,
+                         frames_total, h, w, window, stride, n_win, weights, ld_guidance=0):
+    """``dpmpp2m_step`` of the 8-channel ``state`` (B,8,F_total,H,W) behind the eps rows of ``n_win`` overlapping frame
+    windows; layouts as for ``euler_step_windows`` (``sp_dpmpp2m_step_windows_f16``)."""
+    _window_args("dpmpp2m_step_windows", {"state": state, "out_state": out_state}, 8, batch, frames_total, h, w, eps_cond,
+                 eps_uncond, ld_eps, window, n_win, weights)
+    _check(load().sp_dpmpp2m_step_windows_f16(state.data_ptr(), eps_cond.data_ptr(), _ptr(eps_uncond), ld_eps,
+                                              _ptr(guidance), int(ld_guidance), out_state.data_ptr(), sigma, a, b, c1, c2,
+                                              batch, frames_total, h, w, window, stride, n_win, weights.data_ptr(),
+                                              _stream()), "sp_dpmpp2m_step_windows_f16")
     return out_state
 
 

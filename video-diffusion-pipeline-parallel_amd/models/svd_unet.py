@@ -25,7 +25,7 @@ from dataclasses import dataclass
 import torch
 import torch.nn as nn
 
-from . import euler_schedule, solver_schedule
+from . import euler_schedule, solver_schedule, window_plan
 from .unet_hip import SVDUNetHIP
 from .unet_spec import UNetConfig, random_state_dict
 
@@ -88,6 +88,9 @@ class StableVideoUNet(nn.Module):
         num_train_timesteps: int = 1000,
         batched_cfg: bool = False,
         sampler: str = "euler",
+        window_stride: int | None = None,
+        window_weights: str = "triangle",
+        windows_per_call: int = 1,
     ) -> None:
         """``batched_cfg`` (extension): run the unconditional and conditional passes of
         classifier-free guidance as ONE batch-2 UNet forward instead of two sequential passes
@@ -97,8 +100,25 @@ class StableVideoUNet(nn.Module):
         DPM-Solver++(2M), second order with still one UNet evaluation per step.  Its history -- the previous step's
         denoised estimate -- rides in the latent: ``forward`` then takes and returns (B,8,F,H,W), channels 0-3 the sample,
         channels 4-7 the estimate (``init_state`` / ``sample_of``), the model keeps no state between calls, and the
-        steps are called in index order (0, 1, 2, ...)."""
+        steps are called in index order (0, 1, 2, ...).
+
+        ``window_stride`` (extension): long videos by temporal co-denoising.  ``forward`` then accepts a
+        latent of more frames than the conditioning's ``num_frames`` = W: every step runs the UNet on overlapping windows of
+        W frames, ``window_stride`` apart (``models/window_plan.py``), and ONE sampler update follows behind all windows' eps
+        rows, blended per frame with ``window_weights`` ("triangle": a window counts most at its centre; "uniform").
+        ``windows_per_call`` windows are stacked as extra batch rows of one UNet call.  None: every path is the unwindowed
+        one."""
         super().__init__()
+        if window_stride is not None and int(window_stride) < 1:
+            raise ValueError(f"window_stride must be a positive frame count or None; got {window_stride}")
+        if window_weights not in window_plan.WEIGHTS:
+            raise ValueError(f"window_weights must be one of {window_plan.WEIGHTS}; got {window_weights!r}")
+        if int(windows_per_call) < 1:
+            raise ValueError(f"windows_per_call must be at least 1; got {windows_per_call}")
+        self.window_stride = None if window_stride is None else int(window_stride)
+        self.window_weights = window_weights
+        self.windows_per_call = int(windows_per_call)
+        self._window_plans: dict = {}    # (frames_total, window) -> (plan, its weight table on the device)
         if sampler not in solver_schedule.SAMPLERS:
             raise ValueError(f"sampler must be one of {solver_schedule.SAMPLERS}; got {sampler!r}")
         self.sampler = sampler
@@ -180,6 +200,8 @@ class StableVideoUNet(nn.Module):
         attention_slice_size: int | str = "auto",
         device="cuda",
         sampler: str = "euler",
+        window_stride: int | None = None,
+        window_weights: str = "triangle",
         **kwargs,
     ) -> "StableVideoUNet":
         """Load ``<model_id>/unet/diffusion_pytorch_model*.safetensors`` from a LOCAL directory.
@@ -228,18 +250,21 @@ class StableVideoUNet(nn.Module):
             )
         if timesteps is None:
             timesteps = cls._default_timestep_schedule(num_steps=25)
-        return cls(unet=SVDUNetHIP(cfg, sd, device), timesteps=timesteps, dtype=torch_dtype, sampler=sampler)
+        return cls(unet=SVDUNetHIP(cfg, sd, device), timesteps=timesteps, dtype=torch_dtype, sampler=sampler,
+                   window_stride=window_stride, window_weights=window_weights)
 
     @classmethod
     def from_random_init(cls, timesteps: Sequence[int], *, config: UNetConfig | None = None, seed: int = 0,
                          device="cuda", fp8_attention: bool | None = None,
-                         long_attention: bool | None = None, sampler: str = "euler") -> "StableVideoUNet":
+                         long_attention: bool | None = None, sampler: str = "euler",
+                         window_stride: int | None = None, window_weights: str = "triangle") -> "StableVideoUNet":
         """Random weights of the exact SVD architecture (benchmarks / tests; no checkpoint needed)."""
         cfg = config or UNetConfig.svd()
         sd = random_state_dict(cfg, seed=seed, device=device, dtype=torch.float16)
         unet = SVDUNetHIP(cfg, sd, device, fp8_attention=fp8_attention, long_attention=long_attention)
         del sd
-        return cls(unet=unet, timesteps=timesteps, sampler=sampler)
+        return cls(unet=unet, timesteps=timesteps, sampler=sampler, window_stride=window_stride,
+                   window_weights=window_weights)
 
     def enable_graphs(self, enabled: bool = True) -> None:
         """Replay each diffusion step from a captured HIP graph (one graph per step index and latent shape).
@@ -389,7 +414,7 @@ class StableVideoUNet(nn.Module):
             release()
 
     # ------------------------------------------------------------------ one diffusion step
-    def _unet_pass(self, latent, image_latents, embeddings, in_scale, step, euler=None, added_ids32=None):
+    def _unet_pass(self, latent, image_latents, embeddings, in_scale, step, euler=None, added_ids32=None, eps_out=None):
         from ..hip import ops
 
         b, _, f, h, w = latent.shape
@@ -398,7 +423,8 @@ class StableVideoUNet(nn.Module):
                        cpad=self.unet.cin_pad)
         return self.unet.forward_rows(rows, b=b, frames=f, h=h, w=w, t_value=self._t_dev[step:step + 1],
                                       ctx16=embeddings.reshape(b, -1),
-                                      added_ids32=self._added_ids32 if added_ids32 is None else added_ids32, euler=euler)
+                                      added_ids32=self._added_ids32 if added_ids32 is None else added_ids32, euler=euler,
+                                      **({} if eps_out is None else {"eps_out": eps_out}))
 
     @torch.inference_mode()
     def forward(self, latent: torch.Tensor, step: int, conditioning: VideoConditioning | None = None) -> torch.Tensor:
@@ -437,7 +463,17 @@ class StableVideoUNet(nn.Module):
         elif latent.dim() != 5 or latent.shape[1] != 4:
             raise ValueError(f"latent must be (B, 4, F, H, W); got {tuple(latent.shape)}")
         sample_shape = (latent.shape[0], 4) + tuple(latent.shape[2:])
-        if tuple(cond.image_latents.shape) != sample_shape:
+        frames = latent.shape[2]
+        if self.window_stride is not None:
+            # a long latent against a conditioning prepared for one window of W = num_frames frames
+            frames = cond.num_frames
+            self._window_plan(latent.shape[2], frames)         # ValueError naming (frames_total, window, stride)
+            sample_shape = sample_shape[:2] + (frames,) + sample_shape[3:]
+            if tuple(cond.image_latents.shape) != sample_shape:
+                raise ValueError(f"image_latents {tuple(cond.image_latents.shape)} do not match one window {sample_shape} of "
+                                 f"the latent {tuple(latent.shape)} (window_stride={self.window_stride}: the conditioning is "
+                                 f"prepared for num_frames = the window length)")
+        elif tuple(cond.image_latents.shape) != sample_shape:
             raise ValueError(f"image_latents {tuple(cond.image_latents.shape)} do not match the latent "
                              f"{sample_shape} (set_conditioning was called for another batch / frame count / size)")
         emb = cond.image_embeddings
@@ -448,8 +484,9 @@ class StableVideoUNet(nn.Module):
         if cond.added_ids32.dim() == 2 and cond.added_ids32.shape[0] != latent.shape[0]:
             raise ValueError(f"added time ids for {cond.added_ids32.shape[0]} videos, the latent has {latent.shape[0]}")
         g = cond.guidance32
-        if g is not None and g.shape[-1] != latent.shape[2]:
-            raise ValueError(f"guidance was set for num_frames={g.shape[-1]}, the latent has {latent.shape[2]} frames")
+        if g is not None and g.shape[-1] != frames:
+            raise ValueError(f"guidance was set for num_frames={g.shape[-1]}, the latent has {frames} frames"
+                             + (" per window" if self.window_stride is not None else ""))
         if g is not None and g.dim() == 2 and g.shape[0] != latent.shape[0]:
             raise ValueError(f"guidance rows for {g.shape[0]} videos, the latent has {latent.shape[0]}")
 
@@ -503,6 +540,8 @@ class StableVideoUNet(nn.Module):
         from ..hip import ops
 
         cond = self._cond if cond is None else cond
+        if self.window_stride is not None:
+            return self._forward_windows(latent, step, cond)
         if self.sampler == "dpmpp_2m":
             return self._forward_dpmpp_2m(latent, step, cond)
         b, _, f, h, w = latent.shape
@@ -563,3 +602,67 @@ class StableVideoUNet(nn.Module):
         ops.dpmpp2m_step(state, eps_c, eps_u, cond.guidance32 if eps_u is not None else None, out, ld_eps=eps_c.shape[1],
                          sigma=sigma, a=a, b=b_, c1=c1, c2=c2, batch=b, frames=f, h=h, w=w, ld_guidance=cond.guidance_ld)
         return out
+
+    # ------------------------------------------------------------------ long videos: overlapping frame windows
+    def _window_plan(self, frames_total: int, window: int):
+        """(plan, weight table on the device) of a latent of ``frames_total`` frames cut into windows of ``window``."""
+        key = (int(frames_total), int(window))
+        entry = self._window_plans.get(key)
+        if entry is None:
+            pl = window_plan.plan(frames_total, window, self.window_stride, self.window_weights)
+            entry = self._window_plans[key] = (pl, torch.from_numpy(pl.weights).to(self.unet.device).contiguous())
+        return entry
+
+    def _forward_windows(self, state: torch.Tensor, step: int, cond: VideoConditioning) -> torch.Tensor:
+        """One step of a latent of F_total frames as n_win overlapping windows of W = ``cond.num_frames`` frames: the UNet
+        passes of the unwindowed step on every window's frame slice (``windows_per_call`` windows of all B videos per call,
+        the conditioning rows repeated per window), each call's eps rows stored to its slice of one
+        [n_win][B][W][H*W][4] buffer per pass, then ONE tail behind them (``sp_euler_step_windows_f16`` /
+        ``sp_dpmpp2m_step_windows_f16``).  Both samplers take the stored-eps route: the Euler tail in ``conv_out``'s
+        epilogue cannot see the other windows."""
+        from ..hip import ops
+
+        b, _, ft, h, w = state.shape
+        win = cond.num_frames
+        pl, weights = self._window_plan(ft, win)
+        sigma = self._sigma_host[step]
+        in_scale = 1.0 / math.sqrt(sigma * sigma + 1.0)
+        x = state if self.state_channels == 4 else state[:, :4]
+        ld_eps = self.unet.cfg.out_channels
+        rows = b * win * h * w                                  # eps rows of one window of all videos
+        eps_c = torch.empty((pl.n_win * rows, ld_eps), dtype=torch.float16, device=state.device)
+        eps_u = torch.empty_like(eps_c) if cond.guided else None
+        ids = cond.added_ids32
+        for k0 in range(0, pl.n_win, self.windows_per_call):
+            n = min(self.windows_per_call, pl.n_win - k0)
+            # [window][video] batch rows: the layout of the eps buffer
+            xs = torch.cat([x[:, :, s:s + win] for s in pl.starts[k0:k0 + n]], dim=0).contiguous()
+            dst = slice(k0 * rows, (k0 + n) * rows)
+
+            def rep(t):
+                return t if n == 1 else torch.cat([t] * n, dim=0)
+
+            ids_n = ids if ids.dim() == 1 else rep(ids)
+            if cond.guided and self.batched_cfg:
+                both = self._unet_pass(torch.cat([xs, xs], dim=0),
+                                       torch.cat([rep(cond.uncond_image_latents), rep(cond.image_latents)], dim=0),
+                                       torch.cat([rep(cond.uncond_embeddings), rep(cond.image_embeddings)], dim=0), in_scale,
+                                       step, added_ids32=ids_n if ids.dim() == 1 else torch.cat([ids_n, ids_n], dim=0))
+                eps_u[dst].copy_(both[:n * rows])
+                eps_c[dst].copy_(both[n * rows:])
+                continue
+            if cond.guided:
+                self._unet_pass(xs, rep(cond.uncond_image_latents), rep(cond.uncond_embeddings), in_scale, step,
+                                added_ids32=ids_n, eps_out=eps_u[dst])
+            self._unet_pass(xs, rep(cond.image_latents), rep(cond.image_embeddings), in_scale, step, added_ids32=ids_n,
+                            eps_out=eps_c[dst])
+        out = torch.empty_like(state)
+        common = dict(ld_eps=ld_eps, h=h, w=w, window=win, stride=pl.stride, n_win=pl.n_win, weights=weights,
+                      frames_total=ft, ld_guidance=cond.guidance_ld)
+        guidance = cond.guidance32 if cond.guided else None
+        if self.sampler == "dpmpp_2m":
+            a, b_, c1, c2 = self._solver_coef[step]
+            return ops.dpmpp2m_step_windows(state, eps_c, eps_u, guidance, out, sigma=sigma, a=a, b=b_, c1=c1, c2=c2,
+                                            batch=b, **common)
+        return ops.euler_step_windows(state, eps_c, eps_u, guidance, out, sigma=sigma,
+                                      sigma_next=self._sigma_host[step + 1], b=b, **common)

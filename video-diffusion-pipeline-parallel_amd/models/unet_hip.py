@@ -623,7 +623,7 @@ class SVDUNetHIP:
         return self._gemm(r, p["pout"], mix, res1=x.t, r1scale=1.0, out=out, gn_next=gn_next)
 
     # ------------------------------------------------------------------ forward
-    def forward_rows(self, x_rows, *, b, frames, h, w, t_value, ctx16, added_ids32, euler=None):
+    def forward_rows(self, x_rows, *, b, frames, h, w, t_value, ctx16, added_ids32, euler=None, eps_out=None):
         """x_rows: fp16 [B*F*H*W][cin_pad] (see ``sp_pack_input_f16``); ``t_value``: fp32 device tensor [1]
         (continuous timestep) or [B] (one per video); ``ctx16``: fp16 [B][cross_dim]; ``added_ids32``: fp32 device [3]
         or [B][3] (one (fps-1, motion bucket, noise aug) triple per video).  A [1] timestep with [3] ids is shared by
@@ -632,7 +632,8 @@ class SVDUNetHIP:
         Returns eps rows fp16 [B*F*H*W][out_channels].  With ``euler`` (dict: latent, out, sigma, sigma_next and
         optionally eps_uncond + guidance + ld_eps) the last convolution's epilogue applies the guidance mix and the
         Euler update itself (ref svd_unet.py:410-439): ``euler["out"]`` receives the new latent, the
-        eps rows are not written and ``None`` is returned."""
+        eps rows are not written and ``None`` is returned.  ``eps_out``: where the eps rows go (fp16 [B*F*H*W][out_channels],
+        e.g. one window's slice of a larger buffer) instead of a fresh tensor."""
         cfg, dev = self.cfg, self.device
         if h % 8 or w % 8:
             raise ValueError("latent height/width must be multiples of 8 (three stride-2 levels)")
@@ -731,7 +732,7 @@ class SVDUNetHIP:
         if euler is not None:
             self._gemm(r, self.conv_out, x, conv=geom, euler=dict(euler, frames=r.f, hw=r.hw))
             return None
-        return self._gemm(r, self.conv_out, x, conv=geom).t
+        return self._gemm(r, self.conv_out, x, conv=geom, out=eps_out).t
 
     # diffusers-style call (sample (B,F,8,H,W)) – used by parity tests and as a drop-in `unet`
     def __call__(self, sample, timestep, encoder_hidden_states, added_time_ids, return_dict=False, per_video=False):

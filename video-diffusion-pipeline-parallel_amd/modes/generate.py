@@ -7,6 +7,14 @@ a LOCAL checkpoint directory in the hub layout; ``--random-init`` runs the exact
 
     python -m vdpp_amd.modes.generate --random-init --input-image in.png --output out.gif
 
+``--window-frames W --window-stride S`` makes a video longer than the model's native frame count: ``--num-frames`` is then the
+total, the conditioning is prepared for W frames, and every step denoises the long latent as overlapping windows of W frames
+fused in the sampler update (``StableVideoUNet(window_stride=)``); decode and every output format
+receive all ``--num-frames`` frames:
+
+    python -m vdpp_amd.modes.generate --random-init --input-image in.png --num-frames 28 --window-frames 14 \
+        --window-stride 7 --output out.gif
+
 Every rank builds the conditioning from the file itself -- the image kernels, CLIP and the VAE encoder are deterministic
 and the augmentation noise comes from a seeded CPU generator, so nothing is broadcast (the reference encodes on every rank
 as well, ref ``:250-300``).  The steps go through ``run_pipeline_latents`` as in ``production.py``; the rank that ends up
@@ -48,6 +56,14 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--height", type=int, default=576)
     p.add_argument("--width", type=int, default=1024)
     p.add_argument("--num-frames", type=int, default=14)
+    p.add_argument("--window-frames", type=int, default=None,
+                   help="long videos: the model's native frame count W; --num-frames is then the total, denoised as "
+                        "overlapping windows of W frames (needs --window-stride)")
+    p.add_argument("--window-stride", type=int, default=None,
+                   help="frames between the starts of consecutive windows, from 1 to W; --num-frames must be W plus a whole "
+                        "number of strides")
+    p.add_argument("--window-weights", type=str, default="triangle", choices=["triangle", "uniform"],
+                   help="how the windows covering a frame are blended: weighted most at a window's centre, or equally")
     p.add_argument("--total-steps", type=int, default=25)
     p.add_argument("--sampler", type=str, default="euler", choices=["euler", "dpmpp_2m"],
                    help="euler: the reference's first-order update; dpmpp_2m: DPM-Solver++(2M), second order at one UNet "
@@ -76,6 +92,21 @@ def parse_args(argv=None) -> argparse.Namespace:
         p.error("--jpeg-quality must be from 1 to 100")
     if args.height % 8 or args.width % 8:
         p.error("--height and --width must be multiples of 8")
+    if (args.window_frames is None) != (args.window_stride is None):
+        p.error("--window-frames and --window-stride go together")
+    if args.window_frames is not None:
+        from ..models import window_plan
+
+        w, st = args.window_frames, args.window_stride
+        if w < 1 or not 1 <= st <= w:
+            p.error(f"--window-stride {st} must be from 1 to --window-frames {w}")
+        if args.num_frames < w:
+            p.error(f"--num-frames {args.num_frames} is less than --window-frames {w}: the total must be at least one window; "
+                    f"the nearest legal totals are {w} and {w + st}")
+        if (args.num_frames - w) % st:
+            lo, hi = window_plan.legal_totals(args.num_frames, w, st)
+            p.error(f"--num-frames {args.num_frames} is not --window-frames {w} plus a whole number of strides of {st}: "
+                    f"the nearest legal totals are {lo} and {hi}")
     return args
 
 
@@ -113,14 +144,16 @@ def _build_engines(args, timesteps, device):
         ucfg = UNetConfig.tiny(64) if args.tiny else UNetConfig.svd()
         spec = CLIPVisionSpec.tiny(ucfg.cross_attention_dim) if args.tiny else CLIPVisionSpec.svd()
         vcfg = VAEDecoderConfig.tiny(64) if args.tiny else VAEDecoderConfig.svd()
-        model = StableVideoUNet.from_random_init(timesteps, config=ucfg, seed=args.seed, device=device, sampler=args.sampler)
+        model = StableVideoUNet.from_random_init(timesteps, config=ucfg, seed=args.seed, device=device, sampler=args.sampler,
+                                                 window_stride=args.window_stride, window_weights=args.window_weights)
         clip = CLIPVisionHIP(spec, clip_random_state_dict(spec, seed=args.seed + 1, device=device), device)
         enc = ImageEncoderHIP(vcfg, random_encoder_state_dict(vcfg, seed=args.seed + 2, device=device), device)
         return model, clip, enc, lambda: TemporalDecoderHIP(vcfg, random_state_dict(vcfg, seed=args.seed + 3, device=device),
                                                             device)
     from ..models.edge_stages import load_edge_engines
 
-    model = StableVideoUNet.from_pretrained(args.model_id, timesteps=timesteps, device=device, sampler=args.sampler)
+    model = StableVideoUNet.from_pretrained(args.model_id, timesteps=timesteps, device=device, sampler=args.sampler,
+                                            window_stride=args.window_stride, window_weights=args.window_weights)
     clip, enc, dec = load_edge_engines(args.model_id, device)
     return model, clip, enc, lambda: dec
 
@@ -159,13 +192,21 @@ def main(argv=None) -> None:
             mean, std = _clip_normalisation(args.model_id)
             front = ImageFrontEnd(device, args.height, args.width, clip_size=clip.spec.image_size, clip_mean=mean, clip_std=std)
             noise = torch.randn((1, 3, args.height, args.width), generator=torch.Generator().manual_seed(args.seed))
-            emb, image_latents = encode_image_u8(image, front, clip, enc, args.num_frames, noise=noise,
+            # with windows the model is conditioned for one window; the latent, the decode and the file hold the total
+            cond_frames = args.window_frames or args.num_frames
+            emb, image_latents = encode_image_u8(image, front, clip, enc, cond_frames, noise=noise,
                                                  noise_aug_strength=args.noise_aug_strength)
             del clip, enc, front
             model.set_conditioning(emb, image_latents, fps=args.fps, motion_bucket_id=args.motion_bucket_id,
                                    noise_aug_strength=args.noise_aug_strength, guidance_scale=args.guidance_scale,
-                                   num_frames=args.num_frames)
-            shape = torch.Size((1, 4, args.num_frames, args.height // 8, args.width // 8))
+                                   num_frames=cond_frames)
+            if args.window_frames is not None:
+                from ..models import window_plan
+
+                shape = torch.Size(window_plan.noise_shape(1, args.num_frames, args.height, args.width, args.window_frames,
+                                                           args.window_stride))
+            else:
+                shape = torch.Size((1, 4, args.num_frames, args.height // 8, args.width // 8))
             # what a stage boundary carries: the sample, and with dpmpp_2m the solver's history behind it (8 channels)
             carried = torch.Size((1, model.state_channels) + tuple(shape[2:]))
             spec = LatentSpec(shape=carried, dtype=torch.float16, device=device)
