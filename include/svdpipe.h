@@ -325,7 +325,10 @@ int sp_attn_spatial_fp8(const void *q, const void *k, const void *v, void *o, in
  * (channels 0-3 scaled latent, 4-7 image latents, rest zero): svd_unet.py:382,414-415 */
 int sp_pack_input_f16(const void *latent, const void *image_latents, void *out, float in_scale,
                       int b, int frames, int h, int w, int cpad, void *stream);
-/* v-prediction Euler update with optional CFG, fp32 math (svd_unet.py:410-411,425-439):
+/* The sampler tails behind stored eps rows: one kernel (csrc/sampler_tail.hip; arithmetic: csrc/sampler_math.h).  All five
+ * entry points refuse, without launching: null pointers, eps_uncond without guidance, ld_eps no positive multiple of 4,
+ * dimensions that are not positive, ld_guidance in (0, frames), sigma <= 0, an out that overlaps the input unless it IS the input.
+ * v-prediction Euler update with optional CFG, fp32 math (svd_unet.py:410-411,425-439):
  * eps = eps_u + gs[f]*(eps_c - eps_u) if eps_uncond!=NULL else eps_c;
  * x' = x + ((x - (eps*c_out + x*c_skip))/sigma)*dt.  eps_* are NHWC [B*F*H*W][ld_eps]; latent and
  * out are (B,4,F,H,W). */
@@ -337,7 +340,7 @@ int sp_euler_step_f16(const void *latent, const void *eps_cond, const void *eps_
 int sp_euler_step_rows_f16(const void *latent, const void *eps_cond, const void *eps_uncond,
                            int64_t ld_eps, const float *guidance, int64_t ld_guidance, void *out, float sigma,
                            float sigma_next, int b, int frames, int h, int w, void *stream);
-/* DPM-Solver++(2M) update (csrc/solver.hip), the second-order multistep sampler with one UNet evaluation per step.  The
+/* DPM-Solver++(2M) update, the second-order multistep sampler with one UNet evaluation per step.  The
  * solver's history rides in the latent: state and out_state are fp16 (B,8,F,H,W), channels 0-3 the sample x, channels
  * 4-7 the previous step's denoised estimate D_prev.  Per element, fp32 math on fp16 storage:
  *   e  = eps_u + g[b,f]*(eps_c - eps_u)   evaluated in fp16 exactly as sp_euler_step_rows_f16 does; e = eps_c if !eps_uncond
@@ -351,7 +354,7 @@ int sp_dpmpp2m_step_rows_f16(const void *state, const void *eps_cond, const void
                              int64_t ld_eps, const float *guidance, int64_t ld_guidance, void *out_state,
                              float sigma, float a, float b, float c1, float c2,
                              int batch, int frames, int h, int w, void *stream);
-/* Long videos: the two sampler tails behind overlapping frame windows (csrc/window.hip).  A latent
+/* Long videos: the two sampler tails behind overlapping frame windows.  A latent
  * of frames_total frames is cut into n_win = (frames_total - window)/stride + 1 windows of `window` frames, window k covering
  * global frames k*stride .. k*stride + window - 1 (1 <= stride <= window, (frames_total - window) % stride == 0); the UNet ran
  * on every window and left its eps rows in ONE buffer, NHWC rows [n_win][B][window][H*W][ld_eps]: window k of all videos

@@ -142,7 +142,7 @@ def mint_svd_step():
         arrays["init_noise_sigma"] = np.float64(model.init_noise_sigma)
         for gs_name, gs in (("nocfg", None), ("cfg3", 3.0)):
             model.set_conditioning(emb, img, guidance_scale=gs, num_frames=shape[2])
-            arrays[f"added_time_ids.{dt_name}"] = model._added_time_ids.float().numpy()
+            arrays[f"added_time_ids.{dt_name}"] = model._cond.added_time_ids.float().numpy()
             for step in (0, 12, 24):
                 x = (torch.randn(shape, generator=g) * float(model.sigmas[step] + 1)).to(dt)
                 y = model(x, step)

@@ -1,4 +1,4 @@
-"""The DPM-Solver++(2M) update in fp64 numpy: what ``sp_dpmpp2m_step_rows_f16`` (csrc/solver.hip) is held to.
+"""The DPM-Solver++(2M) update in fp64 numpy: what ``sp_dpmpp2m_step_rows_f16`` (csrc/sampler_tail.hip) is held to.
 
 State layout as the kernel's: ``(B, 8, F, H, W)``, channels 0-3 the sample ``x``, channels 4-7 the previous step's denoised
 estimate ``D_prev``; eps rows ``[B*F*H*W][ld_eps]`` with the four real channels in front; guidance ``None``, ``[F]`` (one row for

@@ -364,10 +364,10 @@ def test_euler_objects_are_untouched_and_the_error_texts():
     # the two-kernel path test_euler_tail_in_conv_out_epilogue_is_bit_identical holds the fused tail to
     sigma, sigma_next = euler._sigma_host[step], euler._sigma_host[step + 1]
     in_scale = 1.0 / (sigma * sigma + 1.0) ** 0.5
-    eps_u = euler._unet_pass(lat, euler._uncond_image_latents, euler._uncond_embeddings, in_scale, step)
-    eps_c = euler._unet_pass(lat, euler._image_latents, euler._image_embeddings, in_scale, step)
+    eps_u = euler._unet_pass(lat, euler._cond.uncond_image_latents, euler._cond.uncond_embeddings, in_scale, step)
+    eps_c = euler._unet_pass(lat, euler._cond.image_latents, euler._cond.image_embeddings, in_scale, step)
     want = torch.empty_like(lat)
-    ops.euler_step(lat, eps_c, eps_u, euler._guidance32, want, ld_eps=eps_c.shape[1], sigma=sigma, sigma_next=sigma_next, b=1,
+    ops.euler_step(lat, eps_c, eps_u, euler._cond.guidance32, want, ld_eps=eps_c.shape[1], sigma=sigma, sigma_next=sigma_next, b=1,
                    frames=frames, h=h, w=w)
     assert torch.equal(euler(lat, step), want) and torch.equal(explicit(lat, step), want)
     # error texts

@@ -250,7 +250,7 @@ def test_adapter_errors_and_api_surface():
     assert out.shape == lat.shape and out.dtype == torch.float16 and torch.isfinite(out).all()
     assert abs(model.init_noise_sigma - (700.0 ** 2 + 1) ** 0.5) < 1e-3
     assert len(model.sigmas) == 26 and float(model.sigmas[-1]) == 0.0
-    assert model._added_time_ids.tolist() == [[5.0, 127.0, torch.tensor(0.02).half().item()]]
+    assert model._cond.added_time_ids.tolist() == [[5.0, 127.0, torch.tensor(0.02).half().item()]]
     model.clear_conditioning()
     with pytest.raises(RuntimeError):
         model(lat, 0)
@@ -347,10 +347,10 @@ def test_euler_tail_in_conv_out_epilogue_is_bit_identical(guidance):
         in_scale = 1.0 / (sigma * sigma + 1.0) ** 0.5
         eps_u = None
         if guidance:
-            eps_u = model._unet_pass(lat, model._uncond_image_latents, model._uncond_embeddings, in_scale, step)
-        eps_c = model._unet_pass(lat, model._image_latents, model._image_embeddings, in_scale, step)
+            eps_u = model._unet_pass(lat, model._cond.uncond_image_latents, model._cond.uncond_embeddings, in_scale, step)
+        eps_c = model._unet_pass(lat, model._cond.image_latents, model._cond.image_embeddings, in_scale, step)
         want = torch.empty_like(lat)
-        ops.euler_step(lat, eps_c, eps_u, model._guidance32 if guidance else None, want, ld_eps=eps_c.shape[1],
+        ops.euler_step(lat, eps_c, eps_u, model._cond.guidance32 if guidance else None, want, ld_eps=eps_c.shape[1],
                        sigma=sigma, sigma_next=sigma_next, b=1, frames=frames, h=h, w=w)
         assert torch.equal(fused, want), f"step {step}"
 

@@ -11,6 +11,7 @@ sum of the magnitudes of the update's terms with each window's weighted eps coun
 with two more roundings for every window that can cover a frame: the rounding of its weight to fp32 and its fmaf, each relative
 to a partial sum that the terms bound.  The sigmas are values of the fp32 table, so the kernels hold them exactly."""
 
+import json
 import os
 import subprocess
 import sys
@@ -21,6 +22,7 @@ import torch
 
 from tests import solver_model as sm
 from tests import window_model as wm
+from tests.golden import make_sampler_tail_golden as golden
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -33,37 +35,7 @@ def rel_l2(a, b):
     return float((a - b).norm() / b.norm().clamp_min(1e-30))
 
 
-def _dev(t):
-    return None if t is None else torch.from_numpy(np.ascontiguousarray(t)).to(DEV)
-
-
-# ------------------------------------------------------------------------------------------------ the kernels
-def _run(state, eps_c, eps_u, guidance, ld_g, shape, step, *, in_place=False, rows_kernel=False):
-    """One tail on numpy inputs; Euler for a 4-channel ``state``, 2M for 8 channels.  ``rows_kernel``: the single-window
-    kernel (the shape must be one window)."""
-    from vdpp_amd.hip import ops
-    from vdpp_amd.models import window_plan
-    nb, ft, window, stride, h, w = shape
-    euler, solver = wm.split_step(step)
-    st = _dev(state)
-    out = st if in_place else torch.full_like(st, float("nan"))
-    ec, eu, g = _dev(eps_c), _dev(eps_u), _dev(guidance)
-    if rows_kernel:
-        assert ft == window
-        if state.shape[1] == 4:
-            ops.euler_step(st, ec, eu, g, out, ld_eps=ec.shape[1], b=nb, frames=ft, h=h, w=w, ld_guidance=ld_g, **euler)
-        else:
-            ops.dpmpp2m_step(st, ec, eu, g, out, ld_eps=ec.shape[1], batch=nb, frames=ft, h=h, w=w, ld_guidance=ld_g, **solver)
-    else:
-        pl = window_plan.plan(ft, window, stride)
-        kw = dict(ld_eps=ec.shape[1], frames_total=ft, h=h, w=w, window=window, stride=stride, n_win=pl.n_win,
-                  weights=_dev(pl.weights), ld_guidance=ld_g)
-        if state.shape[1] == 4:
-            ops.euler_step_windows(st, ec, eu, g, out, b=nb, **euler, **kw)
-        else:
-            ops.dpmpp2m_step_windows(st, ec, eu, g, out, batch=nb, **solver, **kw)
-    torch.cuda.synchronize()
-    return out.cpu().numpy()
+_dev, _run = golden._dev, golden.run_tail      # one tail on numpy inputs (shared with the fixture's generator)
 
 
 def _within(got, want, terms, shape, what):
@@ -114,6 +86,78 @@ def test_one_window_gives_the_bytes_of_the_single_window_kernels(guidance, hw):
                 got = _run(state, ec, eu, g, ld_g, shape, step, in_place=in_place)
                 diff = int((got.view(np.uint16) != want.view(np.uint16)).sum())
                 assert diff == 0, f"{name}, {channels} channels, in_place={in_place}: {diff} of {got.size} values differ"
+
+
+@pytest.mark.parametrize("sampler", ["euler", "2m"])
+@pytest.mark.parametrize("entry", ["rows", "windows"])
+def test_tails_return_the_recorded_bytes(entry, sampler):
+    """``tests/golden/sampler_tails.json``: SHA-256 of what every tail returned at the commit the file names, the last one with
+    three separate kernels behind the five entry points (``tests/golden/make_sampler_tail_golden.py``).  The one kernel that
+    replaced them returns those bytes, out of place and in place."""
+    with open(golden.PATH) as fh:
+        rec = json.load(fh)["cases"]
+    picked = {cid: case for cid, case in golden.cases().items() if cid.startswith(f"{entry}-{sampler}-")}
+    assert len(picked) == {"rows": 12, "windows": 48}[entry] and set(golden.cases()) == set(rec)
+    for cid, case in picked.items():
+        for in_place in (False, True):
+            inputs, output = golden.run(case, in_place=in_place)
+            assert inputs == rec[cid]["inputs"], f"{cid}: the fixture is stale (numpy generates other inputs than it was recorded on)"
+            assert output == rec[cid]["output"], f"{cid}, in_place={in_place}: other bytes than the recorded kernels returned"
+
+
+@pytest.mark.parametrize("misalign", [False, True], ids=["aligned-four-pixels-per-thread", "latent-2-bytes-off-one-pixel-per-thread"])
+def test_euler_rows_entry_at_four_pixels_per_thread_against_the_fp64_model(misalign):
+    """``sp_euler_step_rows_f16`` at H*W = 288 takes the four-pixel form (it had none before the tails shared one kernel) and
+    falls back to one pixel per thread when the latent is not 8-byte aligned; both within the kernel bound of one window
+    (coverage 1) of the fp64 statement."""
+    from vdpp_amd.hip import ops
+    shape = (2, 5, 5, 5, 12, 24)
+    nb, ft, window, stride, h, w = shape
+    for guidance in ("none", "shared", "per-video"):
+        for name, step in wm.kernel_steps().items():
+            euler, _ = wm.split_step(step)
+            lat, ec, eu, g, ld_g = wm.case_inputs(shape, 8, guidance, channels=4, sigma=step["sigma"])
+            want, terms = wm.euler_step_windows(lat, ec, eu, g, window=window, stride=stride, **euler)
+            st = _dev(lat)
+            if misalign:
+                buf = torch.empty(st.numel() + 4, dtype=torch.float16, device=DEV)
+                buf[1:1 + st.numel()] = st.flatten()
+                st = buf[1:1 + st.numel()].view(st.shape)
+            assert st.data_ptr() % 8 == (2 if misalign else 0)
+            out = torch.full(lat.shape, float("nan"), dtype=torch.float16, device=DEV)
+            ops.euler_step(st, _dev(ec), _dev(eu), _dev(g), out, ld_eps=8, b=nb, frames=ft, h=h, w=w, ld_guidance=ld_g, **euler)
+            torch.cuda.synchronize()
+            _within(out.cpu().numpy(), want, terms, shape, f"Euler rows {guidance} {name}")
+
+
+def test_euler_rows_entry_refuses_bad_arguments_without_launching():
+    from vdpp_amd import hip
+    lib = hip.load()
+    fn = lib.sp_euler_step_rows_f16
+    nb, f, h, w = 1, 2, 4, 4
+    n = nb * 4 * f * h * w
+    stream = torch.cuda.current_stream().cuda_stream
+    eps = torch.zeros(nb * f * h * w, 4, dtype=torch.float16, device=DEV)
+    gs = torch.ones(f, dtype=torch.float32, device=DEV)
+    buf = torch.full((2 * n,), 7.0, dtype=torch.float16, device=DEV)           # the poison a refused call must leave
+    st, out = buf[:n], buf[n:]
+
+    def call(latent=st.data_ptr(), ec=eps.data_ptr(), eu=None, ld_eps=4, g=None, ld_g=0, o=out.data_ptr(), sigma=1.0,
+             dims=(nb, f, h, w)):
+        return fn(latent, ec, eu, ld_eps, g, ld_g, o, sigma, 0.5, *dims, stream)
+
+    for word, kw in (("null", dict(latent=None)), ("null", dict(ec=None)), ("null", dict(o=None)), ("ld_eps", dict(ld_eps=6)),
+                     ("ld_eps", dict(ld_eps=0)), ("sigma", dict(sigma=0.0)), ("sigma", dict(sigma=-1.0)),
+                     ("guidance", dict(eu=eps.data_ptr())), ("ld_guidance", dict(eu=eps.data_ptr(), g=gs.data_ptr(), ld_g=f - 1)),
+                     ("dims", dict(dims=(nb, 0, h, w))), ("dims", dict(dims=(nb, f, 0, w))), ("dims", dict(dims=(0, f, h, w))),
+                     ("overlap", dict(o=st.data_ptr() + 2)), ("overlap", dict(o=st.data_ptr() + 2 * (n - 1))),
+                     ("overlap", dict(latent=out.data_ptr(), o=out.data_ptr() - 16))):
+        assert call(**kw) == -1 and word in hip.last_error() and fn.__name__ in hip.last_error(), (kw, hip.last_error())
+    torch.cuda.synchronize()
+    assert bool((buf == 7.0).all()), "a refused call wrote"
+    assert call() == 0 and call(o=st.data_ptr()) == 0                 # apart, and in place (out == latent)
+    torch.cuda.synchronize()
+    assert not bool((buf == 7.0).any())
 
 
 def test_kernels_refuse_bad_arguments_without_launching():

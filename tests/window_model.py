@@ -1,5 +1,5 @@
 """Long videos as overlapping frame windows in fp64 numpy: what ``sp_euler_step_windows_f16`` and
-``sp_dpmpp2m_step_windows_f16`` (csrc/window.hip) and ``models/window_plan.py`` are held to.
+``sp_dpmpp2m_step_windows_f16`` (csrc/sampler_tail.hip) and ``models/window_plan.py`` are held to.
 
 Plan: ``n_win = (F_total - W)/S + 1`` windows, window ``k`` covers global frames ``k*S .. k*S + W - 1``; profile
 ``alpha(p) = min(p + 1, W - p)`` ("triangle") or 1 ("uniform"); ``wn[k][p] = alpha(p) / sum over the windows k' covering

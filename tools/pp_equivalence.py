@@ -47,8 +47,8 @@ def main():
         def logged(latent, step):
             if seen["n"] < args.steps:
                 print(f"[rank {rank}] step {step:2d} in  {float(latent.float().abs().sum()):.6e}  "
-                      f"cond {float(model._image_latents.float().abs().sum()):.6e} "
-                      f"emb {float(model._image_embeddings.float().abs().sum()):.6e}", flush=True)
+                      f"cond {float(model._cond.image_latents.float().abs().sum()):.6e} "
+                      f"emb {float(model._cond.image_embeddings.float().abs().sum()):.6e}", flush=True)
             seen["n"] += 1
             return inner(latent, step)
         model.forward = logged

@@ -28,7 +28,7 @@ solver = StableVideoUNet(unet=euler.unet, timesteps=ts, sampler="dpmpp_2m")
 B, F, H, W = 2, args.frames, 72, 128
 torch.manual_seed(42)
 euler.set_dummy_conditioning(B, F, H, W, dev)
-solver.set_conditioning(euler._image_embeddings, euler._image_latents, num_frames=F)
+solver.set_conditioning(euler._cond.image_embeddings, euler._cond.image_latents, num_frames=F)
 noise = torch.randn(B, 4, F, H, W, device=dev, dtype=torch.float16) * euler.init_noise_sigma
 arms = {"euler": (euler, noise), "dpmpp_2m": (solver, solver.init_state(noise))}
 first = 1                                    # steps 1.. : the second-order form of the 2M kernel (step 0 is first order)

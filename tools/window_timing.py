@@ -47,7 +47,7 @@ if __name__ == "__main__":
     windowed = StableVideoUNet(unet=plain.unet, timesteps=ts, sampler="dpmpp_2m", window_stride=STRIDE)
     torch.manual_seed(42)
     plain.set_dummy_conditioning(B, WIN, H, W, dev)
-    windowed.set_conditioning(plain._image_embeddings, plain._image_latents, num_frames=WIN)
+    windowed.set_conditioning(plain._cond.image_embeddings, plain._cond.image_latents, num_frames=WIN)
     long_state = windowed.init_state(torch.randn(B, 4, FT, H, W, device=dev, dtype=torch.float16) * plain.init_noise_sigma)
     short_state = plain.init_state(torch.randn(B, 4, WIN, H, W, device=dev, dtype=torch.float16) * plain.init_noise_sigma)
     pl = window_plan.plan(FT, WIN, STRIDE)

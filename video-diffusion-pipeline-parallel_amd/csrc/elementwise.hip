@@ -27,38 +27,6 @@ __global__ void pack_input_kernel(const f16 *__restrict__ lat, const f16 *__rest
   for (int c = 8; c < cpad; c += 8) *(f16x8 *)(o + c) = z;
 }
 
-__global__ void euler_kernel(const f16 *__restrict__ lat, const f16 *__restrict__ ec,
-                             const f16 *__restrict__ eu, int64_t ld_eps, const float *__restrict__ gs,
-                             int64_t ld_g, f16 *__restrict__ out, float c_out, float c_skip, float inv_sigma, float dt,
-                             int frames, int64_t hw, int64_t total) {
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // one (b,f,pixel)
-  if (idx >= total) return;
-  const int64_t p = idx % hw;
-  const int64_t bf = idx / hw;
-  const int f = (int)(bf % frames);
-  const int64_t b = bf / frames;
-  const f16x4 c4 = *(const f16x4 *)(ec + idx * ld_eps);
-  f16x4 u4 = c4;
-  float g = 1.f;
-  if (eu) { u4 = *(const f16x4 *)(eu + idx * ld_eps); g = gs[b * ld_g + f]; }
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    const int64_t a = ((b * 4 + c) * frames + f) * hw + p;
-    const float x = (float)lat[a];
-    float e = (float)c4[c];
-    if (eu) {
-      // reference evaluates the guidance mix in fp16 (svd_unet.py:410-411)
-      const f16 gh = (f16)g;
-      const f16 diff = (f16)((float)c4[c] - (float)u4[c]);
-      const f16 prod = (f16)((float)gh * (float)diff);
-      e = (float)(f16)((float)u4[c] + (float)prod);
-    }
-    const float x0 = e * c_out + x * c_skip;
-    const float d = (x - x0) * inv_sigma;
-    out[a] = (f16)(x + d * dt);
-  }
-}
-
 __global__ void concat_kernel(const f16 *__restrict__ a, int oa, const f16 *__restrict__ b, int ob,
                               f16 *__restrict__ out, int64_t total) {
   // one thread per output octet
@@ -166,34 +134,6 @@ extern "C" int sp_pack_input_f16(const void *latent, const void *image_latents, 
                      in_scale, frames, hw, cpad, total);
   SP_CHECK_LAUNCH("sp_pack_input_f16");
   return SP_OK;
-}
-
-extern "C" int sp_euler_step_rows_f16(const void *latent, const void *eps_cond, const void *eps_uncond,
-                                      int64_t ld_eps, const float *guidance, int64_t ld_guidance, void *out, float sigma,
-                                      float sigma_next, int b, int frames, int h, int w, void *stream) {
-  SP_REQUIRE(latent && eps_cond && out, "sp_euler_step_f16: null pointer");
-  SP_REQUIRE(!eps_uncond || guidance, "sp_euler_step_f16: CFG needs a guidance vector");
-  SP_REQUIRE(ld_eps >= 4 && ld_eps % 4 == 0, "sp_euler_step_f16: ld_eps must be a multiple of 4");
-  SP_REQUIRE(sigma > 0.f, "sp_euler_step_f16: sigma must be positive");
-  SP_REQUIRE(ld_guidance == 0 || ld_guidance >= frames,
-             "sp_euler_step_rows_f16: ld_guidance=%lld must be 0 (one shared row) or >= frames (%d)",
-             (long long)ld_guidance, frames);
-  const int64_t hw = (int64_t)h * w, total = (int64_t)b * frames * hw;
-  const float s2 = sigma * sigma + 1.0f;
-  SP_CLEAR_STALE_ERROR();
-  hipLaunchKernelGGL(euler_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                     (hipStream_t)stream, (const f16 *)latent, (const f16 *)eps_cond,
-                     (const f16 *)eps_uncond, ld_eps, guidance, ld_guidance, (f16 *)out, -sigma / sqrtf(s2), 1.0f / s2,
-                     1.0f / sigma, sigma_next - sigma, frames, hw, total);
-  SP_CHECK_LAUNCH("sp_euler_step_f16");
-  return SP_OK;
-}
-
-extern "C" int sp_euler_step_f16(const void *latent, const void *eps_cond, const void *eps_uncond,
-                                 int64_t ld_eps, const float *guidance, void *out, float sigma,
-                                 float sigma_next, int b, int frames, int h, int w, void *stream) {
-  return sp_euler_step_rows_f16(latent, eps_cond, eps_uncond, ld_eps, guidance, 0, out, sigma, sigma_next, b, frames,
-                                h, w, stream);
 }
 
 extern "C" int sp_concat_channels_f16(const void *a, int ca, const void *b, int cb, void *out, int64_t rows,

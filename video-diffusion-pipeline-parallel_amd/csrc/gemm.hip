@@ -343,7 +343,8 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void gemm_f16_kernel(const GemmArgs
     f16x8 v = *(const f16x8 *)(sc + r * ldc + c * 8);
     if (p.eul_out) {
       // guidance mix + Euler update of the four latent channels of row m = (b, f, pixel) (same arithmetic, same
-      // roundings as sp_euler_step_f16 on the eps rows this epilogue would otherwise have written)
+      // roundings as sp_euler_step_f16 on the eps rows this epilogue would otherwise have written: sampler_math.h is the
+      // statement that this copy of guidance_mix_f16 and euler_update must match)
       if (col != 0) continue;
       const int64_t pix = m % p.eul_hw, bf = m / p.eul_hw;
       const int f = (int)(bf % p.eul_frames);

@@ -1,0 +1,227 @@
+// The sampler tails behind the UNet's stored eps rows, one kernel: the Euler update of the latent (B,4,F,H,W) or the
+// DPM-Solver++(2M) update of the state (B,8,F,H,W: channels 0-3 the sample x, channels 4-7 the previous step's denoised
+// estimate, the solver's history riding in the latent itself), each behind one set of eps rows [B][F][H*W][ld_eps] or behind
+// overlapping frame windows (temporal co-denoising): a latent of F_total frames cut into n_win windows of `window` frames,
+// `stride` apart, the UNet run once per window, the eps rows of all windows in one buffer [n_win][B][window][H*W][ld_eps],
+// blended frame by frame with the host's normalised weight table in front of ONE update of the whole latent.  The arithmetic
+// is that of sampler_math.h.  See sp_euler_step_rows_f16 ... sp_dpmpp2m_step_windows_f16 in svdpipe.h.
+#include "sampler_math.h"
+
+namespace {
+
+struct WindowPlan {
+  int frames, window, stride, n_win, batch;   // frames = F_total
+};
+
+enum { EULER = 0, FIRST_ORDER = 1, SECOND_ORDER = 2 };   // FIRST_ORDER: 2M with c2 == 0, the D_prev planes are never read
+
+// A thread owns PX adjacent pixels of one (b, f): the planes are read and written PX at a time (8 bytes for PX = 4), the eps
+// rows one 8-byte row per pixel and covering window.  Every value a thread reads from `st` is in a register before its first
+// store and no other thread touches those elements, so out == st (update in place) is safe; hence no __restrict__ on the two.
+// WINDOWS = false is one window that is the whole latent: no weight table, one eps row per pixel at bf * hw + p, guidance
+// indexed by the frame; the loop below is then one pass and e the eps itself.
+template <int PX, int MODE, bool WINDOWS>
+__global__ __launch_bounds__(256) void sampler_tail_kernel(const f16 *st, const f16 *__restrict__ ec,
+                                                           const f16 *__restrict__ eu, int64_t ld_eps,
+                                                           const float *__restrict__ gs, int64_t ld_g,
+                                                           const float *__restrict__ wn, f16 *out, SamplerCoef k,
+                                                           WindowPlan wp, int64_t hw, int64_t total) {
+  typedef f16 vec __attribute__((ext_vector_type(PX)));
+  constexpr int CH = MODE == EULER ? 4 : 8;
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // one group of PX pixels of a (b, f)
+  if (idx >= total) return;
+  const int frames = wp.frames;
+  const int64_t groups = hw / PX;
+  const int64_t p = (idx % groups) * PX;
+  const int64_t bf = idx / groups;
+  const int f = (int)(bf % frames);
+  const int64_t b = bf / frames;
+  const int64_t plane0 = (b * CH * frames + f) * hw + p;                 // channel c: + c * frames * hw
+  const int64_t cs = (int64_t)frames * hw;
+
+  float x[4][PX], dp[4][PX], e[4][PX];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    if constexpr (PX == 1) {
+      x[c][0] = (float)st[plane0 + c * cs];
+      dp[c][0] = MODE == SECOND_ORDER ? (float)st[plane0 + (4 + c) * cs] : 0.f;
+    } else {
+      const vec xv = *(const vec *)(st + plane0 + c * cs);
+      vec dv = {};
+      if (MODE == SECOND_ORDER) dv = *(const vec *)(st + plane0 + (4 + c) * cs);
+#pragma unroll
+      for (int j = 0; j < PX; ++j) { x[c][j] = (float)xv[j]; dp[c][j] = (float)dv[j]; }
+    }
+#pragma unroll
+    for (int j = 0; j < PX; ++j) e[c][j] = 0.f;
+  }
+  // the windows that cover global frame f, in ascending order: k*stride <= f <= k*stride + window - 1
+  int k_lo = 0, k_hi = 0;
+  if constexpr (WINDOWS) {
+    k_lo = f < wp.window ? 0 : (f - wp.window) / wp.stride + 1;
+    k_hi = min(f / wp.stride, wp.n_win - 1);
+  }
+  for (int kw = k_lo; kw <= k_hi; ++kw) {
+    int pos = f;                                                         // position in the window: 0 .. window - 1
+    float wgt = 1.f;
+    int64_t row = bf * hw + p;                                           // eps row of the first pixel
+    if constexpr (WINDOWS) {
+      pos = f - kw * wp.stride;
+      wgt = wn[kw * wp.window + pos];
+      row = (((int64_t)kw * wp.batch + b) * wp.window + pos) * hw + p;
+    }
+    float g = 1.f;
+    if (eu) g = gs[b * ld_g + pos];                                      // guidance follows the position in the window
+#pragma unroll
+    for (int j = 0; j < PX; ++j) {
+      const f16x4 c4 = *(const f16x4 *)(ec + (row + j) * ld_eps);
+      f16x4 u4 = c4;
+      if (eu) u4 = *(const f16x4 *)(eu + (row + j) * ld_eps);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const float v = eu ? guidance_mix_f16(g, c4[c], u4[c]) : (float)c4[c];
+        e[c][j] = WINDOWS ? fmaf(wgt, v, e[c][j]) : v;                   // fp32, never rounded to fp16
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    vec xo, dn;
+#pragma unroll
+    for (int j = 0; j < PX; ++j) {
+      if constexpr (MODE == EULER) {
+        xo[j] = euler_update(x[c][j], e[c][j], k);
+      } else {
+        float d;
+        xo[j] = (f16)dpmpp2m_update(x[c][j], e[c][j], dp[c][j], MODE == SECOND_ORDER, k, &d);
+        dn[j] = (f16)d;
+      }
+    }
+    *(vec *)(out + plane0 + c * cs) = xo;
+    if constexpr (MODE != EULER) *(vec *)(out + plane0 + (4 + c) * cs) = dn;
+  }
+}
+
+// One checked call: the pointers as the entry got them, the constants of its step, its plan (for one set of eps rows: a
+// single window that is the whole latent, weights null) and whether the four-pixel form applies.
+struct Tail {
+  const char *name;
+  const f16 *st, *ec, *eu;
+  const float *gs, *wn;
+  int64_t ld_eps, ld_g, hw;
+  f16 *out;
+  SamplerCoef k;
+  WindowPlan wp;
+  bool wide;
+};
+
+template <int MODE>
+void launch(const Tail &t, void *stream) {
+  const auto kernel = t.wn ? (t.wide ? sampler_tail_kernel<4, MODE, true> : sampler_tail_kernel<1, MODE, true>)
+                           : (t.wide ? sampler_tail_kernel<4, MODE, false> : sampler_tail_kernel<1, MODE, false>);
+  const int64_t total = (int64_t)t.wp.batch * t.wp.frames * t.hw / (t.wide ? 4 : 1);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, t.st, t.ec, t.eu, t.ld_eps,
+                     t.gs, t.ld_g, t.wn, t.out, t.k, t.wp, t.hw, total);
+}
+
+// Everything all entry points refuse; on success fills the call (but for the step's own constants in t->k).  `windows`: the
+// entry takes a plan and a weight table; the others give the plan of one window that is the whole latent, and no weights.
+int check(const char *name, const void *state, const void *eps_cond, const void *eps_uncond, int64_t ld_eps,
+          const float *guidance, int64_t ld_guidance, void *out, float sigma, int channels, int batch, int frames_total, int h,
+          int w, bool windows, int window, int stride, int n_win, const float *weights, Tail *t) {
+  SP_REQUIRE(state && eps_cond && out, "%s: null pointer", name);
+  SP_REQUIRE(!windows || weights, "%s: null weights (the normalised [n_win][window] table of the window plan)", name);
+  SP_REQUIRE(!eps_uncond || guidance, "%s: CFG needs a guidance vector", name);
+  SP_REQUIRE(ld_eps >= 4 && ld_eps % 4 == 0, "%s: ld_eps must be a multiple of 4", name);
+  SP_REQUIRE(batch > 0 && frames_total > 0 && window > 0 && h > 0 && w > 0, "%s: dims must be positive", name);
+  SP_REQUIRE(window <= frames_total, "%s: window=%d exceeds frames_total=%d", name, window, frames_total);
+  SP_REQUIRE(stride >= 1 && stride <= window, "%s: stride=%d must be from 1 to window (%d)", name, stride, window);
+  SP_REQUIRE((frames_total - window) % stride == 0,
+             "%s: frames_total=%d is not window (%d) plus a whole number of strides (%d)", name, frames_total, window, stride);
+  SP_REQUIRE(n_win == (frames_total - window) / stride + 1, "%s: n_win=%d, the plan of (%d, %d, %d) has %d windows", name,
+             n_win, frames_total, window, stride, (frames_total - window) / stride + 1);
+  SP_REQUIRE(ld_guidance == 0 || ld_guidance >= window,
+             "%s: ld_guidance=%lld must be 0 (one shared row) or >= the frames of a window (%d)", name, (long long)ld_guidance, window);
+  SP_REQUIRE(sigma > 0.f, "%s: sigma must be positive", name);
+  const int64_t hw = (int64_t)h * w;
+  const int64_t bytes = (int64_t)batch * frames_total * hw * channels * (int64_t)sizeof(f16);
+  const uintptr_t s0 = (uintptr_t)state, o0 = (uintptr_t)out;
+  SP_REQUIRE(s0 == o0 || s0 + (uintptr_t)bytes <= o0 || o0 + (uintptr_t)bytes <= s0,
+             "%s: out must be the input itself or not overlap it", name);
+  const float s2 = sigma * sigma + 1.0f;
+  *t = Tail{name, (const f16 *)state, (const f16 *)eps_cond, (const f16 *)eps_uncond, guidance, weights, ld_eps, ld_guidance, hw,
+            (f16 *)out, SamplerCoef{-sigma / sqrtf(s2), 1.0f / s2}, WindowPlan{frames_total, window, stride, n_win, batch},
+            // four pixels per thread where every plane access stays 8-byte aligned
+            hw % 4 == 0 && s0 % 8 == 0 && o0 % 8 == 0};
+  return SP_OK;
+}
+
+int euler_step(Tail &t, float sigma, float sigma_next, void *stream) {
+  t.k.inv_sigma = 1.0f / sigma; t.k.dt = sigma_next - sigma;
+  SP_CLEAR_STALE_ERROR();
+  launch<EULER>(t, stream);
+  SP_CHECK_LAUNCH(t.name);
+  return SP_OK;
+}
+
+int dpmpp2m_step(Tail &t, float a, float b, float c1, float c2, void *stream) {
+  SP_REQUIRE(a >= 0.f && a < 1.f, "%s: a = sigma'/sigma = %g must be in [0, 1)", t.name, (double)a);
+  SP_REQUIRE(c2 >= 0.f, "%s: c2 = %g must not be negative", t.name, (double)c2);
+  t.k.a = a; t.k.b = b; t.k.c1 = c1; t.k.c2 = c2;
+  SP_CLEAR_STALE_ERROR();
+  if (c2 != 0.f) launch<SECOND_ORDER>(t, stream);
+  else launch<FIRST_ORDER>(t, stream);
+  SP_CHECK_LAUNCH(t.name);
+  return SP_OK;
+}
+
+}  // namespace
+
+extern "C" int sp_euler_step_rows_f16(const void *latent, const void *eps_cond, const void *eps_uncond, int64_t ld_eps,
+                                      const float *guidance, int64_t ld_guidance, void *out, float sigma, float sigma_next,
+                                      int b, int frames, int h, int w, void *stream) {
+  Tail t;
+  if (int rc = check("sp_euler_step_rows_f16", latent, eps_cond, eps_uncond, ld_eps, guidance, ld_guidance, out, sigma, 4, b, frames, h, w, false,
+                     frames, frames, 1, nullptr, &t))
+    return rc;
+  return euler_step(t, sigma, sigma_next, stream);
+}
+
+extern "C" int sp_euler_step_f16(const void *latent, const void *eps_cond, const void *eps_uncond, int64_t ld_eps,
+                                 const float *guidance, void *out, float sigma, float sigma_next, int b, int frames, int h,
+                                 int w, void *stream) {
+  return sp_euler_step_rows_f16(latent, eps_cond, eps_uncond, ld_eps, guidance, 0, out, sigma, sigma_next, b, frames, h, w,
+                                stream);
+}
+
+extern "C" int sp_dpmpp2m_step_rows_f16(const void *state, const void *eps_cond, const void *eps_uncond, int64_t ld_eps,
+                                        const float *guidance, int64_t ld_guidance, void *out_state, float sigma, float a,
+                                        float b, float c1, float c2, int batch, int frames, int h, int w, void *stream) {
+  Tail t;
+  if (int rc = check("sp_dpmpp2m_step_rows_f16", state, eps_cond, eps_uncond, ld_eps, guidance, ld_guidance, out_state, sigma, 8, batch, frames, h, w,
+                     false, frames, frames, 1, nullptr, &t))
+    return rc;
+  return dpmpp2m_step(t, a, b, c1, c2, stream);
+}
+
+extern "C" int sp_euler_step_windows_f16(const void *latent, const void *eps_cond, const void *eps_uncond, int64_t ld_eps,
+                                         const float *guidance, int64_t ld_guidance, void *out, float sigma,
+                                         float sigma_next, int b, int frames_total, int h, int w, int window, int stride,
+                                         int n_win, const float *weights, void *stream) {
+  Tail t;
+  if (int rc = check("sp_euler_step_windows_f16", latent, eps_cond, eps_uncond, ld_eps, guidance, ld_guidance, out, sigma, 4, b, frames_total, h, w,
+                     true, window, stride, n_win, weights, &t))
+    return rc;
+  return euler_step(t, sigma, sigma_next, stream);
+}
+
+extern "C" int sp_dpmpp2m_step_windows_f16(const void *state, const void *eps_cond, const void *eps_uncond, int64_t ld_eps,
+                                           const float *guidance, int64_t ld_guidance, void *out_state, float sigma, float a,
+                                           float b, float c1, float c2, int batch, int frames_total, int h, int w, int window,
+                                           int stride, int n_win, const float *weights, void *stream) {
+  Tail t;
+  if (int rc = check("sp_dpmpp2m_step_windows_f16", state, eps_cond, eps_uncond, ld_eps, guidance, ld_guidance, out_state, sigma, 8, batch, frames_total,
+                     h, w, true, window, stride, n_win, weights, &t))
+    return rc;
+  return dpmpp2m_step(t, a, b, c1, c2, stream);
+}

@@ -909,7 +909,7 @@ def euler_step(latent, eps_cond, eps_uncond, guidance, out, *, ld_eps, sigma, si
     shared by every video (``sp_euler_step_rows_f16``)."""
     _check(load().sp_euler_step_rows_f16(latent.data_ptr(), eps_cond.data_ptr(), _ptr(eps_uncond), ld_eps, _ptr(guidance),
                                          int(ld_guidance), out.data_ptr(), sigma, sigma_next, b, frames, h, w, _stream()),
-           "sp_euler_step_f16")
+           "sp_euler_step_rows_f16")
     return out
 
 

@@ -25,6 +25,7 @@ from dataclasses import dataclass
 import torch
 import torch.nn as nn
 
+from ..hip import ops
 from . import euler_schedule, solver_schedule, window_plan
 from .unet_hip import SVDUNetHIP
 from .unet_spec import UNetConfig, random_state_dict
@@ -139,16 +140,7 @@ class StableVideoUNet(nn.Module):
         self.dtype = dtype
         self.num_train_timesteps = num_train_timesteps
         self._init_scheduler()
-        self._image_embeddings = None
-        self._added_time_ids = None
-        self._image_latents = None
-        self._conditioning_set = False
-        self._guidance_scale = None
-        self._uncond_embeddings = None
-        self._uncond_image_latents = None
-        self._guidance_scale_tensor = None
-        self._guidance32 = None
-        self._cond: VideoConditioning | None = None
+        self._cond: VideoConditioning | None = None      # the model's own conditioning (set_conditioning)
         self._graph_conds: dict = {}     # (calling stream, layout of a VideoConditioning) -> that lane's static copy
 
     # ------------------------------------------------------------------ schedule
@@ -278,12 +270,17 @@ class StableVideoUNet(nn.Module):
         each replay (one graph per lane, step, latent shape and conditioning layout)."""
         self._use_graphs = enabled
         if not enabled:
-            self._graphs.clear()
-            self._graph_lanes.clear()
-            self._graph_conds.clear()
-            release = getattr(self.unet, "release_stream_state", None)
-            if release is not None:
-                release()
+            self._drop_replay_state()
+
+    def _drop_replay_state(self) -> None:
+        """Forget the captured graphs, their lanes (capture streams / pools are keyed by the calling stream's raw handle), the
+        lanes' conditioning copies and the engine's per-stream scratch."""
+        self._graphs.clear()
+        self._graph_lanes.clear()
+        self._graph_conds.clear()
+        release = getattr(self.unet, "release_stream_state", None)
+        if release is not None:
+            release()
 
     def enable_memory_optimizations(self) -> None:
         """Kept for API compatibility (ref ``svd_unet.py:166-194``); nothing to toggle here."""
@@ -361,21 +358,10 @@ class StableVideoUNet(nn.Module):
         guidance_scale: float | None = None,
         num_frames: int = 14,
     ) -> None:
-        c = self._cond = self.prepare_conditioning(image_embeddings, image_latents, fps=fps, motion_bucket_id=motion_bucket_id,
-                                                   noise_aug_strength=noise_aug_strength, guidance_scale=guidance_scale,
-                                                   num_frames=num_frames)
-        self._added_time_ids = c.added_time_ids
-        self._added_ids32 = c.added_ids32
-        self._image_embeddings = c.image_embeddings
-        self._image_latents = c.image_latents
-        self._conditioning_set = True
-        self._num_frames = c.num_frames
+        self._cond = self.prepare_conditioning(image_embeddings, image_latents, fps=fps, motion_bucket_id=motion_bucket_id,
+                                               noise_aug_strength=noise_aug_strength, guidance_scale=guidance_scale,
+                                               num_frames=num_frames)
         self._graphs.clear()          # captured graphs hold pointers to the previous conditioning tensors
-        self._guidance_scale = c.guidance_scale
-        self._uncond_embeddings = c.uncond_embeddings
-        self._uncond_image_latents = c.uncond_image_latents
-        self._guidance32 = c.guidance32
-        self._guidance_scale_tensor = c.guidance_scale_tensor
 
     def set_dummy_conditioning(
         self,
@@ -396,43 +382,62 @@ class StableVideoUNet(nn.Module):
                               num_frames=num_frames)
 
     def clear_conditioning(self) -> None:
-        self._image_embeddings = None
-        self._added_time_ids = None
-        self._image_latents = None
-        self._conditioning_set = False
-        self._guidance_scale = None
-        self._uncond_embeddings = None
-        self._uncond_image_latents = None
-        self._guidance_scale_tensor = None
-        self._guidance32 = None
         self._cond = None
-        self._graphs.clear()
-        self._graph_lanes.clear()            # capture streams / pools are keyed by the calling stream's raw handle
-        self._graph_conds.clear()
-        release = getattr(self.unet, "release_stream_state", None)
-        if release is not None:
-            release()
+        self._drop_replay_state()
 
     # ------------------------------------------------------------------ one diffusion step
     def _unet_pass(self, latent, image_latents, embeddings, in_scale, step, euler=None, added_ids32=None, eps_out=None):
-        from ..hip import ops
-
         b, _, f, h, w = latent.shape
         rows = torch.empty((b * f * h * w, self.unet.cin_pad), dtype=torch.float16, device=latent.device)
         ops.pack_input(latent, image_latents, rows, in_scale=in_scale, b=b, frames=f, h=h, w=w,
                        cpad=self.unet.cin_pad)
         return self.unet.forward_rows(rows, b=b, frames=f, h=h, w=w, t_value=self._t_dev[step:step + 1],
                                       ctx16=embeddings.reshape(b, -1),
-                                      added_ids32=self._added_ids32 if added_ids32 is None else added_ids32, euler=euler,
+                                      added_ids32=self._cond.added_ids32 if added_ids32 is None else added_ids32, euler=euler,
                                       **({} if eps_out is None else {"eps_out": eps_out}))
+
+    def _unet_passes(self, x, cond: VideoConditioning, step, in_scale, *, windows=1, eps_out=None, euler=None):
+        """The UNet passes of one step on the sample ``x``: the conditional one and, with guidance, the unconditional one,
+        as two sequential passes (the reference's order) or, with ``batched_cfg``, as the halves ``[uncond, cond]`` of one
+        call.  Returns ``(eps_cond, eps_uncond or None)``.
+
+        ``windows``: ``x`` holds that many frame windows of all videos stacked as ``[window][video]`` batch rows; the
+        conditioning rows are repeated per window.  ``eps_out``: ``(rows for eps_cond, rows for eps_uncond or None)`` to
+        store the passes' eps rows in (a batched call's halves are copied there).  ``euler``: the Euler tail (``latent``,
+        ``out``, ``sigma``, ``sigma_next``) for the epilogue of a sequential conditional pass' last convolution, which applies
+        the guidance mix and the update itself: its eps rows never exist in HBM and ``eps_cond`` is None.  A batched call
+        cannot take it: both eps come back and the tail is the caller's."""
+        def rep(t):
+            return t if windows == 1 else torch.cat([t] * windows, dim=0)
+
+        ids = cond.added_ids32 if cond.added_ids32.dim() == 1 else rep(cond.added_ids32)      # [3], or one row per video
+        out_c, out_u = (None, None) if eps_out is None else eps_out
+        if not cond.guided:
+            return self._unet_pass(x, rep(cond.image_latents), rep(cond.image_embeddings), in_scale, step, euler=euler,
+                                   added_ids32=ids, eps_out=out_c), None
+        if self.batched_cfg:
+            both = self._unet_pass(torch.cat([x, x], dim=0),
+                                   torch.cat([rep(cond.uncond_image_latents), rep(cond.image_latents)], dim=0),
+                                   torch.cat([rep(cond.uncond_embeddings), rep(cond.image_embeddings)], dim=0), in_scale, step,
+                                   added_ids32=ids if ids.dim() == 1 else torch.cat([ids, ids], dim=0))
+            half = both.shape[0] // 2
+            eps_u, eps_c = both[:half], both[half:]
+            if eps_out is not None:
+                eps_u, eps_c = out_u.copy_(eps_u), out_c.copy_(eps_c)
+            return eps_c, eps_u
+        eps_u = self._unet_pass(x, rep(cond.uncond_image_latents), rep(cond.uncond_embeddings), in_scale, step,
+                                added_ids32=ids, eps_out=out_u)
+        if euler is not None:
+            euler = dict(euler, eps_uncond=eps_u, guidance=cond.guidance32, ld_eps=eps_u.shape[1],
+                         ld_guidance=cond.guidance_ld)
+        return self._unet_pass(x, rep(cond.image_latents), rep(cond.image_embeddings), in_scale, step, euler=euler,
+                               added_ids32=ids, eps_out=out_c), eps_u
 
     @torch.inference_mode()
     def forward(self, latent: torch.Tensor, step: int, conditioning: VideoConditioning | None = None) -> torch.Tensor:
         """One Euler step of ``latent`` (B,4,F,H,W), or with ``sampler="dpmpp_2m"`` one DPM-Solver++(2M) step of the
         (B,8,F,H,W) state (``init_state``).  ``conditioning`` (``prepare_conditioning``): what this call is conditioned on;
         None = the model's own (``set_conditioning``)."""
-        from ..hip import ops
-
         cond = self._cond if conditioning is None else conditioning
         if cond is None:
             raise RuntimeError(
@@ -537,8 +542,6 @@ class StableVideoUNet(nn.Module):
         return static_out.clone()                          # the static buffer is overwritten by this lane's next replay
 
     def _forward_eager(self, latent: torch.Tensor, step: int, cond: VideoConditioning | None = None) -> torch.Tensor:
-        from ..hip import ops
-
         cond = self._cond if cond is None else cond
         if self.window_stride is not None:
             return self._forward_windows(latent, step, cond)
@@ -546,58 +549,24 @@ class StableVideoUNet(nn.Module):
             return self._forward_dpmpp_2m(latent, step, cond)
         b, _, f, h, w = latent.shape
         sigma, sigma_next = self._sigma_host[step], self._sigma_host[step + 1]
-        in_scale = 1.0 / math.sqrt(sigma * sigma + 1.0)
-
-        eps_u = None
-        ids = cond.added_ids32
-        if cond.guided and self.batched_cfg:
-            both = self._unet_pass(torch.cat([latent, latent], dim=0),
-                                   torch.cat([cond.uncond_image_latents, cond.image_latents], dim=0),
-                                   torch.cat([cond.uncond_embeddings, cond.image_embeddings], dim=0), in_scale, step,
-                                   added_ids32=ids if ids.dim() == 1 else torch.cat([ids, ids], dim=0))
-            half = both.shape[0] // 2
-            eps_u, eps_c = both[:half], both[half:]
-        else:
-            # sequential passes (the reference's order): the conditional pass' last convolution applies the guidance
-            # mix and the Euler update in its epilogue, so its eps rows never exist in HBM
-            out = torch.empty_like(latent)
-            tail = dict(latent=latent, out=out, sigma=sigma, sigma_next=sigma_next)
-            if cond.guided:
-                eps_u = self._unet_pass(latent, cond.uncond_image_latents, cond.uncond_embeddings, in_scale, step,
-                                        added_ids32=ids)
-                tail.update(eps_uncond=eps_u, guidance=cond.guidance32, ld_eps=eps_u.shape[1], ld_guidance=cond.guidance_ld)
-            self._unet_pass(latent, cond.image_latents, cond.image_embeddings, in_scale, step, euler=tail, added_ids32=ids)
-            return out
         out = torch.empty_like(latent)
-        ops.euler_step(latent, eps_c, eps_u, cond.guidance32 if eps_u is not None else None, out,
-                       ld_eps=eps_c.shape[1], sigma=sigma, sigma_next=sigma_next, b=b, frames=f, h=h, w=w,
-                       ld_guidance=cond.guidance_ld)
+        eps_c, eps_u = self._unet_passes(latent, cond, step, 1.0 / math.sqrt(sigma * sigma + 1.0),
+                                         euler=dict(latent=latent, out=out, sigma=sigma, sigma_next=sigma_next))
+        if eps_c is not None:                             # the conditional pass did not take the tail
+            ops.euler_step(latent, eps_c, eps_u, cond.guidance32 if eps_u is not None else None, out,
+                           ld_eps=eps_c.shape[1], sigma=sigma, sigma_next=sigma_next, b=b, frames=f, h=h, w=w,
+                           ld_guidance=cond.guidance_ld)
         return out
 
     def _forward_dpmpp_2m(self, state: torch.Tensor, step: int, cond: VideoConditioning) -> torch.Tensor:
         """One DPM-Solver++(2M) step of ``state`` (B,8,F,H,W).  The UNet passes are those of the Euler step without its
         tail: ``conv_out`` stores its four eps channels and ``sp_dpmpp2m_step_rows_f16`` follows with this step's
         coefficients (host constants, so a captured graph of the step holds them)."""
-        from ..hip import ops
-
         b, _, f, h, w = state.shape
         sigma = self._sigma_host[step]
-        in_scale = 1.0 / math.sqrt(sigma * sigma + 1.0)
         a, b_, c1, c2 = self._solver_coef[step]
         x = state[:, :4].contiguous()                     # (a view for one video; else a copy of the four sample planes)
-        ids = cond.added_ids32
-        eps_u = None
-        if cond.guided and self.batched_cfg:
-            both = self._unet_pass(torch.cat([x, x], dim=0),
-                                   torch.cat([cond.uncond_image_latents, cond.image_latents], dim=0),
-                                   torch.cat([cond.uncond_embeddings, cond.image_embeddings], dim=0), in_scale, step,
-                                   added_ids32=ids if ids.dim() == 1 else torch.cat([ids, ids], dim=0))
-            half = both.shape[0] // 2
-            eps_u, eps_c = both[:half], both[half:]
-        else:
-            if cond.guided:
-                eps_u = self._unet_pass(x, cond.uncond_image_latents, cond.uncond_embeddings, in_scale, step, added_ids32=ids)
-            eps_c = self._unet_pass(x, cond.image_latents, cond.image_embeddings, in_scale, step, added_ids32=ids)
+        eps_c, eps_u = self._unet_passes(x, cond, step, 1.0 / math.sqrt(sigma * sigma + 1.0))
         out = torch.empty_like(state)
         ops.dpmpp2m_step(state, eps_c, eps_u, cond.guidance32 if eps_u is not None else None, out, ld_eps=eps_c.shape[1],
                          sigma=sigma, a=a, b=b_, c1=c1, c2=c2, batch=b, frames=f, h=h, w=w, ld_guidance=cond.guidance_ld)
@@ -620,8 +589,6 @@ class StableVideoUNet(nn.Module):
         [n_win][B][W][H*W][4] buffer per pass, then ONE tail behind them (``sp_euler_step_windows_f16`` /
         ``sp_dpmpp2m_step_windows_f16``).  Both samplers take the stored-eps route: the Euler tail in ``conv_out``'s
         epilogue cannot see the other windows."""
-        from ..hip import ops
-
         b, _, ft, h, w = state.shape
         win = cond.num_frames
         pl, weights = self._window_plan(ft, win)
@@ -632,30 +599,13 @@ class StableVideoUNet(nn.Module):
         rows = b * win * h * w                                  # eps rows of one window of all videos
         eps_c = torch.empty((pl.n_win * rows, ld_eps), dtype=torch.float16, device=state.device)
         eps_u = torch.empty_like(eps_c) if cond.guided else None
-        ids = cond.added_ids32
         for k0 in range(0, pl.n_win, self.windows_per_call):
             n = min(self.windows_per_call, pl.n_win - k0)
             # [window][video] batch rows: the layout of the eps buffer
             xs = torch.cat([x[:, :, s:s + win] for s in pl.starts[k0:k0 + n]], dim=0).contiguous()
             dst = slice(k0 * rows, (k0 + n) * rows)
-
-            def rep(t):
-                return t if n == 1 else torch.cat([t] * n, dim=0)
-
-            ids_n = ids if ids.dim() == 1 else rep(ids)
-            if cond.guided and self.batched_cfg:
-                both = self._unet_pass(torch.cat([xs, xs], dim=0),
-                                       torch.cat([rep(cond.uncond_image_latents), rep(cond.image_latents)], dim=0),
-                                       torch.cat([rep(cond.uncond_embeddings), rep(cond.image_embeddings)], dim=0), in_scale,
-                                       step, added_ids32=ids_n if ids.dim() == 1 else torch.cat([ids_n, ids_n], dim=0))
-                eps_u[dst].copy_(both[:n * rows])
-                eps_c[dst].copy_(both[n * rows:])
-                continue
-            if cond.guided:
-                self._unet_pass(xs, rep(cond.uncond_image_latents), rep(cond.uncond_embeddings), in_scale, step,
-                                added_ids32=ids_n, eps_out=eps_u[dst])
-            self._unet_pass(xs, rep(cond.image_latents), rep(cond.image_embeddings), in_scale, step, added_ids32=ids_n,
-                            eps_out=eps_c[dst])
+            self._unet_passes(xs, cond, step, in_scale, windows=n,
+                              eps_out=(eps_c[dst], eps_u[dst] if cond.guided else None))
         out = torch.empty_like(state)
         common = dict(ld_eps=ld_eps, h=h, w=w, window=win, stride=pl.stride, n_win=pl.n_win, weights=weights,
                       frames_total=ft, ld_guidance=cond.guidance_ld)
