@@ -380,6 +380,39 @@ int sp_dpmpp2m_step_windows_f16(const void *state, const void *eps_cond, const v
                                 float sigma, float a, float b, float c1, float c2,
                                 int batch, int frames_total, int h, int w,
                                 int window, int stride, int n_win, const float *weights /*[n_win][window]*/, void *stream);
+/* The stochastic samplers: the two tails above with fresh noise at every step, n*z added in fp32 inside
+ * the update.  z is standard normal and a pure function of (the video's 64-bit seed, `step`, the element's position in the
+ * video's latent): Philox4x32-10 (csrc/noise.h) with, for element (c, f, p) of the video's (4, frames_total, H, W) latent,
+ * e = (c*frames_total + f)*H*W + p, f the GLOBAL frame: counter (e >> 2, step, 1, 0), key (seed & 0xffffffff, seed >> 32),
+ * lane e & 3 of the block's four Box-Muller normals.  Nothing depends on the video's row in the batch, on the windows or on
+ * who calls.  seeds is [batch] on the device, 8-byte aligned.  Arguments as for the _windows_ functions; weights == NULL with
+ * n_win == 1 and window == frames_total is the unwindowed form (eps rows [B][F][H*W][ld_eps], guidance indexed by the frame).
+ *   Euler ancestral:  t = x + (x - x0)/sigma*(sigma_down - sigma) in fp32, out = fp16(noise_scale*z + t), one rounding;
+ *                     sigma_down and noise_scale = s_noise*sigma_up from models/solver_schedule.py
+ *   2M SDE:           x' = noise_scale*z + (a*x + b*(c1*D - c2*D_prev)); D -> channels 4-7 without noise
+ * noise_scale == 0 launches the deterministic kernel: the bytes of the _windows_ / _rows_ functions for the same constants,
+ * seeds not read (may be NULL).  Refused besides what those refuse: null seeds with noise_scale != 0, misaligned seeds, a
+ * negative or non-finite noise_scale, 4*frames_total*H*W > 2^34. */
+int sp_euler_ancestral_step_f16(const void *latent, const void *eps_cond, const void *eps_uncond,
+                                int64_t ld_eps, const float *guidance, int64_t ld_guidance, void *out, float sigma,
+                                float sigma_down, int b, int frames_total, int h, int w,
+                                int window, int stride, int n_win, const float *weights /*[n_win][window] or NULL*/,
+                                float noise_scale, const uint64_t *seeds /*[batch], device*/, uint32_t step, void *stream);
+int sp_dpmpp2m_sde_step_f16(const void *state, const void *eps_cond, const void *eps_uncond,
+                            int64_t ld_eps, const float *guidance, int64_t ld_guidance, void *out_state,
+                            float sigma, float a, float b, float c1, float c2,
+                            int batch, int frames_total, int h, int w,
+                            int window, int stride, int n_win, const float *weights /*[n_win][window] or NULL*/,
+                            float noise_scale, const uint64_t *seeds /*[batch], device*/, uint32_t step, void *stream);
+/* out (B,4,F,H,W) fp16 = fp16(scale*z), the product rounded once, with z of counter (e >> 2, step, purpose, 0) as above: the initial latent of a video
+ * from its seed (scale = init_noise_sigma, step 0, purpose 0), or with purpose 1 the normals a tail adds at `step`.  Refused:
+ * null or misaligned pointers, a negative or non-finite scale, 4*F*H*W > 2^34. */
+int sp_randn_f16(void *out, const uint64_t *seeds /*[batch], device*/, float scale, int batch, int frames, int h, int w,
+                 uint32_t step, uint32_t purpose, void *stream);
+/* The generator's raw words, out [batch][n_blocks][4] (16-byte aligned): block j of video b is Philox4x32-10 of counter
+ * (j, step, purpose, 0) under the key of seeds[b]; n_blocks <= 2^32. */
+int sp_philox_blocks_u32(uint32_t *out, const uint64_t *seeds, int batch, int64_t n_blocks, uint32_t step,
+                         uint32_t purpose, void *stream);
 /* channel concat of two NHWC tensors (torch.cat([hidden, skip], dim=1) in the up blocks) */
 int sp_concat_channels_f16(const void *a, int ca, const void *b, int cb, void *out, int64_t rows,
                            void *stream);

@@ -3,8 +3,10 @@
 random-init full-width weights, no guidance (what bench.py's headline runs).  Same box, same process, same engine and weights;
 the two samplers alternate for ROUNDS rounds of STEPS steps each (host clock around a synchronised stretch), as
 tools/ab_forward.py alternates its arms.  The 2M arm carries the (2,8,14,72,128) state, stores conv_out's four eps channels
-and runs sp_dpmpp2m_step_rows_f16 behind them; the Euler arm applies its update in conv_out's epilogue.  Also timed with device
-events: the two update kernels alone on stored eps rows.
+and runs sp_dpmpp2m_step_rows_f16 behind them; the Euler arm applies its update in conv_out's epilogue.  The two stochastic
+samplers (euler_a, dpmpp_2m_sde; eta = 1) are two more arms of the same alternation: the stored-eps route and the tail kernel
+with the step's noise evaluated in registers.  Also timed with device events: the update kernels alone on stored eps rows,
+and sp_randn_f16 against torch.randn for the initial latent.
 usage: sampler_timing.py [--rounds 7] [--steps 6] [--commit TEXT] [--out profiles/sampler_timing.txt]"""
 import argparse, os, statistics, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -30,7 +32,12 @@ torch.manual_seed(42)
 euler.set_dummy_conditioning(B, F, H, W, dev)
 solver.set_conditioning(euler._cond.image_embeddings, euler._cond.image_latents, num_frames=F)
 noise = torch.randn(B, 4, F, H, W, device=dev, dtype=torch.float16) * euler.init_noise_sigma
-arms = {"euler": (euler, noise), "dpmpp_2m": (solver, solver.init_state(noise))}
+euler_a = StableVideoUNet(unet=euler.unet, timesteps=ts, sampler="euler_a")
+sde = StableVideoUNet(unet=euler.unet, timesteps=ts, sampler="dpmpp_2m_sde")
+for m in (euler_a, sde):
+    m.set_conditioning(euler._cond.image_embeddings, euler._cond.image_latents, num_frames=F, noise_seed=[42, 43])
+arms = {"euler": (euler, noise), "dpmpp_2m": (solver, solver.init_state(noise)), "euler_a": (euler_a, noise),
+        "dpmpp_2m_sde": (sde, sde.init_state(noise))}
 first = 1                                    # steps 1.. : the second-order form of the 2M kernel (step 0 is first order)
 
 
@@ -64,6 +71,20 @@ with torch.no_grad():
         "sp_dpmpp2m_step_rows_f16": lambda: ops.dpmpp2m_step(state, eps, None, None, out8, ld_eps=64, sigma=sigma, a=a_, b=b_, c1=c1,
                                                              c2=c2, batch=B, frames=F, h=H, w=W),
     }
+    seeds = euler_a._cond.noise_seeds
+    down, n_e = euler_a._noise_coef[first]
+    sa, sb, sc1, sc2, n_s = sde._noise_coef[first]
+    rand = torch.empty_like(noise)
+    kernels.update({
+        "sp_euler_ancestral_step_f16": lambda: ops.euler_ancestral_step(noise, eps, None, None, out4, ld_eps=64, sigma=sigma,
+                                                                        sigma_down=down, noise_scale=n_e, seeds=seeds, step=first,
+                                                                        b=B, frames_total=F, h=H, w=W),
+        "sp_dpmpp2m_sde_step_f16": lambda: ops.dpmpp2m_sde_step(state, eps, None, None, out8, ld_eps=64, sigma=sigma, a=sa, b=sb,
+                                                                c1=sc1, c2=sc2, noise_scale=n_s, seeds=seeds, step=first, batch=B,
+                                                                frames_total=F, h=H, w=W),
+        "sp_randn_f16": lambda: ops.randn(rand, seeds, scale=euler.init_noise_sigma),
+        "torch.randn * sigma": lambda: torch.randn(B, 4, F, H, W, device=dev, dtype=torch.float16) * euler.init_noise_sigma,
+    })
     kernel_us = {}
     for name, fn in kernels.items():
         fn(); torch.cuda.synchronize()
@@ -86,14 +107,13 @@ lines = [f"device: {torch.cuda.get_device_name(0)}; commit: {commit or 'unknown'
          f"host clock around the synchronised stretch, ms per step (= per call of two videos)"]
 med = {a: statistics.median(v) for a, v in times.items()}
 for a, v in times.items():
-    lines.append(f"  {a:<9} median {med[a]:8.3f} ms  best {min(v):8.3f}  worst {max(v):8.3f}   rounds: {' '.join(f'{t:.2f}' for t in v)}")
+    lines.append(f"  {a:<12} median {med[a]:8.3f} ms  best {min(v):8.3f}  worst {max(v):8.3f}   rounds: {' '.join(f'{t:.2f}' for t in v)}")
 spread = max((max(v) - min(v)) / statistics.median(v) for v in times.values())
-diff = med["dpmpp_2m"] / med["euler"] - 1
-lines.append(f"  dpmpp_2m against euler, medians: {100 * diff:+.2f} % per step; run-to-run spread (max - min over median, the wider arm): "
-             f"{100 * spread:.2f} %")
-lines.append("update kernels alone on stored eps rows (ld_eps 64), device events, 20 launches each:")
+lines.append("  against euler, medians: " + ", ".join(f"{a} {100 * (med[a] / med['euler'] - 1):+.2f} %" for a in arms if a != "euler")
+             + f" per step; run-to-run spread (max - min over median, the widest arm): {100 * spread:.2f} %")
+lines.append("kernels alone (the updates on stored eps rows, ld_eps 64; the initial latent), device events, 20 launches each:")
 for name, v in kernel_us.items():
-    lines.append(f"  {name:<26} median {statistics.median(v):7.1f} us  min {min(v):7.1f}  max {max(v):7.1f}")
+    lines.append(f"  {name:<28} median {statistics.median(v):7.1f} us  min {min(v):7.1f}  max {max(v):7.1f}")
 lines.append(f"arithmetic consequence at the medians: 25 Euler steps = {25 * med['euler'] / 1e3:.3f} s per call; dpmpp_2m steps: "
              + ", ".join(f"{n_} = {n_ * med['dpmpp_2m'] / 1e3:.3f} s" for n_ in (13, 15, 20, 25))
              + "  (step counts are arithmetic only: no claim about image quality on trained weights)")

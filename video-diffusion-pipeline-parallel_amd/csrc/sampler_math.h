@@ -1,6 +1,7 @@
 // The arithmetic of the sampler tails, stated once: the fp16 guidance mix, the Euler update and the DPM-Solver++(2M) update of
-// one latent value.  sampler_tail.hip evaluates every tail with these functions; the conv_out epilogue of gemm.hip keeps a
-// copy of the mix and the Euler update in plain C that must return the same bytes
+// one latent value, and the two stochastic forms that add n*z behind them.  sampler_tail.hip evaluates every tail with these
+// functions; the conv_out epilogue of gemm.hip keeps a copy of the mix and the Euler update in plain C that must return the same
+// bytes
 // (tests/test_unet_gpu.py::test_euler_tail_in_conv_out_epilogue_is_bit_identical).
 //
 // Every body is compiled with fp contraction off and names each fused operation as an fmaf, so where a product is rounded
@@ -14,6 +15,7 @@ struct SamplerCoef {
   float c_out, c_skip;
   float inv_sigma, dt;      // Euler
   float a, b, c1, c2;       // 2M
+  float n;                  // noise scale of the step (Euler ancestral, 2M SDE); 0 in the deterministic samplers
 };
 
 // a*b + c rounded to fp16 inside the fma.  For a scalar store the compiler fuses an fp32 fma with the conversion behind it
@@ -53,4 +55,25 @@ __device__ __forceinline__ float dpmpp2m_update(float x, float e, float d_prev, 
   const float dd = history ? fmaf(k.c1, d, -(k.c2 * d_prev)) : d;
   *denoised = d;
   return fmaf(k.a, x, k.b * dd);
+}
+
+// The Euler ancestral step: the Euler update towards sigma_down (k.dt = sigma_down - sigma) kept in fp32, t = dt*d + x, and
+// the step's noise joins it inside the one rounding to fp16: n*z + t.
+__device__ __forceinline__ f16 euler_ancestral_update(float x, float e, float z, const SamplerCoef &k) {
+#pragma clang fp contract(off)
+  const float x0 = fmaf(e, k.c_out, x * k.c_skip);
+  const float d = (x - x0) * k.inv_sigma;
+  const float t = fmaf(k.dt, d, x);
+  return fma_to_f16(k.n, z, t);
+}
+
+// The 2M SDE step: x' = n*z + (a*x + b*(c1*D - c2*D_prev)), the deterministic update as dpmpp2m_update rounds it and one more
+// fma; D leaves without noise.  Both in fp32.
+__device__ __forceinline__ float dpmpp2m_sde_update(float x, float e, float d_prev, bool history, float z, const SamplerCoef &k,
+                                                    float *denoised) {
+#pragma clang fp contract(off)
+  const float d = fmaf(x, k.c_skip, e * k.c_out);
+  const float dd = history ? fmaf(k.c1, d, -(k.c2 * d_prev)) : d;
+  *denoised = d;
+  return fmaf(k.n, z, fmaf(k.a, x, k.b * dd));
 }

@@ -4,7 +4,10 @@
 // overlapping frame windows (temporal co-denoising): a latent of F_total frames cut into n_win windows of `window` frames,
 // `stride` apart, the UNet run once per window, the eps rows of all windows in one buffer [n_win][B][window][H*W][ld_eps],
 // blended frame by frame with the host's normalised weight table in front of ONE update of the whole latent.  The arithmetic
-// is that of sampler_math.h.  See sp_euler_step_rows_f16 ... sp_dpmpp2m_step_windows_f16 in svdpipe.h.
+// is that of sampler_math.h.  See sp_euler_step_rows_f16 ... sp_dpmpp2m_step_windows_f16 in svdpipe.h.  The stochastic
+// samplers (sp_euler_ancestral_step_f16, sp_dpmpp2m_sde_step_f16) are the same kernel with NOISE: behind the window loop it
+// evaluates the step's normals of its elements from the video's seed (noise.h) and adds n*z inside the update.
+#include "noise.h"
 #include "sampler_math.h"
 
 namespace {
@@ -20,12 +23,15 @@ enum { EULER = 0, FIRST_ORDER = 1, SECOND_ORDER = 2 };   // FIRST_ORDER: 2M with
 // store and no other thread touches those elements, so out == st (update in place) is safe; hence no __restrict__ on the two.
 // WINDOWS = false is one window that is the whole latent: no weight table, one eps row per pixel at bf * hw + p, guidance
 // indexed by the frame; the loop below is then one pass and e the eps itself.
-template <int PX, int MODE, bool WINDOWS>
+// NOISE: z of element (c, f, p) of video b from (seeds[b], step), f the GLOBAL frame: with PX = 4 the thread's four pixels of a
+// channel are the four lanes of one block (hw % 4 == 0), with PX = 1 it evaluates its element's block and takes its lane.
+template <int PX, int MODE, bool WINDOWS, bool NOISE>
 __global__ __launch_bounds__(256) void sampler_tail_kernel(const f16 *st, const f16 *__restrict__ ec,
                                                            const f16 *__restrict__ eu, int64_t ld_eps,
                                                            const float *__restrict__ gs, int64_t ld_g,
                                                            const float *__restrict__ wn, f16 *out, SamplerCoef k,
-                                                           WindowPlan wp, int64_t hw, int64_t total) {
+                                                           WindowPlan wp, int64_t hw, int64_t total,
+                                                           const uint64_t *__restrict__ seeds, uint32_t step) {
   typedef f16 vec __attribute__((ext_vector_type(PX)));
   constexpr int CH = MODE == EULER ? 4 : 8;
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // one group of PX pixels of a (b, f)
@@ -84,16 +90,25 @@ __global__ __launch_bounds__(256) void sampler_tail_kernel(const f16 *st, const 
       }
     }
   }
+  uint64_t seed = 0;
+  if constexpr (NOISE) seed = seeds[b];
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
+    float z[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (NOISE) {
+      const int64_t el = ((int64_t)c * frames + f) * hw + p;             // in the video's (4, F_total, H, W) latent
+      if constexpr (PX == 4) noise_normals4(noise_block(seed, (uint32_t)(el >> 2), step, NOISE_STEP), z);
+      else z[0] = noise_normal_at(seed, el, step, NOISE_STEP);
+    }
     vec xo, dn;
 #pragma unroll
     for (int j = 0; j < PX; ++j) {
       if constexpr (MODE == EULER) {
-        xo[j] = euler_update(x[c][j], e[c][j], k);
+        xo[j] = NOISE ? euler_ancestral_update(x[c][j], e[c][j], z[j], k) : euler_update(x[c][j], e[c][j], k);
       } else {
         float d;
-        xo[j] = (f16)dpmpp2m_update(x[c][j], e[c][j], dp[c][j], MODE == SECOND_ORDER, k, &d);
+        xo[j] = (f16)(NOISE ? dpmpp2m_sde_update(x[c][j], e[c][j], dp[c][j], MODE == SECOND_ORDER, z[j], k, &d)
+                            : dpmpp2m_update(x[c][j], e[c][j], dp[c][j], MODE == SECOND_ORDER, k, &d));
         dn[j] = (f16)d;
       }
     }
@@ -113,15 +128,24 @@ struct Tail {
   SamplerCoef k;
   WindowPlan wp;
   bool wide;
+  const uint64_t *seeds;   // [batch] on the device; read only where k.n != 0
+  uint32_t step;
 };
 
-template <int MODE>
-void launch(const Tail &t, void *stream) {
-  const auto kernel = t.wn ? (t.wide ? sampler_tail_kernel<4, MODE, true> : sampler_tail_kernel<1, MODE, true>)
-                           : (t.wide ? sampler_tail_kernel<4, MODE, false> : sampler_tail_kernel<1, MODE, false>);
+template <int MODE, bool NOISE>
+void launch_form(const Tail &t, void *stream) {
+  const auto kernel = t.wn ? (t.wide ? sampler_tail_kernel<4, MODE, true, NOISE> : sampler_tail_kernel<1, MODE, true, NOISE>)
+                           : (t.wide ? sampler_tail_kernel<4, MODE, false, NOISE> : sampler_tail_kernel<1, MODE, false, NOISE>);
   const int64_t total = (int64_t)t.wp.batch * t.wp.frames * t.hw / (t.wide ? 4 : 1);
   hipLaunchKernelGGL(kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, t.st, t.ec, t.eu, t.ld_eps,
-                     t.gs, t.ld_g, t.wn, t.out, t.k, t.wp, t.hw, total);
+                     t.gs, t.ld_g, t.wn, t.out, t.k, t.wp, t.hw, total, t.seeds, t.step);
+}
+
+// n == 0 (the deterministic samplers, eta == 0, the last step) is the kernel without noise: the bytes of the existing entries
+template <int MODE>
+void launch(const Tail &t, void *stream) {
+  if (t.k.n != 0.f) launch_form<MODE, true>(t, stream);
+  else launch_form<MODE, false>(t, stream);
 }
 
 // Everything all entry points refuse; on success fills the call (but for the step's own constants in t->k).  `windows`: the
@@ -152,7 +176,28 @@ int check(const char *name, const void *state, const void *eps_cond, const void 
   *t = Tail{name, (const f16 *)state, (const f16 *)eps_cond, (const f16 *)eps_uncond, guidance, weights, ld_eps, ld_guidance, hw,
             (f16 *)out, SamplerCoef{-sigma / sqrtf(s2), 1.0f / s2}, WindowPlan{frames_total, window, stride, n_win, batch},
             // four pixels per thread where every plane access stays 8-byte aligned
-            hw % 4 == 0 && s0 % 8 == 0 && o0 % 8 == 0};
+            hw % 4 == 0 && s0 % 8 == 0 && o0 % 8 == 0, nullptr, 0u};
+  return SP_OK;
+}
+
+// The stochastic entries: check() with the unwindowed form spelled as weights == NULL, n_win == 1, window == frames_total,
+// then the noise arguments.
+int check_noise(const char *name, const void *state, const void *eps_cond, const void *eps_uncond, int64_t ld_eps,
+                const float *guidance, int64_t ld_guidance, void *out, float sigma, int channels, int batch, int frames_total,
+                int h, int w, int window, int stride, int n_win, const float *weights, float noise_scale,
+                const uint64_t *seeds, uint32_t step, Tail *t) {
+  const bool whole = !weights && n_win == 1 && window == frames_total;
+  if (int rc = check(name, state, eps_cond, eps_uncond, ld_eps, guidance, ld_guidance, out, sigma, channels, batch, frames_total,
+                     h, w, !whole, window, whole ? window : stride, n_win, weights, t))
+    return rc;
+  SP_REQUIRE(noise_scale >= 0.f && noise_scale <= 3.402823466e38f, "%s: noise_scale = %g must be finite and not negative", name,
+             (double)noise_scale);
+  SP_REQUIRE(noise_scale == 0.f || seeds, "%s: null seeds with noise_scale = %g (one 64-bit seed per video, on the device)",
+             name, (double)noise_scale);
+  SP_REQUIRE((uintptr_t)seeds % 8 == 0, "%s: seeds must be 8-byte aligned", name);
+  SP_REQUIRE(noise_fits(frames_total, t->hw), "%s: 4*frames_total*h*w = 4*%d*%lld exceeds 2^34, the noise address' range", name,
+             frames_total, (long long)t->hw);
+  t->k.n = noise_scale; t->seeds = seeds; t->step = step;
   return SP_OK;
 }
 
@@ -222,6 +267,30 @@ extern "C" int sp_dpmpp2m_step_windows_f16(const void *state, const void *eps_co
   Tail t;
   if (int rc = check("sp_dpmpp2m_step_windows_f16", state, eps_cond, eps_uncond, ld_eps, guidance, ld_guidance, out_state, sigma, 8, batch, frames_total,
                      h, w, true, window, stride, n_win, weights, &t))
+    return rc;
+  return dpmpp2m_step(t, a, b, c1, c2, stream);
+}
+
+extern "C" int sp_euler_ancestral_step_f16(const void *latent, const void *eps_cond, const void *eps_uncond, int64_t ld_eps,
+                                           const float *guidance, int64_t ld_guidance, void *out, float sigma,
+                                           float sigma_down, int b, int frames_total, int h, int w, int window, int stride,
+                                           int n_win, const float *weights, float noise_scale, const uint64_t *seeds,
+                                           uint32_t step, void *stream) {
+  Tail t;
+  if (int rc = check_noise("sp_euler_ancestral_step_f16", latent, eps_cond, eps_uncond, ld_eps, guidance, ld_guidance, out, sigma, 4, b,
+                           frames_total, h, w, window, stride, n_win, weights, noise_scale, seeds, step, &t))
+    return rc;
+  return euler_step(t, sigma, sigma_down, stream);
+}
+
+extern "C" int sp_dpmpp2m_sde_step_f16(const void *state, const void *eps_cond, const void *eps_uncond, int64_t ld_eps,
+                                       const float *guidance, int64_t ld_guidance, void *out_state, float sigma, float a,
+                                       float b, float c1, float c2, int batch, int frames_total, int h, int w, int window,
+                                       int stride, int n_win, const float *weights, float noise_scale, const uint64_t *seeds,
+                                       uint32_t step, void *stream) {
+  Tail t;
+  if (int rc = check_noise("sp_dpmpp2m_sde_step_f16", state, eps_cond, eps_uncond, ld_eps, guidance, ld_guidance, out_state, sigma, 8,
+                           batch, frames_total, h, w, window, stride, n_win, weights, noise_scale, seeds, step, &t))
     return rc;
   return dpmpp2m_step(t, a, b, c1, c2, stream);
 }

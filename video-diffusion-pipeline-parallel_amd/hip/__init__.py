@@ -46,6 +46,7 @@ class GemmDesc(ctypes.Structure):
 
 # name -> (restype, argtypes); every symbol declared in include/svdpipe.h
 _P, _I, _L, _F, _Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
+_U = ctypes.c_uint32
 SIGNATURES = {
     "sp_last_error": (ctypes.c_char_p, []),
     "sp_version": (_I, []),
@@ -81,6 +82,11 @@ SIGNATURES = {
     "sp_dpmpp2m_step_rows_f16": (_I, [_P, _P, _P, _L, _P, _L, _P, _F, _F, _F, _F, _F, _I, _I, _I, _I, _P]),
     "sp_euler_step_windows_f16": (_I, [_P, _P, _P, _L, _P, _L, _P, _F, _F, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "sp_dpmpp2m_step_windows_f16": (_I, [_P, _P, _P, _L, _P, _L, _P, _F, _F, _F, _F, _F, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "sp_euler_ancestral_step_f16": (_I, [_P, _P, _P, _L, _P, _L, _P, _F, _F, _I, _I, _I, _I, _I, _I, _I, _P, _F, _P, _U, _P]),
+    "sp_dpmpp2m_sde_step_f16": (_I, [_P, _P, _P, _L, _P, _L, _P, _F, _F, _F, _F, _F, _I, _I, _I, _I, _I, _I, _I, _P, _F, _P, _U,
+                                     _P]),
+    "sp_randn_f16": (_I, [_P, _P, _F, _I, _I, _I, _I, _U, _U, _P]),
+    "sp_philox_blocks_u32": (_I, [_P, _P, _I, _L, _U, _U, _P]),
     "sp_concat_channels_f16": (_I, [_P, _I, _P, _I, _P, _L, _P]),
     "sp_add_rowvec_f16": (_I, [_P, _P, _P, _L, _I, _P]),
     "sp_softmax_rows_f16": (_I, [_P, _L, _L, _I, _P]),

@@ -971,6 +971,81 @@ def dpmpp2m_step_windows(state, eps_cond, eps_uncond, guidance, out_state, *, ld
     return out_state
 
 
+def _seeds(seeds, batch: int, name: str):
+    """The per-video noise seeds of a stochastic tail: int64 ``[batch]`` on the device (the kernels read them as uint64)."""
+    if seeds.dtype != torch.int64 or not seeds.is_cuda or seeds.shape != (batch,) or not seeds.is_contiguous():
+        raise ValueError(f"{name}: seeds must be a contiguous int64 [{batch}] tensor on the HIP device; got {seeds.dtype} "
+                         f"{tuple(seeds.shape)}")
+    return seeds.data_ptr()
+
+
+def _noise_tail_args(name, tensors, channels, batch, frames_total, h, w, eps_cond, eps_uncond, ld_eps, window, stride, n_win,
+                     weights, noise_scale, seeds):
+    """``(window, stride, n_win, weights pointer, seeds pointer)`` of a stochastic tail; ``weights=None`` is the unwindowed
+    form (one window that is the whole latent)."""
+    if weights is None:
+        window, stride, n_win = frames_total, frames_total, 1
+        for what, t in tensors.items():
+            if _f16(t, what).shape != (batch, channels, frames_total, h, w) or not t.is_contiguous():
+                raise ValueError(f"{name}: {what} must be a contiguous ({batch}, {channels}, {frames_total}, {h}, {w}) tensor; "
+                                 f"got {tuple(t.shape)}, strides {tuple(t.stride())}")
+    else:
+        _window_args(name, tensors, channels, batch, frames_total, h, w, eps_cond, eps_uncond, ld_eps, window, n_win, weights)
+    if seeds is None and noise_scale != 0.0:
+        raise ValueError(f"{name}: noise_scale={noise_scale} needs the videos' seeds")
+    return window, stride, n_win, _ptr(weights), None if seeds is None else _seeds(seeds, batch, name)
+
+
+def euler_ancestral_step(latent, eps_cond, eps_uncond, guidance, out, *, ld_eps, sigma, sigma_down, noise_scale, seeds, step,
+                         b, frames_total, h, w, window=None, stride=None, n_win=None, weights=None, ld_guidance=0):
+    """The Euler ancestral update of ``latent`` (B,4,F_total,H,W): the Euler step to ``sigma_down`` plus ``noise_scale * z``,
+    ``z`` the normals of (``seeds[b]``, ``step``, the element) (``sp_euler_ancestral_step_f16``).  ``weights=None``: eps rows
+    ``[B][F][H*W][ld_eps]``; else the window arguments of ``euler_step_windows``."""
+    window, stride, n_win, wp, sp = _noise_tail_args("euler_ancestral_step", {"latent": latent, "out": out}, 4, b, frames_total,
+                                                     h, w, eps_cond, eps_uncond, ld_eps, window, stride, n_win, weights,
+                                                     noise_scale, seeds)
+    _check(load().sp_euler_ancestral_step_f16(latent.data_ptr(), eps_cond.data_ptr(), _ptr(eps_uncond), ld_eps, _ptr(guidance),
+                                              int(ld_guidance), out.data_ptr(), sigma, sigma_down, b, frames_total, h, w,
+                                              window, stride, n_win, wp, noise_scale, sp, int(step), _stream()),
+           "sp_euler_ancestral_step_f16")
+    return out
+
+
+def dpmpp2m_sde_step(state, eps_cond, eps_uncond, guidance, out_state, *, ld_eps, sigma, a, b, c1, c2, noise_scale, seeds, step,
+                     batch, frames_total, h, w, window=None, stride=None, n_win=None, weights=None, ld_guidance=0):
+    """The DPM-Solver++(2M) SDE update of the 8-channel ``state`` (B,8,F_total,H,W): ``dpmpp2m_step`` with ``noise_scale * z``
+    added to the sample, not to the stored estimate (``sp_dpmpp2m_sde_step_f16``); windows as for ``euler_ancestral_step``."""
+    window, stride, n_win, wp, sp = _noise_tail_args("dpmpp2m_sde_step", {"state": state, "out_state": out_state}, 8, batch,
+                                                     frames_total, h, w, eps_cond, eps_uncond, ld_eps, window, stride, n_win,
+                                                     weights, noise_scale, seeds)
+    _check(load().sp_dpmpp2m_sde_step_f16(state.data_ptr(), eps_cond.data_ptr(), _ptr(eps_uncond), ld_eps, _ptr(guidance),
+                                          int(ld_guidance), out_state.data_ptr(), sigma, a, b, c1, c2, batch, frames_total, h, w,
+                                          window, stride, n_win, wp, noise_scale, sp, int(step), _stream()),
+           "sp_dpmpp2m_sde_step_f16")
+    return out_state
+
+
+def randn(out, seeds, *, scale=1.0, step=0, purpose=0):
+    """``out`` (B,4,F,H,W) fp16 = ``scale * z``: video ``b``'s normals of (``seeds[b]``, ``step``, ``purpose``), whatever it is
+    batched with (``sp_randn_f16``; purpose 0 = the initial latent, 1 = a sampler step's noise)."""
+    if _f16(out, "out").dim() != 5 or out.shape[1] != 4 or not out.is_contiguous():
+        raise ValueError(f"randn: out must be a contiguous (B, 4, F, H, W) tensor; got {tuple(out.shape)}")
+    b, _, f, h, w = out.shape
+    _check(load().sp_randn_f16(out.data_ptr(), _seeds(seeds, b, "randn"), scale, b, f, h, w, int(step), int(purpose), _stream()),
+           "sp_randn_f16")
+    return out
+
+
+def philox_blocks(out, seeds, *, step=0, purpose=0):
+    """``out`` int32 ``[B][n_blocks][4]``: the generator's raw words (``sp_philox_blocks_u32``)."""
+    if out.dtype != torch.int32 or not out.is_cuda or out.dim() != 3 or out.shape[2] != 4 or not out.is_contiguous():
+        raise ValueError(f"philox_blocks: out must be a contiguous int32 [B][n_blocks][4] tensor on the HIP device; got "
+                         f"{out.dtype} {tuple(out.shape)}")
+    _check(load().sp_philox_blocks_u32(out.data_ptr(), _seeds(seeds, out.shape[0], "philox_blocks"), out.shape[0], out.shape[1],
+                                       int(step), int(purpose), _stream()), "sp_philox_blocks_u32")
+    return out
+
+
 def concat_channels(a, ca, b, cb, out, rows):
     with _Timed("concat", 0.0, 2 * 2.0 * rows * (ca + cb)):
         _check(load().sp_concat_channels_f16(a.data_ptr(), ca, b.data_ptr(), cb, out.data_ptr(), rows, _stream()),

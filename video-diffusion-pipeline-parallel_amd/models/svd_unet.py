@@ -17,6 +17,7 @@ caller decides the order.
 
 from __future__ import annotations
 
+import dataclasses
 import math
 import os
 from collections.abc import Sequence
@@ -40,7 +41,8 @@ class VideoConditioning:
     video has the same (fps-1, motion bucket, noise aug) triple, else [B][3]; ``guidance32`` None (no guidance), [F]
     (one per-frame scale row for every video, ``guidance_ld`` 0) or [B][F] (one row per video, ``guidance_ld`` = F);
     ``guidance_scale_tensor`` the same scales in fp16, (1 or B, 1, F, 1, 1);
-    ``uncond_*`` the zero conditioning of the guidance pass (None without guidance)."""
+    ``uncond_*`` the zero conditioning of the guidance pass (None without guidance); ``noise_seeds`` int64 [B], each video's
+    noise seed for the stochastic samplers (None: none given; ``with_noise_seed``)."""
 
     image_embeddings: torch.Tensor
     image_latents: torch.Tensor
@@ -53,6 +55,7 @@ class VideoConditioning:
     uncond_embeddings: torch.Tensor | None
     uncond_image_latents: torch.Tensor | None
     num_frames: int
+    noise_seeds: torch.Tensor | None = None
 
     @property
     def guided(self) -> bool:
@@ -66,7 +69,23 @@ class VideoConditioning:
         """The device tensors by field name (None where absent)."""
         return {k: getattr(self, k) for k in ("image_embeddings", "image_latents", "added_time_ids", "added_ids32",
                                               "guidance32", "guidance_scale_tensor", "uncond_embeddings",
-                                              "uncond_image_latents")}
+                                              "uncond_image_latents", "noise_seeds")}
+
+    def with_noise_seed(self, seed) -> "VideoConditioning":
+        """This conditioning with other noise seeds (one int for every video, or one per video, in [0, 2^63)); every other
+        tensor is shared, not copied."""
+        return dataclasses.replace(self, noise_seeds=_noise_seeds(seed, self.batch, self.image_embeddings.device))
+
+
+def _noise_seeds(seed, batch: int, device) -> torch.Tensor | None:
+    """``noise_seed=`` of ``prepare_conditioning`` as the int64 [B] device tensor the tails read; None stays None."""
+    if seed is None:
+        return None
+    values = [int(s) for s in _per_video("noise_seed", seed, batch)]
+    for s in values:
+        if not 0 <= s < 2 ** 63:
+            raise ValueError(f"noise_seed must be in [0, 2^63); got {s}")
+    return torch.tensor(values, dtype=torch.int64, device=device)
 
 
 def _per_video(name: str, value, batch: int) -> list:
@@ -92,6 +111,8 @@ class StableVideoUNet(nn.Module):
         window_stride: int | None = None,
         window_weights: str = "triangle",
         windows_per_call: int = 1,
+        eta: float = 1.0,
+        s_noise: float = 1.0,
     ) -> None:
         """``batched_cfg`` (extension): run the unconditional and conditional passes of
         classifier-free guidance as ONE batch-2 UNet forward instead of two sequential passes
@@ -101,7 +122,12 @@ class StableVideoUNet(nn.Module):
         DPM-Solver++(2M), second order with still one UNet evaluation per step.  Its history -- the previous step's
         denoised estimate -- rides in the latent: ``forward`` then takes and returns (B,8,F,H,W), channels 0-3 the sample,
         channels 4-7 the estimate (``init_state`` / ``sample_of``), the model keeps no state between calls, and the
-        steps are called in index order (0, 1, 2, ...).
+        steps are called in index order (0, 1, 2, ...).  ``"euler_a"`` (Euler ancestral, 4-channel latent) and
+        ``"dpmpp_2m_sde"`` (the SDE form of 2M, 8-channel state) are the stochastic samplers: every
+        step adds fresh noise of scale ``eta`` (0: the deterministic sampler's bytes) times ``s_noise``, evaluated inside
+        the tail kernel from the videos' seeds (``prepare_conditioning(..., noise_seed=)``), the step index and the
+        element's position -- no generator state, so a sample may change rank, stream or graph lane between steps.  Steps
+        ascend as for ``dpmpp_2m``; ``eta`` and ``s_noise`` are ignored by the deterministic samplers.
 
         ``window_stride`` (extension): long videos by temporal co-denoising.  ``forward`` then accepts a
         latent of more frames than the conditioning's ``num_frames`` = W: every step runs the UNet on overlapping windows of
@@ -123,7 +149,9 @@ class StableVideoUNet(nn.Module):
         if sampler not in solver_schedule.SAMPLERS:
             raise ValueError(f"sampler must be one of {solver_schedule.SAMPLERS}; got {sampler!r}")
         self.sampler = sampler
-        self.state_channels = 8 if sampler == "dpmpp_2m" else 4
+        self.stochastic = sampler in solver_schedule.STOCHASTIC
+        self.eta, self.s_noise = float(eta), float(s_noise)
+        self.state_channels = 8 if sampler in ("dpmpp_2m", "dpmpp_2m_sde") else 4
         self.batched_cfg = batched_cfg
         self._use_graphs = os.environ.get("VDPP_GRAPHS", "0") == "1"
         self._graphs: dict = {}          # (calling stream, step, latent shape) -> (graph, static_in, static_out)
@@ -152,6 +180,12 @@ class StableVideoUNet(nn.Module):
         self._t_dev = self.scheduler_timesteps.to(self.unet.device)   # device table, indexed per step
         self._init_noise_sigma = float((sig[0] ** 2 + 1) ** 0.5)
         self._solver_coef = solver_schedule.dpmpp_2m_coefficients(sig) if self.sampler == "dpmpp_2m" else None
+        # the stochastic samplers' per-step constants: (sigma_down, n) / (a, b, c1, c2, n)
+        self._noise_coef = None
+        if self.sampler == "euler_a":
+            self._noise_coef = solver_schedule.euler_ancestral_coefficients(sig, self.eta, self.s_noise)
+        elif self.sampler == "dpmpp_2m_sde":
+            self._noise_coef = solver_schedule.dpmpp_2m_sde_coefficients(sig, self.eta, self.s_noise)
 
     # ------------------------------------------------------------------ sampler state
     def init_state(self, noise: torch.Tensor) -> torch.Tensor:
@@ -170,6 +204,18 @@ class StableVideoUNet(nn.Module):
         """The sample (B,4,F,H,W) inside a stepped tensor: the tensor itself for Euler, a view of channels 0-3 for
         ``dpmpp_2m``."""
         return state if self.state_channels == 4 else state[:, :4]
+
+    def initial_noise(self, seeds, frames: int, h: int, w: int) -> torch.Tensor:
+        """The initial latent (B,4,F,H,W) of the videos with the noise seeds ``seeds`` (one int, a sequence of ints or an
+        int64 [B] device tensor): ``init_noise_sigma`` times the normals of (seed, step 0, purpose 0, element)
+        (``sp_randn_f16``).  A video's noise depends on its seed and shape alone, not on what it is batched with."""
+        if not isinstance(seeds, torch.Tensor) or seeds.dtype != torch.int64 or not seeds.is_cuda:
+            if isinstance(seeds, torch.Tensor):
+                seeds = seeds.tolist()
+            values = list(seeds) if isinstance(seeds, (list, tuple)) else [seeds]
+            seeds = _noise_seeds(values, len(values), self.unet.device)
+        out = torch.empty((seeds.shape[0], 4, int(frames), int(h), int(w)), dtype=torch.float16, device=seeds.device)
+        return ops.randn(out, seeds.contiguous(), scale=self._init_noise_sigma, step=0, purpose=0)
 
     @property
     def init_noise_sigma(self) -> float:
@@ -194,6 +240,8 @@ class StableVideoUNet(nn.Module):
         sampler: str = "euler",
         window_stride: int | None = None,
         window_weights: str = "triangle",
+        eta: float = 1.0,
+        s_noise: float = 1.0,
         **kwargs,
     ) -> "StableVideoUNet":
         """Load ``<model_id>/unet/diffusion_pytorch_model*.safetensors`` from a LOCAL directory.
@@ -243,20 +291,21 @@ class StableVideoUNet(nn.Module):
         if timesteps is None:
             timesteps = cls._default_timestep_schedule(num_steps=25)
         return cls(unet=SVDUNetHIP(cfg, sd, device), timesteps=timesteps, dtype=torch_dtype, sampler=sampler,
-                   window_stride=window_stride, window_weights=window_weights)
+                   window_stride=window_stride, window_weights=window_weights, eta=eta, s_noise=s_noise)
 
     @classmethod
     def from_random_init(cls, timesteps: Sequence[int], *, config: UNetConfig | None = None, seed: int = 0,
                          device="cuda", fp8_attention: bool | None = None,
                          long_attention: bool | None = None, sampler: str = "euler",
-                         window_stride: int | None = None, window_weights: str = "triangle") -> "StableVideoUNet":
+                         window_stride: int | None = None, window_weights: str = "triangle", eta: float = 1.0,
+                         s_noise: float = 1.0) -> "StableVideoUNet":
         """Random weights of the exact SVD architecture (benchmarks / tests; no checkpoint needed)."""
         cfg = config or UNetConfig.svd()
         sd = random_state_dict(cfg, seed=seed, device=device, dtype=torch.float16)
         unet = SVDUNetHIP(cfg, sd, device, fp8_attention=fp8_attention, long_attention=long_attention)
         del sd
         return cls(unet=unet, timesteps=timesteps, sampler=sampler, window_stride=window_stride,
-                   window_weights=window_weights)
+                   window_weights=window_weights, eta=eta, s_noise=s_noise)
 
     def enable_graphs(self, enabled: bool = True) -> None:
         """Replay each diffusion step from a captured HIP graph (one graph per step index and latent shape).
@@ -298,13 +347,15 @@ class StableVideoUNet(nn.Module):
         noise_aug_strength=0.02,
         guidance_scale=None,
         num_frames: int = 14,
+        noise_seed=None,
     ) -> VideoConditioning:
         """The conditioning of one (micro-)batch of videos as an immutable object for ``forward(..., conditioning=)``.
 
         ``fps``, ``motion_bucket_id``, ``noise_aug_strength`` and ``guidance_scale`` are each a scalar (every video) or
         a sequence of one value per video.  Guidance of video i is ``linspace(1, g_i, num_frames)`` per frame; a batch
         mixes no guided (g > 1) and unguided videos (ValueError), a sequence of another length than the batch is a
-        ValueError.  Videos that agree on all of them run exactly the shared-conditioning path."""
+        ValueError.  Videos that agree on all of them run exactly the shared-conditioning path.  ``noise_seed``: one int
+        (every video) or one per video, in [0, 2^63): the seeds of the stochastic samplers' noise; None = none."""
         if image_embeddings.dim() == 2:
             image_embeddings = image_embeddings.unsqueeze(1)
         batch = image_embeddings.shape[0]
@@ -346,7 +397,7 @@ class StableVideoUNet(nn.Module):
             image_embeddings=emb16, image_latents=lat16, added_time_ids=added, added_ids32=ids32,
             guidance_scale=guidance_scale if not isinstance(guidance_scale, (list, torch.Tensor)) else tuple(gs_v),
             guidance32=g32, guidance_ld=g_ld, guidance_scale_tensor=gs16, uncond_embeddings=uncond_e,
-            uncond_image_latents=uncond_l, num_frames=int(num_frames))
+            uncond_image_latents=uncond_l, num_frames=int(num_frames), noise_seeds=_noise_seeds(noise_seed, batch, dev))
 
     def set_conditioning(
         self,
@@ -357,10 +408,11 @@ class StableVideoUNet(nn.Module):
         noise_aug_strength: float = 0.02,
         guidance_scale: float | None = None,
         num_frames: int = 14,
+        noise_seed=None,
     ) -> None:
         self._cond = self.prepare_conditioning(image_embeddings, image_latents, fps=fps, motion_bucket_id=motion_bucket_id,
                                                noise_aug_strength=noise_aug_strength, guidance_scale=guidance_scale,
-                                               num_frames=num_frames)
+                                               num_frames=num_frames, noise_seed=noise_seed)
         self._graphs.clear()          # captured graphs hold pointers to the previous conditioning tensors
 
     def set_dummy_conditioning(
@@ -380,6 +432,11 @@ class StableVideoUNet(nn.Module):
         self.set_conditioning(emb, lat, fps=fps, motion_bucket_id=motion_bucket_id,
                               noise_aug_strength=noise_aug_strength, guidance_scale=guidance_scale,
                               num_frames=num_frames)
+
+    @property
+    def conditioning(self) -> VideoConditioning | None:
+        """The model's own conditioning (``set_conditioning``), e.g. to derive per-sample copies ``with_noise_seed``."""
+        return self._cond
 
     def clear_conditioning(self) -> None:
         self._cond = None
@@ -436,8 +493,9 @@ class StableVideoUNet(nn.Module):
     @torch.inference_mode()
     def forward(self, latent: torch.Tensor, step: int, conditioning: VideoConditioning | None = None) -> torch.Tensor:
         """One Euler step of ``latent`` (B,4,F,H,W), or with ``sampler="dpmpp_2m"`` one DPM-Solver++(2M) step of the
-        (B,8,F,H,W) state (``init_state``).  ``conditioning`` (``prepare_conditioning``): what this call is conditioned on;
-        None = the model's own (``set_conditioning``)."""
+        (B,8,F,H,W) state (``init_state``); ``"euler_a"`` / ``"dpmpp_2m_sde"`` step the same tensors and add the step's noise
+        from the conditioning's ``noise_seeds``.  ``conditioning`` (``prepare_conditioning``): what this call is conditioned
+        on; None = the model's own (``set_conditioning``)."""
         cond = self._cond if conditioning is None else conditioning
         if cond is None:
             raise RuntimeError(
@@ -461,10 +519,10 @@ class StableVideoUNet(nn.Module):
         cond = self._cond if cond is None else cond
         if self.state_channels == 8:
             if latent.dim() == 5 and latent.shape[1] == 4:
-                raise ValueError(f"sampler='dpmpp_2m' steps a (B, 8, F, H, W) state (sample ++ previous denoised estimate); "
+                raise ValueError(f"sampler={self.sampler!r} steps a (B, 8, F, H, W) state (sample ++ previous denoised estimate); "
                                  f"got the bare sample {tuple(latent.shape)}: wrap the noise in model.init_state()")
             if latent.dim() != 5 or latent.shape[1] != 8:
-                raise ValueError(f"latent must be (B, 8, F, H, W) with sampler='dpmpp_2m'; got {tuple(latent.shape)}")
+                raise ValueError(f"latent must be (B, 8, F, H, W) with sampler={self.sampler!r}; got {tuple(latent.shape)}")
         elif latent.dim() != 5 or latent.shape[1] != 4:
             raise ValueError(f"latent must be (B, 4, F, H, W); got {tuple(latent.shape)}")
         sample_shape = (latent.shape[0], 4) + tuple(latent.shape[2:])
@@ -494,6 +552,14 @@ class StableVideoUNet(nn.Module):
                              + (" per window" if self.window_stride is not None else ""))
         if g is not None and g.dim() == 2 and g.shape[0] != latent.shape[0]:
             raise ValueError(f"guidance rows for {g.shape[0]} videos, the latent has {latent.shape[0]}")
+        if self.stochastic:
+            seeds = cond.noise_seeds
+            if seeds is None:
+                raise ValueError(f"sampler={self.sampler!r} adds noise at every step and the conditioning carries no seeds: pass "
+                                 "noise_seed= to set_conditioning / prepare_conditioning, or use cond.with_noise_seed(seed)")
+            if seeds.dtype != torch.int64 or tuple(seeds.shape) != (latent.shape[0],):
+                raise ValueError(f"noise_seeds must be int64 [{latent.shape[0]}], one per video of the latent; got "
+                                 f"{seeds.dtype} {tuple(seeds.shape)}")
 
     def _lane_conditioning(self, lane, cond: VideoConditioning):
         """(This lane's static copy of a conditioning of ``cond``'s layout, refreshed from ``cond`` on the calling stream;
@@ -545,8 +611,10 @@ class StableVideoUNet(nn.Module):
         cond = self._cond if cond is None else cond
         if self.window_stride is not None:
             return self._forward_windows(latent, step, cond)
-        if self.sampler == "dpmpp_2m":
+        if self.state_channels == 8:
             return self._forward_dpmpp_2m(latent, step, cond)
+        if self.sampler == "euler_a":
+            return self._forward_euler_ancestral(latent, step, cond)
         b, _, f, h, w = latent.shape
         sigma, sigma_next = self._sigma_host[step], self._sigma_host[step + 1]
         out = torch.empty_like(latent)
@@ -564,13 +632,31 @@ class StableVideoUNet(nn.Module):
         coefficients (host constants, so a captured graph of the step holds them)."""
         b, _, f, h, w = state.shape
         sigma = self._sigma_host[step]
-        a, b_, c1, c2 = self._solver_coef[step]
         x = state[:, :4].contiguous()                     # (a view for one video; else a copy of the four sample planes)
         eps_c, eps_u = self._unet_passes(x, cond, step, 1.0 / math.sqrt(sigma * sigma + 1.0))
         out = torch.empty_like(state)
-        ops.dpmpp2m_step(state, eps_c, eps_u, cond.guidance32 if eps_u is not None else None, out, ld_eps=eps_c.shape[1],
+        guidance = cond.guidance32 if eps_u is not None else None
+        if self.sampler == "dpmpp_2m_sde":                # the same step plus n*z from (the videos' seeds, the step index)
+            a, b_, c1, c2, n = self._noise_coef[step]
+            return ops.dpmpp2m_sde_step(state, eps_c, eps_u, guidance, out, ld_eps=eps_c.shape[1], sigma=sigma, a=a, b=b_, c1=c1,
+                                        c2=c2, noise_scale=n, seeds=cond.noise_seeds, step=step, batch=b, frames_total=f, h=h,
+                                        w=w, ld_guidance=cond.guidance_ld)
+        a, b_, c1, c2 = self._solver_coef[step]
+        ops.dpmpp2m_step(state, eps_c, eps_u, guidance, out, ld_eps=eps_c.shape[1],
                          sigma=sigma, a=a, b=b_, c1=c1, c2=c2, batch=b, frames=f, h=h, w=w, ld_guidance=cond.guidance_ld)
         return out
+
+    def _forward_euler_ancestral(self, latent: torch.Tensor, step: int, cond: VideoConditioning) -> torch.Tensor:
+        """One Euler ancestral step of ``latent`` (B,4,F,H,W) through the stored-eps route, as 2M takes it: the noise is
+        evaluated in the tail kernel, which ``conv_out``'s fused Euler epilogue is not."""
+        b, _, f, h, w = latent.shape
+        sigma = self._sigma_host[step]
+        sigma_down, n = self._noise_coef[step]
+        eps_c, eps_u = self._unet_passes(latent, cond, step, 1.0 / math.sqrt(sigma * sigma + 1.0))
+        return ops.euler_ancestral_step(latent, eps_c, eps_u, cond.guidance32 if eps_u is not None else None,
+                                        torch.empty_like(latent), ld_eps=eps_c.shape[1], sigma=sigma, sigma_down=sigma_down,
+                                        noise_scale=n, seeds=cond.noise_seeds, step=step, b=b, frames_total=f, h=h, w=w,
+                                        ld_guidance=cond.guidance_ld)
 
     # ------------------------------------------------------------------ long videos: overlapping frame windows
     def _window_plan(self, frames_total: int, window: int):
@@ -610,6 +696,15 @@ class StableVideoUNet(nn.Module):
         common = dict(ld_eps=ld_eps, h=h, w=w, window=win, stride=pl.stride, n_win=pl.n_win, weights=weights,
                       frames_total=ft, ld_guidance=cond.guidance_ld)
         guidance = cond.guidance32 if cond.guided else None
+        if self.stochastic:                                    # the noise of global frame f, whichever windows cover it
+            noise = dict(seeds=cond.noise_seeds, step=step, **common)
+            if self.sampler == "dpmpp_2m_sde":
+                a, b_, c1, c2, n = self._noise_coef[step]
+                return ops.dpmpp2m_sde_step(state, eps_c, eps_u, guidance, out, sigma=sigma, a=a, b=b_, c1=c1, c2=c2,
+                                            noise_scale=n, batch=b, **noise)
+            sigma_down, n = self._noise_coef[step]
+            return ops.euler_ancestral_step(state, eps_c, eps_u, guidance, out, sigma=sigma, sigma_down=sigma_down,
+                                            noise_scale=n, b=b, **noise)
         if self.sampler == "dpmpp_2m":
             a, b_, c1, c2 = self._solver_coef[step]
             return ops.dpmpp2m_step_windows(state, eps_c, eps_u, guidance, out, sigma=sigma, a=a, b=b_, c1=c1, c2=c2,

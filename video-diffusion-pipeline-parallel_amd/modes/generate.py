@@ -65,9 +65,15 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--window-weights", type=str, default="triangle", choices=["triangle", "uniform"],
                    help="how the windows covering a frame are blended: weighted most at a window's centre, or equally")
     p.add_argument("--total-steps", type=int, default=25)
-    p.add_argument("--sampler", type=str, default="euler", choices=["euler", "dpmpp_2m"],
+    p.add_argument("--sampler", type=str, default="euler", choices=["euler", "dpmpp_2m", "euler_a", "dpmpp_2m_sde"],
                    help="euler: the reference's first-order update; dpmpp_2m: DPM-Solver++(2M), second order at one UNet "
-                        "evaluation per step (its history travels in the latent; the steps run in index order)")
+                        "evaluation per step (its history travels in the latent; the steps run in index order); euler_a, "
+                        "dpmpp_2m_sde: their stochastic forms, fresh noise at every step from the sample's seed")
+    p.add_argument("--eta", type=float, default=1.0, help="stochastic samplers: how much noise a step adds (0: none)")
+    p.add_argument("--s-noise", type=float, default=1.0, help="stochastic samplers: scale of the added noise")
+    p.add_argument("--noise", type=str, default="torch", choices=["torch", "device"],
+                   help="the initial latent: torch.randn under the sample's seed, or the counter-based device generator, "
+                        "whose values depend on the sample's seed and shape alone")
     p.add_argument("--fps", type=int, default=7)
     p.add_argument("--jpeg-quality", type=int, default=90, help="quality (1-100) of .avi / .jpg frames")
     p.add_argument("--motion-bucket-id", type=int, default=127)
@@ -88,6 +94,11 @@ def parse_args(argv=None) -> argparse.Namespace:
         p.error("give exactly one of --model-id <local dir> and --random-init")
     if args.tiny and not args.random_init:
         p.error("--tiny needs --random-init")
+    if args.eta < 0 or args.s_noise < 0:
+        p.error("--eta and --s-noise must not be negative")
+    if (args.noise == "device" or args.sampler in ("euler_a", "dpmpp_2m_sde")) \
+            and not (0 <= args.seed and args.seed + args.num_samples <= 2 ** 63):
+        p.error("--seed .. --seed + --num-samples - 1 must lie in [0, 2^63) for the device generator")
     if not 1 <= args.jpeg_quality <= 100:
         p.error("--jpeg-quality must be from 1 to 100")
     if args.height % 8 or args.width % 8:
@@ -145,7 +156,8 @@ def _build_engines(args, timesteps, device):
         spec = CLIPVisionSpec.tiny(ucfg.cross_attention_dim) if args.tiny else CLIPVisionSpec.svd()
         vcfg = VAEDecoderConfig.tiny(64) if args.tiny else VAEDecoderConfig.svd()
         model = StableVideoUNet.from_random_init(timesteps, config=ucfg, seed=args.seed, device=device, sampler=args.sampler,
-                                                 window_stride=args.window_stride, window_weights=args.window_weights)
+                                                 window_stride=args.window_stride, window_weights=args.window_weights,
+                                                 eta=args.eta, s_noise=args.s_noise)
         clip = CLIPVisionHIP(spec, clip_random_state_dict(spec, seed=args.seed + 1, device=device), device)
         enc = ImageEncoderHIP(vcfg, random_encoder_state_dict(vcfg, seed=args.seed + 2, device=device), device)
         return model, clip, enc, lambda: TemporalDecoderHIP(vcfg, random_state_dict(vcfg, seed=args.seed + 3, device=device),
@@ -153,7 +165,8 @@ def _build_engines(args, timesteps, device):
     from ..models.edge_stages import load_edge_engines
 
     model = StableVideoUNet.from_pretrained(args.model_id, timesteps=timesteps, device=device, sampler=args.sampler,
-                                            window_stride=args.window_stride, window_weights=args.window_weights)
+                                            window_stride=args.window_stride, window_weights=args.window_weights,
+                                            eta=args.eta, s_noise=args.s_noise)
     clip, enc, dec = load_edge_engines(args.model_id, device)
     return model, clip, enc, lambda: dec
 
@@ -161,8 +174,8 @@ def _build_engines(args, timesteps, device):
 def _step_order(sampler: str, total_steps: int) -> list:
     """The ``step`` values the pipeline hands to the model, in order.  Euler keeps the reference modes' descending list
     (``production.py:88``: the value is passed verbatim); a multistep solver needs the previous
-    step's estimate and walks the sigma table in index order."""
-    return list(range(total_steps)) if sampler == "dpmpp_2m" else list(range(total_steps - 1, -1, -1))
+    step's estimate and walks the sigma table in index order, and so do the stochastic samplers."""
+    return list(range(total_steps)) if sampler != "euler" else list(range(total_steps - 1, -1, -1))
 
 
 def main(argv=None) -> None:
@@ -212,13 +225,25 @@ def main(argv=None) -> None:
             spec = LatentSpec(shape=carried, dtype=torch.float16, device=device)
 
             def supplier(i: int) -> torch.Tensor:
+                if args.noise == "device":
+                    return model.init_state(model.initial_noise(args.seed + i, *shape[2:]))
                 torch.manual_seed(args.seed + i)
                 return model.init_state(torch.randn(shape, device=device, dtype=torch.float16) * model.init_noise_sigma)
+
+            # a stochastic sampler draws sample i's step noise from seed + i: the model's one conditioning with that seed,
+            # handed to every step of the sample on whichever rank runs it
+            conditioning, seeded = None, {}
+            if model.stochastic:
+                def conditioning(i: int):
+                    if i not in seeded:
+                        seeded[i] = model.conditioning.with_noise_seed(args.seed + i)
+                    return seeded[i]
 
             outs = run_pipeline_latents(model, total_steps=args.total_steps,
                                         timesteps=_step_order(args.sampler, args.total_steps), world_size=world,
                                         rank=rank, latent_spec=spec, num_samples=args.num_samples,
-                                        input_supplier=supplier if rank == 0 else None, balanced=args.balanced)
+                                        input_supplier=supplier if rank == 0 else None, balanced=args.balanced,
+                                        conditioning_supplier=conditioning)
             if outs:
                 decoder = make_decoder()
                 for i, latents in enumerate(outs):

@@ -22,9 +22,15 @@ LOGGER = logging.getLogger(__name__)
 def parse_args(argv=None) -> argparse.Namespace:
     p = argparse.ArgumentParser(description="Pipeline production mode (SVD)")
     p.add_argument("--total-steps", type=int, default=28)
-    p.add_argument("--sampler", type=str, default="euler", choices=["euler", "dpmpp_2m"],
+    p.add_argument("--sampler", type=str, default="euler", choices=["euler", "dpmpp_2m", "euler_a", "dpmpp_2m_sde"],
                    help="euler: the reference's first-order update; dpmpp_2m: DPM-Solver++(2M), second order at one UNet "
-                        "evaluation per step (its history travels in the latent; the steps run in index order)")
+                        "evaluation per step (its history travels in the latent; the steps run in index order); euler_a, "
+                        "dpmpp_2m_sde: their stochastic forms, fresh noise at every step from the sample's seed (seed + i)")
+    p.add_argument("--eta", type=float, default=1.0, help="stochastic samplers: how much noise a step adds (0: none)")
+    p.add_argument("--s-noise", type=float, default=1.0, help="stochastic samplers: scale of the added noise")
+    p.add_argument("--noise", type=str, default="torch", choices=["torch", "device"],
+                   help="the initial latent: torch.randn under the sample's seed, or the counter-based device generator, "
+                        "whose values depend on the sample's seed and shape alone")
     p.add_argument("--num-samples", type=int, default=1)
     p.add_argument("--latent-frames", type=int, default=14)
     p.add_argument("--latent-height", type=int, default=72)
@@ -60,8 +66,10 @@ def main(argv=None) -> None:
     init_distributed(backend=backend, rank=rank, world_size=world, init_method=args.init_method)
 
     timesteps = StableVideoUNet._default_timestep_schedule(args.total_steps)
-    model = (StableVideoUNet.from_random_init(timesteps, device=device, sampler=args.sampler) if args.random_init
-             else StableVideoUNet.from_pretrained(args.model_id, timesteps=timesteps, device=device, sampler=args.sampler))
+    noise = dict(eta=args.eta, s_noise=args.s_noise)
+    model = (StableVideoUNet.from_random_init(timesteps, device=device, sampler=args.sampler, **noise) if args.random_init
+             else StableVideoUNet.from_pretrained(args.model_id, timesteps=timesteps, device=device, sampler=args.sampler,
+                                                  **noise))
     torch.manual_seed(args.seed)
     model.set_dummy_conditioning(1, args.latent_frames, args.latent_height, args.latent_width, device,
                                  fps=args.fps, motion_bucket_id=args.motion_bucket_id,
@@ -70,9 +78,12 @@ def main(argv=None) -> None:
     # what a stage boundary carries: the sample, and with dpmpp_2m the solver's history behind it (8 channels)
     spec = LatentSpec(shape=torch.Size((1, model.state_channels) + tuple(shape[2:])), dtype=torch.float16, device=device)
     # Euler keeps the reference's descending list (ref production.py:88); a multistep solver walks the table in index order
-    order = list(range(args.total_steps)) if args.sampler == "dpmpp_2m" else list(range(args.total_steps - 1, -1, -1))
+    # (and so do the stochastic samplers)
+    order = list(range(args.total_steps)) if args.sampler != "euler" else list(range(args.total_steps - 1, -1, -1))
 
     def supplier(i: int) -> torch.Tensor:
+        if args.noise == "device":
+            return model.init_state(model.initial_noise(args.seed + i, *shape[2:]))
         torch.manual_seed(args.seed + i)
         return model.init_state(torch.randn(shape, device=device, dtype=torch.float16) * model.init_noise_sigma)
 
@@ -87,7 +98,16 @@ def main(argv=None) -> None:
             img = torch.randn(shape, generator=g, device=device, dtype=torch.float16)
             return model.prepare_conditioning(emb, img, fps=args.fps, motion_bucket_id=buckets[i % len(buckets)],
                                               noise_aug_strength=args.noise_aug_strength,
-                                              guidance_scale=args.guidance_scale, num_frames=args.latent_frames)
+                                              guidance_scale=args.guidance_scale, num_frames=args.latent_frames,
+                                              noise_seed=args.seed + i if model.stochastic else None)
+    elif model.stochastic:
+        seeded: dict = {}
+
+        def conditioning_supplier(i: int):
+            # sample i's step noise comes from seed + i: the model's one conditioning with that seed, on every rank
+            if i not in seeded:
+                seeded[i] = model.conditioning.with_noise_seed(args.seed + i)
+            return seeded[i]
 
     try:
         with torch.no_grad():
