@@ -823,6 +823,37 @@ int sp_webp_code(const void *residual, const void *modes, const void *flags, int
                  void *out, size_t cap, void *out_len, void *ws, size_t ws_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Frames between the frames: one round doubles the frame rate of uint8 frames that are in device memory (n frames become
+ * 2n - 1: out[2i] = frames[i], out[2i + 1] the motion-compensated midpoint of the pair (i, i + 1)).  The reference leaves
+ * this to a separate tool behind its mp4.  Classical and all-integer: a bilateral block motion search, a vector median, an
+ * overlapped blend; tests/interp_model.py states it in numpy and the kernels equal it bit for bit.  n is 2..32768; h and w
+ * are multiples of 8 from 16 to 16384; range is 1..24; lam is 0..255.
+ *   luma     Y = (77 R + 150 G + 29 B + 128) >> 8
+ *   search   per pair (A, B) and 8x8 block (by, bx) of the midpoint's grid, over all v = (vy, vx) in [-range, range]^2:
+ *              cost(v) = sum_q |YA[clamp(q - v)] - YB[clamp(q + v)]| + lam * (|vy| + |vx|)
+ *            q over the 16x16 window with origin (8 by - 4, 8 bx - 4), unclamped; clamp acts once, on the displaced
+ *            coordinate, per axis, to the image.  key(v) = cost * 4096 + ((vy + range) * (2 range + 1) + (vx + range)); the
+ *            block's raw vector is the v of least key (cost < 2^17 and the index < 2^12: a key fits 32 bits and the least
+ *            is unique whatever the order of reduction).
+ *   median   the component-wise 5th smallest over the 3x3 neighbourhood of raw vectors, block coordinates clamped to the grid
+ *   blend    pixel (y, x): ty = y + 4, by0 = (ty >> 3) - 1, wy1 = 2 (ty & 7) + 1, wy0 = 16 - wy1, likewise x; over the four
+ *            blocks (by0 + {0, 1}, bx0 + {0, 1}) clamped to the grid, with weights wy * wx (they sum to 256):
+ *              out_c = (sum_k w_k * (A_c[clamp(p - v_k)] + B_c[clamp(p + v_k)]) + 256) >> 9
+ * ------------------------------------------------------------------------------------------- */
+/* Scratch of sp_interp_motion_u8: n luma planes of (h + 2 range + 8) rows of w + 2 range + 8 bytes rounded up to 4 (replicate
+ * padding by range + 4, so that the search reads without clamping), the sum rounded up to 16, and the raw vectors,
+ * 4 (n - 1) (h / 8) (w / 8) bytes.  Needs no GPU; 0 for arguments the calls refuse. */
+size_t sp_interp_ws_bytes(int n, int h, int w, int range);
+/* frames: uint8 [n][h][w][3] RGB -> vectors, and raw_vectors unless it is NULL: int16 [n - 1][h / 8][w / 8][2] in (vy, vx)
+ * order, after and before the median.  Three launches: the luma of all n frames, the search of all n - 1 pairs, the median.
+ * ws: sp_interp_ws_bytes, 4-byte aligned. */
+int sp_interp_motion_u8(const void *frames, int n, int h, int w, int range, int lam, void *vectors, void *raw_vectors, void *ws,
+                        size_t ws_bytes, void *stream);
+/* frames and vectors as above -> out: uint8 [2n - 1][h][w][3], the copies of the frames and the midpoints between them.  A
+ * vector may be any int16: reads are clamped to the image.  out may not overlap frames. */
+int sp_interp_compensate_u8(const void *frames, int n, int h, int w, const void *vectors, void *out, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement aid (bench.py `roofline.clock_ghz_live`; the reference has no counterpart -- its benchmark reads no clocks,
  * /root/reference/src/modes/benchmark.py:170-262).  One time stamp in stream order: `blocks` one-wave workgroups each write
  * four u64 words to out[block][4]: the id of the place the workgroup ran on (bits 3:0 the XCD, HW_REG_XCC_ID; bits 11:4 the

@@ -137,6 +137,9 @@ SIGNATURES = {
     "sp_webp_stream_bytes": (_Z, [_I, _I, _I, _I]),
     "sp_webp_transform_u8": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
     "sp_webp_code": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _Z, _P, _P, _Z, _P]),
+    "sp_interp_ws_bytes": (_Z, [_I, _I, _I, _I]),
+    "sp_interp_motion_u8": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    "sp_interp_compensate_u8": (_I, [_P, _I, _I, _I, _P, _P, _P]),
     "sp_clock_stamp": (_I, [_P, _I, _P]),
     "sp_dummy_unet_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _I, _I, _I, _I, _I, _I, _P]),
 }

@@ -864,6 +864,49 @@ def webp_code(residual, modes, flags, out, out_len, ws, *, pred_bits, group_bits
     return out, out_len
 
 
+def interp_ws_bytes(n: int, h: int, w: int, search_range: int) -> int:
+    return int(load().sp_interp_ws_bytes(n, h, w, search_range))
+
+
+def _interp_frames(frames_u8, name: str):
+    _dev_buf(frames_u8, torch.uint8, f"{name}: frames")
+    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
+        raise ValueError(f"{name}: frames must be (n, h, w, 3); got {tuple(frames_u8.shape)}")
+    return frames_u8.shape[:3]
+
+
+def interp_motion(frames_u8, vectors, ws, *, search_range, penalty, raw_vectors=None):
+    """uint8 (n, h, w, 3) RGB -> ``vectors`` int16 (n - 1, h / 8, w / 8, 2), (vy, vx) per 8x8 block of each pair's midpoint:
+    the exhaustive bilateral search over [-search_range, search_range]^2 on luma with ``penalty`` per unit of |vy| + |vx|,
+    then the 3x3 median (``sp_interp_motion_u8``); ``raw_vectors``, if given, takes the vectors before the median; ``ws``:
+    uint8 scratch of ``interp_ws_bytes``."""
+    n, h, w = _interp_frames(frames_u8, "interp_motion")
+    shape = (n - 1, h // 8, w // 8, 2)
+    for t, what in ((vectors, "vectors"), (raw_vectors, "raw_vectors")):
+        if t is None:
+            continue
+        _dev_buf(t, torch.int16, f"interp_motion: {what}")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"interp_motion: {what} must be {shape}; got {tuple(t.shape)}")
+    _dev_buf(ws, torch.uint8, "interp_motion: ws")
+    _check(load().sp_interp_motion_u8(frames_u8.data_ptr(), n, h, w, int(search_range), int(penalty), vectors.data_ptr(),
+                                      _ptr(raw_vectors), ws.data_ptr(), ws.numel(), _stream()), "sp_interp_motion_u8")
+    return vectors
+
+
+def interp_compensate(frames_u8, vectors, out):
+    """uint8 (n, h, w, 3) and int16 ``vectors`` (n - 1, h / 8, w / 8, 2) -> ``out`` uint8 (2n - 1, h, w, 3): ``out[2i]`` is frame
+    i, ``out[2i + 1]`` the overlapped, motion-compensated blend of frames i and i + 1 (``sp_interp_compensate_u8``)."""
+    n, h, w = _interp_frames(frames_u8, "interp_compensate")
+    _dev_buf(vectors, torch.int16, "interp_compensate: vectors"), _dev_buf(out, torch.uint8, "interp_compensate: out")
+    if tuple(vectors.shape) != (n - 1, h // 8, w // 8, 2) or tuple(out.shape) != (2 * n - 1, h, w, 3):
+        raise ValueError(f"interp_compensate: vectors must be {(n - 1, h // 8, w // 8, 2)} and out {(2 * n - 1, h, w, 3)}; got "
+                         f"{tuple(vectors.shape)} and {tuple(out.shape)}")
+    _check(load().sp_interp_compensate_u8(frames_u8.data_ptr(), n, h, w, vectors.data_ptr(), out.data_ptr(), _stream()),
+           "sp_interp_compensate_u8")
+    return out
+
+
 class ClockStamps:
     """Stamps of the shader-clock counter against the constant 100 MHz counter, taken in stream order between other work
     (``sp_clock_stamp``; bench.py ``roofline.clock_ghz_live``).  ``stamp()`` enqueues one on the current stream (a 3 us

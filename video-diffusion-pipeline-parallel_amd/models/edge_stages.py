@@ -155,11 +155,17 @@ class FrameEmitter:
     ``latent_view`` (a callable, default None): applied to a finished latent before it is decoded, for pipelines whose
     carried tensor holds more than the sample -- ``StableVideoUNet(sampler="dpmpp_2m").sample_of`` takes the four sample
     channels out of the 8-channel solver state.
+
+    ``interpolate`` 2 or 4 (default 1: nothing changes) puts motion-compensated frames between each video's frames on the
+    decode stream (``image_io.FrameInterpolator`` with ``interp_range`` and ``interp_penalty``) before any of the 8-bit
+    outputs: ``"uint8"`` keeps (B, (F-1)*interpolate+1, 8H, 8W, 3), the encoders see that many frames, and ``"gif"`` /
+    ``"webp"`` play them at ``gif_fps * interpolate``.  ``output="float32"`` has no 8-bit frames and refuses it.
     """
 
     def __init__(self, decoder: TemporalDecoderHIP, stage, num_frames: int, *, decode_chunk_size: int = 14,
                  spread: bool = True, keep: str = "all", check_finite: bool = False, output: str = "float32",
-                 jpeg_quality: int = 90, gif_fps=7, latent_view=None) -> None:
+                 jpeg_quality: int = 90, gif_fps=7, latent_view=None, interpolate: int = 1, interp_range: int = 16,
+                 interp_penalty: int = 4) -> None:
         from ..pipeline.step_assignment import ring_finish_rank
 
         if latent_view is not None and not callable(latent_view):
@@ -176,7 +182,17 @@ class FrameEmitter:
             raise ValueError(f"jpeg_quality must be an integer from 1 to 100; got {jpeg_quality!r}")
         if output in ("gif", "webp") and (isinstance(gif_fps, bool) or not isinstance(gif_fps, (int, float)) or not gif_fps > 0):
             raise ValueError(f"gif_fps must be a positive number; got {gif_fps!r}")
+        if isinstance(interpolate, bool) or interpolate not in (1, 2, 4):
+            raise ValueError(f"interpolate must be 1, 2 or 4; got {interpolate!r}")
+        if interpolate > 1 and output == "float32":
+            raise ValueError("interpolate works on 8-bit frames: it needs output='uint8', 'jpeg', 'gif', 'png' or 'webp'")
+        if interpolate > 1:
+            from .image_io import _check_interp_search
+            interp_range, interp_penalty = _check_interp_search(interp_range, interp_penalty)
+        self.interpolate, self.interp_range, self.interp_penalty = interpolate, interp_range, interp_penalty
+        self._interp = None             # the FrameInterpolator, made for the first sample's frame size
         self.output, self.jpeg_quality, self.gif_fps = output, jpeg_quality, gif_fps
+        self._play_fps = gif_fps * interpolate if interpolate > 1 else gif_fps      # what the animated outputs are written at
         self._jpeg = None               # the JpegEncoder (or, for output="png", the PngEncoder), made for the first sample's frame size
         self._gif = None                # the GifEncoders (or, for output="webp", the WebpEncoders), one per video of a sample (a video's buffers wait for the fetch)
         self._pending = None            # (sample index, videos, streams or files, lengths, event) of the encode still on the device
@@ -218,6 +234,18 @@ class FrameEmitter:
                 self._collect_jpeg()           # before this decode is queued: the encoder's buffers are free again after it
             decode = self.decoder.decode_latents if self.output == "float32" else self.decoder.decode_latents_uint8
             out = decode(latent.contiguous(), self.num_frames, decode_chunk_size=self.chunk)
+            if self.interpolate > 1:
+                if self._interp is None or (self._interp.height, self._interp.width) != tuple(out.shape[2:4]):
+                    from .image_io import FrameInterpolator
+                    self._interp = FrameInterpolator(self.device, out.shape[2], out.shape[3], self.interpolate,
+                                                     self.interp_range, self.interp_penalty)
+                # the interpolator's buffers are reused from video to video, so each result is copied out, in stream
+                # order, before the next video's kernels are queued
+                videos = out
+                out = torch.empty((videos.shape[0], (videos.shape[1] - 1) * self.interpolate + 1, *videos.shape[2:]),
+                                  dtype=torch.uint8, device=self.device)
+                for kept, video in zip(out, videos):
+                    kept.copy_(self._interp(video))
             if self.output in ("jpeg", "png"):
                 if self._jpeg is None or (self._jpeg.height, self._jpeg.width) != tuple(out.shape[2:4]):
                     from .image_io import JpegEncoder, PngEncoder
@@ -232,7 +260,7 @@ class FrameEmitter:
             elif self.output in ("gif", "webp"):
                 if self._gif is None or len(self._gif) != out.shape[0] or (self._gif[0].height, self._gif[0].width) != tuple(out.shape[2:4]):
                     from .image_io import GifEncoder, WebpEncoder
-                    self._gif = [GifEncoder(self.device, out.shape[2], out.shape[3], fps=self.gif_fps) if self.output == "gif"
+                    self._gif = [GifEncoder(self.device, out.shape[2], out.shape[3], fps=self._play_fps) if self.output == "gif"
                                  else WebpEncoder(self.device, out.shape[2], out.shape[3]) for _ in range(out.shape[0])]
                 bufs = [enc.enqueue(video) for enc, video in zip(self._gif, out)]
                 done = torch.cuda.Event()
@@ -265,7 +293,7 @@ class FrameEmitter:
                     return
                 if self.output == "webp":
                     from .image_io import write_webp
-                    self._keep(idx, [write_webp(None, enc.collect_streams(*bufs), enc.width, enc.height, self.gif_fps)
+                    self._keep(idx, [write_webp(None, enc.collect_streams(*bufs), enc.width, enc.height, self._play_fps)
                                      for enc, bufs in zip(self._gif, streams)])
                     return
                 files = (self._jpeg.collect_files if self._device_files() else self._jpeg.collect)(streams, lens)

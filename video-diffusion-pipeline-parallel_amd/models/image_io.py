@@ -18,6 +18,8 @@
   * ``WebpEncoder`` / ``webp_file`` / ``write_webp``: lossless WebP stills and one animated WebP, full colour and playable
     in a browser: frames on the device become VP8L bitstreams there by the kernels of ``csrc/webp.hip``; the RIFF container
     has no checksum, so the host only wraps bytes.
+  * ``FrameInterpolator``: frames between the frames (2x or 4x the frame rate) before any of the writers above: block motion
+    search on luma, a vector median and an overlapped blend by the kernels of ``csrc/interp.hip``, integer arithmetic only.
   * ``load_image``: the decode half of ``load_and_preprocess_image`` (Pillow; a file format is host work).
   * ``parse_jpeg`` / ``JpegDecoder`` / ``load_image_device``: the same decode for the common baseline JPEG on the device: the
     host walks the markers, the compressed bytes are uploaded, and the kernels of ``csrc/jpeg_decode.hip`` go from the
@@ -927,6 +929,62 @@ class WebpEncoder(_FrameEncoder):
         return write_webp(None, self._finished(self.enqueue, self.collect_streams, frames_u8), self.width, self.height, fps)
 
 
+INTERP_FACTORS = (1, 2, 4)
+
+
+def _check_interpolate(factor) -> int:
+    if isinstance(factor, bool) or not isinstance(factor, (int, np.integer)) or factor not in INTERP_FACTORS:
+        raise ValueError(f"interpolate must be 1, 2 or 4; got {factor!r}")
+    return int(factor)
+
+
+def _check_interp_search(search_range, penalty) -> tuple[int, int]:
+    """``(search_range, penalty)`` as ints, or ``ValueError``: the one check of ``FrameInterpolator`` and its callers."""
+    if isinstance(search_range, bool) or not isinstance(search_range, (int, np.integer)) or not 1 <= search_range <= 24:
+        raise ValueError(f"search_range must be an integer from 1 to 24; got {search_range!r}")
+    if isinstance(penalty, bool) or not isinstance(penalty, (int, np.integer)) or not 0 <= penalty <= 255:
+        raise ValueError(f"penalty must be an integer from 0 to 255; got {penalty!r}")
+    return int(search_range), int(penalty)
+
+
+class FrameInterpolator(_FrameEncoder):
+    """(F, H, W, 3) uint8 frames on the device -> ((F - 1) * factor + 1, H, W, 3) uint8 on the device: every round puts the
+    motion-compensated midpoint between neighbours (``out[2i]`` is frame i), ``factor`` 4 is two rounds, ``factor`` 1 hands the
+    input back as it is.  Per pair and 8x8 block an exhaustive bilateral search over ``[-search_range, search_range]^2`` on
+    luma (``penalty`` per unit of |vy| + |vx| against wandering vectors in flat areas), a 3x3 median of the vectors and an
+    overlapped blend of the two displaced frames (``ops.interp_motion`` / ``ops.interp_compensate``); H and W are multiples
+    of 8, at least 16.  Scratch, vectors and frames are kept per frame count; the result is a view of this object's buffers,
+    valid until the next call with as many frames.  ``vectors`` is the last round's (pairs, H / 8, W / 8, 2) int16 in (vy, vx)
+    order.  This is classical interpolation: no learned model's quality, and where something is uncovered or hidden between
+    two frames the blend of the two is all there is."""
+
+    def __init__(self, device, height: int, width: int, factor: int = 2, search_range: int = 16, penalty: int = 4) -> None:
+        super().__init__(device, height, width)
+        self.factor = _check_interpolate(factor)
+        if self.height % 8 or self.width % 8 or self.height < 16 or self.width < 16:
+            raise ValueError(f"frame interpolation needs a height and width that are multiples of 8 and at least 16; got "
+                             f"{self.height} x {self.width}")
+        self.search_range, self.penalty = _check_interp_search(search_range, penalty)
+        self.vectors = None
+
+    def enqueue(self, frames_u8: torch.Tensor) -> torch.Tensor:
+        """Run the rounds on the current stream and return the frames (for ``factor`` 1, or one frame, the input itself)."""
+        n = self._check_frames(frames_u8)
+        if self.factor == 1 or n == 1:
+            return frames_u8
+        frames = frames_u8.to(self.device).contiguous()
+        h, w = self.height, self.width
+        for rnd in range(self.factor.bit_length() - 1):
+            ws = self._buf(f"ws{rnd}", (ops.interp_ws_bytes(n, h, w, self.search_range),), torch.uint8)
+            self.vectors = self._buf(f"vectors{rnd}", (n - 1, h // 8, w // 8, 2), torch.int16)
+            out = self._buf(f"out{rnd}", (2 * n - 1, h, w, 3), torch.uint8)
+            ops.interp_motion(frames, self.vectors, ws, search_range=self.search_range, penalty=self.penalty)
+            frames, n = ops.interp_compensate(frames, self.vectors, out), 2 * n - 1
+        return frames
+
+    __call__ = enqueue
+
+
 def _jpeg_frames(frames_u8, quality: int) -> tuple[list[bytes], int, int]:
     """``(files, height, width)``: a tensor on a GPU is compressed there (``JpegEncoder``), anything else by Pillow."""
     if isinstance(frames_u8, torch.Tensor) and frames_u8.is_cuda:
@@ -945,7 +1003,40 @@ def _frames_array(frames_u8) -> np.ndarray:
     return a
 
 
-def save_frames(frames_u8, path: str, fps: int = 7, quality: int = 90) -> list[str]:
+_FFMPEG_EXTS = (".mp4", ".mov", ".mkv", ".webm")
+
+
+def _needs_ffmpeg(path: str) -> ValueError:
+    return ValueError(f"cannot write '{path}': video encoding needs imageio / ffmpeg, which this package does not depend "
+                      f"on; write .avi (Motion-JPEG) instead, or .gif, .webp (lossless, animated), .npy, JPEG or PNG frames (a "
+                      f"%03d.jpg / %03d.png pattern or a directory)")
+
+
+def _unknown_format(path: str, ext: str) -> ValueError:
+    return ValueError(f"'{path}': unknown output format {ext!r} (.avi, .gif, .apng, .webp, .npy, %03d.jpg / %03d.png / "
+                      f"%03d.webp pattern or a directory)")
+
+
+def _check_target(path: str, ext: str, fps, quality) -> None:
+    """What ``save_frames`` refuses about a target and its ``fps`` / ``quality``, with no look at the frames: asked before
+    work is spent on frames that could not be written."""
+    if ext in _FFMPEG_EXTS:
+        raise _needs_ffmpeg(path)
+    if ext not in (".avi", ".jpg", ".jpeg", ".gif", ".apng", ".webp", ".npy", ".png", ""):
+        raise _unknown_format(path, ext)
+    if ext in (".avi", ".jpg", ".jpeg"):
+        _check_quality(quality)
+    if ext == ".avi" and (isinstance(fps, bool) or not isinstance(fps, (int, np.integer)) or fps <= 0):
+        raise ValueError("fps must be a positive integer")
+    if ext in (".gif", ".apng") or (ext == ".webp" and "%" not in path):
+        _check_fps(fps)
+    if ext in (".jpg", ".jpeg", ".png") and "%" not in path:
+        raise ValueError(f"'{path}': {'PNG' if ext == '.png' else 'JPEG'} output needs a frame pattern such as "
+                         f"frame_%03d{ext}")
+
+
+def save_frames(frames_u8, path: str, fps: int = 7, quality: int = 90, interpolate: int = 1, interp_range: int = 16,
+                interp_penalty: int = 4) -> list[str]:
     """Write one video's (F, H, W, 3) uint8 frames and return the files written.  ``*.avi``: Motion-JPEG at ``fps`` frames
     per second, the video file of the reference's ``save_video`` (ref :198-209) in a container that needs no ffmpeg;
     ``*.gif``: an animated GIF that loops for ever, ``1000 / fps`` ms per frame (ref ``save_gif`` :212-222); ``*.npy``:
@@ -958,9 +1049,26 @@ def save_frames(frames_u8, path: str, fps: int = 7, quality: int = 90) -> list[s
     (``PngEncoder``); an array in host memory goes through Pillow.  ``*.webp`` is lossless WebP: one animated file
     (``round(1000 / fps)`` ms per frame, looping for ever), or with a ``%03d``-style pattern one still per frame; a tensor on
     a GPU is transformed and entropy-coded there (``WebpEncoder``), an array in host memory, or frames the kernels refuse, go
-    through Pillow (``lossless=True``).  ``*.mp4`` is refused: imageio / ffmpeg are not dependencies."""
+    through Pillow (``lossless=True``).  ``*.mp4`` is refused: imageio / ffmpeg are not dependencies.
+
+    ``interpolate`` 2 or 4 puts motion-compensated frames between the frames first (``FrameInterpolator`` with
+    ``interp_range`` and ``interp_penalty``) and writes at ``fps * interpolate``, so the video lasts as long as before
+    (to within one frame time).  That runs on the device only: the frames must be a tensor on a GPU, of a height and width
+    that are multiples of 8."""
     path = os.fspath(path)
     ext = os.path.splitext(path)[1].lower()
+    if _check_interpolate(interpolate) > 1:
+        if not (isinstance(frames_u8, torch.Tensor) and frames_u8.is_cuda):
+            raise ValueError(f"interpolate={interpolate} runs on the device (image_io.FrameInterpolator): pass the frames as a "
+                             f"uint8 tensor on a GPU, or interpolate=1 for frames in host memory")
+        if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or 0 in frames_u8.shape:
+            raise ValueError(f"frames must be (F, H, W, 3) uint8; got {frames_u8.dtype} {tuple(frames_u8.shape)}")
+        # (a frame size that is not a multiple of 8 is refused here, by the interpolator); no kernel runs before the
+        # target and its arguments are accepted
+        interpolator = FrameInterpolator(frames_u8.device, frames_u8.shape[1], frames_u8.shape[2], interpolate, interp_range,
+                                         interp_penalty)
+        _check_target(path, ext, fps, quality)
+        frames_u8, fps = interpolator(frames_u8), fps * interpolate
     # frames on a GPU stay there for the targets that are compressed there; everything else is host work on an array
     on_gpu = isinstance(frames_u8, torch.Tensor) and frames_u8.is_cuda and ext in (".avi", ".jpg", ".jpeg", ".gif", ".apng", "")
     if on_gpu and ext == ".gif" and frames_u8.dim() == 4 and frames_u8.shape[1] * frames_u8.shape[2] > 2 ** 24:
@@ -976,10 +1084,8 @@ def save_frames(frames_u8, path: str, fps: int = 7, quality: int = 90) -> list[s
         on_gpu = (frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4 and frames_u8.shape[3] == 3 and frames_u8.shape[0] > 0
                   and ops.webp_stream_bytes(frames_u8.shape[1], frames_u8.shape[2], WEBP_PRED_BITS, WEBP_GROUP_BITS) > 0)
     a = None if on_gpu else _frames_array(frames_u8)
-    if ext in (".mp4", ".mov", ".mkv", ".webm"):
-        raise ValueError(f"cannot write '{path}': video encoding needs imageio / ffmpeg, which this package does not depend "
-                         f"on; write .avi (Motion-JPEG) instead, or .gif, .webp (lossless, animated), .npy, JPEG or PNG frames (a "
-                         f"%03d.jpg / %03d.png pattern or a directory)")
+    if ext in _FFMPEG_EXTS:
+        raise _needs_ffmpeg(path)
     if ext in (".avi", ".jpg", ".jpeg"):
         _check_quality(quality)
         if ext == ".avi" and (not isinstance(fps, (int, np.integer)) or fps <= 0):
@@ -1043,6 +1149,5 @@ def save_frames(frames_u8, path: str, fps: int = 7, quality: int = 90) -> list[s
         os.makedirs(path, exist_ok=True)
         pattern = os.path.join(path, "%03d.png")
     else:
-        raise ValueError(f"'{path}': unknown output format {ext!r} (.avi, .gif, .apng, .webp, .npy, %03d.jpg / %03d.png / "
-                         f"%03d.webp pattern or a directory)")
+        raise _unknown_format(path, ext)
     return _write_numbered(pattern, len(a), (_pillow_bytes(f, "PNG") for f in a))

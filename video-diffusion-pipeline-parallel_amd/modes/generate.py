@@ -25,7 +25,9 @@ palette per frame and LZW-coded on the GPU as well (``image_io.GifEncoder``), at
 or a directory of PNGs, and ``.apng``, one lossless animated PNG at ``--fps``: PNG rows are filtered and deflated on the GPU
 too (``image_io.PngEncoder``) -- and ``.webp``, lossless WebP in full colour that a browser plays: one animated file at
 ``--fps``, or with a ``%03d.webp`` pattern one still per frame, transformed and entropy-coded on the GPU
-(``image_io.WebpEncoder``)).  The frames go to ``save_frames`` as the device tensor they are.
+(``image_io.WebpEncoder``)).  The frames go to ``save_frames`` as the device tensor they are.  ``--interpolate 2`` / ``4`` puts
+motion-compensated frames between the generated ones first, on the GPU (``image_io.FrameInterpolator``; ``--interp-range``,
+``--interp-penalty``), and writes at ``--fps`` times that factor, so the video lasts as long.
 
 ``--input-decode device`` decodes a baseline JPEG picture on the GPU from its compressed bytes (``image_io.load_image_device``:
 only plan and entropy-coded segment are uploaded; files outside the device decoder's scope still go through Pillow); the
@@ -76,6 +78,11 @@ def parse_args(argv=None) -> argparse.Namespace:
                         "whose values depend on the sample's seed and shape alone")
     p.add_argument("--fps", type=int, default=7)
     p.add_argument("--jpeg-quality", type=int, default=90, help="quality (1-100) of .avi / .jpg frames")
+    p.add_argument("--interpolate", type=int, default=1, choices=[1, 2, 4],
+                   help="frame-rate factor: put 1 or 3 motion-compensated frames between the generated ones on the GPU and "
+                        "write at --fps times this, so the video lasts as long (1: off)")
+    p.add_argument("--interp-range", type=int, default=16, help="--interpolate: motion search range in pixels (1-24)")
+    p.add_argument("--interp-penalty", type=int, default=4, help="--interpolate: cost per pixel of vector length (0-255)")
     p.add_argument("--motion-bucket-id", type=int, default=127)
     p.add_argument("--noise-aug-strength", type=float, default=0.02)
     p.add_argument("--guidance-scale", type=float, default=3.0, help="CFG guidance scale (1.0 disables CFG)")
@@ -101,6 +108,8 @@ def parse_args(argv=None) -> argparse.Namespace:
         p.error("--seed .. --seed + --num-samples - 1 must lie in [0, 2^63) for the device generator")
     if not 1 <= args.jpeg_quality <= 100:
         p.error("--jpeg-quality must be from 1 to 100")
+    if not 1 <= args.interp_range <= 24 or not 0 <= args.interp_penalty <= 255:
+        p.error("--interp-range must be from 1 to 24 and --interp-penalty from 0 to 255")
     if args.height % 8 or args.width % 8:
         p.error("--height and --width must be multiples of 8")
     if (args.window_frames is None) != (args.window_stride is None):
@@ -251,9 +260,14 @@ def main(argv=None) -> None:
                                                           decode_chunk_size=args.decode_chunk_size)
                     # the device tensor goes in as it is: .avi / .jpg frames are compressed where they are
                     files = save_frames(frames[0], sample_output_path(args.output, i, args.num_samples), args.fps,
-                                        quality=args.jpeg_quality)
+                                        quality=args.jpeg_quality, interpolate=args.interpolate, interp_range=args.interp_range,
+                                        interp_penalty=args.interp_penalty)
                     LOGGER.info("sample %d (seed %d): %d frames of %dx%d -> %s", i, args.seed + i, frames.shape[1],
                                 frames.shape[3], frames.shape[2], files[0] if len(files) == 1 else os.path.dirname(files[0]))
+                    if args.interpolate > 1:
+                        LOGGER.info("sample %d: interpolated %d frames at %d fps to %d at %d fps (range %d, penalty %d)", i,
+                                    frames.shape[1], args.fps, (frames.shape[1] - 1) * args.interpolate + 1,
+                                    args.fps * args.interpolate, args.interp_range, args.interp_penalty)
     finally:
         finalize_distributed()
         if rendezvous is not None:
