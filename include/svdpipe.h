@@ -404,6 +404,36 @@ int sp_dpmpp2m_sde_step_f16(const void *state, const void *eps_cond, const void 
                             int batch, int frames_total, int h, int w,
                             int window, int stride, int n_win, const float *weights /*[n_win][window] or NULL*/,
                             float noise_scale, const uint64_t *seeds /*[batch], device*/, uint32_t step, void *stream);
+/* Large frames: the tails behind overlapping spatial tiles times the frame windows.  Per axis the
+ * rule of the frame windows: total T, tile t, stride s, 1 <= s <= t <= T, (T - t) % s == 0, n = (T - t)/s + 1 tiles, tile k
+ * covering cells k*s .. k*s + t - 1.  The UNet ran on every patch (kf, ky, kx) -- frame window kf, tile (ky, kx) -- and left
+ * its eps rows in ONE buffer, NHWC rows [n_patch][B][window][tile_h*tile_w][ld_eps], patch k = (kf*n_ty + ky)*n_tx + kx of all
+ * videos starting at row k*B*window*tile_h*tile_w.  The weights are separable: three normalised fp32 tables on the device
+ * (models/tile_plan.py), wf [n_win][window], wy [n_ty][tile_h], wx [n_tx][tile_w]; without frame windows n_win = 1, window =
+ * stride = frames_total and wf is all 1.0.  Per element of global frame f and pixel (y, x) of the LARGE latent:
+ *   e_k = eps_u + g[b,p]*(eps_c - eps_u)    per covering patch, in fp16, as in the _windows_ functions; p = f - kf*stride
+ *   w_k = (wf[kf][p] * wy[ky][y - ky*stride_y]) * wx[kx][x - kx*stride_x]      fp32 products in this order
+ *   e   = fmaf(w_k, e_k, e) from 0 over the covering patches, kf ascending outermost, then ky, then kx; never rounded to fp16
+ * and the update of the _windows_ functions follows, or with noise_scale != 0 that of the stochastic ones (sigma_next_or_down
+ * is then sigma_down); the noise address stays (c*frames_total + f)*h*w + y*w + x with the large h, w, so z does not depend on
+ * the tiling.  One tile that is the whole frame (wy = wx = {1.0}) gives the bytes of the _windows_ / stochastic functions.
+ * out may be the input itself.  Refused, without launching: a null plan or table, a stride outside [1, tile] on any axis, a
+ * total that is not tile plus whole strides, a tile count other than the plan's, ld_guidance in (0, window), 4*frames_total*h*w
+ * > 2^34, out overlapping the input unless it IS the input, and everything the _windows_ and stochastic functions refuse. */
+typedef struct sp_tile_plan {
+  int frames_total, window, stride, n_win;
+  int h, w, tile_h, tile_w, stride_y, stride_x, n_ty, n_tx;
+  const float *wf, *wy, *wx;
+} sp_tile_plan;
+size_t sp_tile_plan_size(void);
+int sp_euler_step_tiles_f16(const sp_tile_plan *plan, const void *latent, const void *eps_cond, const void *eps_uncond,
+                            int64_t ld_eps, const float *guidance, int64_t ld_guidance, void *out, float sigma,
+                            float sigma_next_or_down, int batch, float noise_scale,
+                            const uint64_t *seeds /*[batch], device, or NULL with noise_scale 0*/, uint32_t step, void *stream);
+int sp_dpmpp2m_step_tiles_f16(const sp_tile_plan *plan, const void *state, const void *eps_cond, const void *eps_uncond,
+                              int64_t ld_eps, const float *guidance, int64_t ld_guidance, void *out_state,
+                              float sigma, float a, float b, float c1, float c2, int batch, float noise_scale,
+                              const uint64_t *seeds /*[batch], device, or NULL with noise_scale 0*/, uint32_t step, void *stream);
 /* out (B,4,F,H,W) fp16 = fp16(scale*z), the product rounded once, with z of counter (e >> 2, step, purpose, 0) as above: the initial latent of a video
  * from its seed (scale = init_noise_sigma, step 0, purpose 0), or with purpose 1 the normals a tail adds at `step`.  Refused:
  * null or misaligned pointers, a negative or non-finite scale, 4*F*H*W > 2^34. */

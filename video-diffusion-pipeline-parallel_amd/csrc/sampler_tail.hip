@@ -7,6 +7,10 @@
 // is that of sampler_math.h.  See sp_euler_step_rows_f16 ... sp_dpmpp2m_step_windows_f16 in svdpipe.h.  The stochastic
 // samplers (sp_euler_ancestral_step_f16, sp_dpmpp2m_sde_step_f16) are the same kernel with NOISE: behind the window loop it
 // evaluates the step's normals of its elements from the video's seed (noise.h) and adds n*z inside the update.
+// Large frames (sp_euler_step_tiles_f16, sp_dpmpp2m_step_tiles_f16) are the same kernel with PLAN = TILES: the frame windows
+// times overlapping spatial tiles of tile_h x tile_w cells, the eps rows of all patches in one buffer
+// [n_patch][B][window][tile_h*tile_w][ld_eps], patch (kf, ky, kx) at k = (kf*n_ty + ky)*n_tx + kx, blended per pixel with the
+// product of three small tables, (wf[kf][p] * wy[ky][y - ky*sy]) * wx[kx][x - kx*sx].
 #include "noise.h"
 #include "sampler_math.h"
 
@@ -16,23 +20,34 @@ struct WindowPlan {
   int frames, window, stride, n_win, batch;   // frames = F_total
 };
 
+// The space half of a tile plan: the latent's row length, the tile, the strides, the tile counts and the two axis tables.
+struct TileGeom {
+  int w, th, tw, sy, sx, n_ty, n_tx;
+  const float *wy, *wx;                       // [n_ty][th], [n_tx][tw]
+};
+
 enum { EULER = 0, FIRST_ORDER = 1, SECOND_ORDER = 2 };   // FIRST_ORDER: 2M with c2 == 0, the D_prev planes are never read
+enum { ROWS = 0, WINDOWS = 1, TILES = 2 };               // what the eps rows are cut into: nothing, frame windows, windows x tiles
 
 // A thread owns PX adjacent pixels of one (b, f): the planes are read and written PX at a time (8 bytes for PX = 4), the eps
 // rows one 8-byte row per pixel and covering window.  Every value a thread reads from `st` is in a register before its first
 // store and no other thread touches those elements, so out == st (update in place) is safe; hence no __restrict__ on the two.
-// WINDOWS = false is one window that is the whole latent: no weight table, one eps row per pixel at bf * hw + p, guidance
+// PLAN = ROWS is one window that is the whole latent: no weight table, one eps row per pixel at bf * hw + p, guidance
 // indexed by the frame; the loop below is then one pass and e the eps itself.
+// PLAN = TILES: the covering tiles are those of the thread's first pixel (y, x).  With PX = 4 the host has seen to w, tw and
+// sx being multiples of 4, so the four pixels lie in one row, share their covering tiles and have adjacent eps rows inside a
+// tile -- or to there being one tile that is the whole frame, whose eps rows are the frame's pixels in order.
 // NOISE: z of element (c, f, p) of video b from (seeds[b], step), f the GLOBAL frame: with PX = 4 the thread's four pixels of a
 // channel are the four lanes of one block (hw % 4 == 0), with PX = 1 it evaluates its element's block and takes its lane.
-template <int PX, int MODE, bool WINDOWS, bool NOISE>
+template <int PX, int MODE, int PLAN, bool NOISE>
 __global__ __launch_bounds__(256) void sampler_tail_kernel(const f16 *st, const f16 *__restrict__ ec,
                                                            const f16 *__restrict__ eu, int64_t ld_eps,
                                                            const float *__restrict__ gs, int64_t ld_g,
                                                            const float *__restrict__ wn, f16 *out, SamplerCoef k,
-                                                           WindowPlan wp, int64_t hw, int64_t total,
+                                                           WindowPlan wp, TileGeom tg, int64_t hw, int64_t total,
                                                            const uint64_t *__restrict__ seeds, uint32_t step) {
   typedef f16 vec __attribute__((ext_vector_type(PX)));
+  constexpr bool WINDOWS = PLAN != ROWS;
   constexpr int CH = MODE == EULER ? 4 : 8;
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // one group of PX pixels of a (b, f)
   if (idx >= total) return;
@@ -67,28 +82,57 @@ __global__ __launch_bounds__(256) void sampler_tail_kernel(const f16 *st, const 
     k_lo = f < wp.window ? 0 : (f - wp.window) / wp.stride + 1;
     k_hi = min(f / wp.stride, wp.n_win - 1);
   }
+  // the tiles that cover the pixels, per axis by the same rule; one pass of both loops unless PLAN is TILES
+  int y = 0, x0 = 0, ky_lo = 0, ky_hi = 0, kx_lo = 0, kx_hi = 0;
+  if constexpr (PLAN == TILES) {
+    y = (int)(p / tg.w);
+    x0 = (int)(p % tg.w);
+    ky_lo = y < tg.th ? 0 : (y - tg.th) / tg.sy + 1;
+    ky_hi = min(y / tg.sy, tg.n_ty - 1);
+    kx_lo = x0 < tg.tw ? 0 : (x0 - tg.tw) / tg.sx + 1;
+    kx_hi = min(x0 / tg.sx, tg.n_tx - 1);
+  }
   for (int kw = k_lo; kw <= k_hi; ++kw) {
     int pos = f;                                                         // position in the window: 0 .. window - 1
     float wgt = 1.f;
-    int64_t row = bf * hw + p;                                           // eps row of the first pixel
+    int64_t wrow = bf * hw + p;                                          // eps row of the first pixel
     if constexpr (WINDOWS) {
       pos = f - kw * wp.stride;
       wgt = wn[kw * wp.window + pos];
-      row = (((int64_t)kw * wp.batch + b) * wp.window + pos) * hw + p;
+      wrow = (((int64_t)kw * wp.batch + b) * wp.window + pos) * hw + p;
     }
     float g = 1.f;
     if (eu) g = gs[b * ld_g + pos];                                      // guidance follows the position in the window
+    for (int ky = ky_lo; ky <= ky_hi; ++ky)
+      for (int kx = kx_lo; kx <= kx_hi; ++kx) {
+        float wj[PX];
+        int64_t row = wrow;
+        if constexpr (PLAN == TILES) {
+          const int ly = y - ky * tg.sy, lx = x0 - kx * tg.sx;          // the first pixel inside the tile
 #pragma unroll
-    for (int j = 0; j < PX; ++j) {
-      const f16x4 c4 = *(const f16x4 *)(ec + (row + j) * ld_eps);
-      f16x4 u4 = c4;
-      if (eu) u4 = *(const f16x4 *)(eu + (row + j) * ld_eps);
+          for (int j = 0; j < PX; ++j) {
+            int lyj = ly, lxj = lx + j;
+            while (lxj >= tg.tw) { lxj -= tg.tw; ++lyj; }              // one tile that is the whole frame: into the next row
+            wj[j] = (wgt * tg.wy[ky * tg.th + lyj]) * tg.wx[kx * tg.tw + lxj];
+          }
+          const int64_t patch = ((int64_t)kw * tg.n_ty + ky) * tg.n_tx + kx;
+          row = ((patch * wp.batch + b) * wp.window + pos) * ((int64_t)tg.th * tg.tw) + (int64_t)ly * tg.tw + lx;
+        } else {
 #pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const float v = eu ? guidance_mix_f16(g, c4[c], u4[c]) : (float)c4[c];
-        e[c][j] = WINDOWS ? fmaf(wgt, v, e[c][j]) : v;                   // fp32, never rounded to fp16
+          for (int j = 0; j < PX; ++j) wj[j] = wgt;
+        }
+#pragma unroll
+        for (int j = 0; j < PX; ++j) {
+          const f16x4 c4 = *(const f16x4 *)(ec + (row + j) * ld_eps);
+          f16x4 u4 = c4;
+          if (eu) u4 = *(const f16x4 *)(eu + (row + j) * ld_eps);
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            const float v = eu ? guidance_mix_f16(g, c4[c], u4[c]) : (float)c4[c];
+            e[c][j] = WINDOWS ? fmaf(wj[j], v, e[c][j]) : v;             // fp32, never rounded to fp16
+          }
+        }
       }
-    }
   }
   uint64_t seed = 0;
   if constexpr (NOISE) seed = seeds[b];
@@ -118,7 +162,7 @@ __global__ __launch_bounds__(256) void sampler_tail_kernel(const f16 *st, const 
 }
 
 // One checked call: the pointers as the entry got them, the constants of its step, its plan (for one set of eps rows: a
-// single window that is the whole latent, weights null) and whether the four-pixel form applies.
+// single window that is the whole latent, weights null; for tiles also the space half) and whether the four-pixel form applies.
 struct Tail {
   const char *name;
   const f16 *st, *ec, *eu;
@@ -127,6 +171,7 @@ struct Tail {
   f16 *out;
   SamplerCoef k;
   WindowPlan wp;
+  TileGeom tg;             // tg.wy != null: the tiles form
   bool wide;
   const uint64_t *seeds;   // [batch] on the device; read only where k.n != 0
   uint32_t step;
@@ -134,11 +179,13 @@ struct Tail {
 
 template <int MODE, bool NOISE>
 void launch_form(const Tail &t, void *stream) {
-  const auto kernel = t.wn ? (t.wide ? sampler_tail_kernel<4, MODE, true, NOISE> : sampler_tail_kernel<1, MODE, true, NOISE>)
-                           : (t.wide ? sampler_tail_kernel<4, MODE, false, NOISE> : sampler_tail_kernel<1, MODE, false, NOISE>);
+  const int plan = t.tg.wy ? TILES : t.wn ? WINDOWS : ROWS;
+  const auto kernel = plan == TILES     ? (t.wide ? sampler_tail_kernel<4, MODE, TILES, NOISE> : sampler_tail_kernel<1, MODE, TILES, NOISE>)
+                      : plan == WINDOWS ? (t.wide ? sampler_tail_kernel<4, MODE, WINDOWS, NOISE> : sampler_tail_kernel<1, MODE, WINDOWS, NOISE>)
+                                        : (t.wide ? sampler_tail_kernel<4, MODE, ROWS, NOISE> : sampler_tail_kernel<1, MODE, ROWS, NOISE>);
   const int64_t total = (int64_t)t.wp.batch * t.wp.frames * t.hw / (t.wide ? 4 : 1);
   hipLaunchKernelGGL(kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, t.st, t.ec, t.eu, t.ld_eps,
-                     t.gs, t.ld_g, t.wn, t.out, t.k, t.wp, t.hw, total, t.seeds, t.step);
+                     t.gs, t.ld_g, t.wn, t.out, t.k, t.wp, t.tg, t.hw, total, t.seeds, t.step);
 }
 
 // n == 0 (the deterministic samplers, eta == 0, the last step) is the kernel without noise: the bytes of the existing entries
@@ -174,7 +221,7 @@ int check(const char *name, const void *state, const void *eps_cond, const void 
              "%s: out must be the input itself or not overlap it", name);
   const float s2 = sigma * sigma + 1.0f;
   *t = Tail{name, (const f16 *)state, (const f16 *)eps_cond, (const f16 *)eps_uncond, guidance, weights, ld_eps, ld_guidance, hw,
-            (f16 *)out, SamplerCoef{-sigma / sqrtf(s2), 1.0f / s2}, WindowPlan{frames_total, window, stride, n_win, batch},
+            (f16 *)out, SamplerCoef{-sigma / sqrtf(s2), 1.0f / s2}, WindowPlan{frames_total, window, stride, n_win, batch}, TileGeom{},
             // four pixels per thread where every plane access stays 8-byte aligned
             hw % 4 == 0 && s0 % 8 == 0 && o0 % 8 == 0, nullptr, 0u};
   return SP_OK;
@@ -198,6 +245,37 @@ int check_noise(const char *name, const void *state, const void *eps_cond, const
   SP_REQUIRE(noise_fits(frames_total, t->hw), "%s: 4*frames_total*h*w = 4*%d*%lld exceeds 2^34, the noise address' range", name,
              frames_total, (long long)t->hw);
   t->k.n = noise_scale; t->seeds = seeds; t->step = step;
+  return SP_OK;
+}
+
+// The tiles entries: the plan record, its two space triples, then check_noise() on the frame triple and everything else.
+int check_tiles(const char *name, const sp_tile_plan *pl, const void *state, const void *eps_cond, const void *eps_uncond,
+                int64_t ld_eps, const float *guidance, int64_t ld_guidance, void *out, float sigma, int channels, int batch,
+                float noise_scale, const uint64_t *seeds, uint32_t step, Tail *t) {
+  SP_REQUIRE(pl, "%s: null plan", name);
+  SP_REQUIRE(pl->wf && pl->wy && pl->wx, "%s: null table (the plan's normalised wf [n_win][window], wy [n_ty][tile_h], wx [n_tx][tile_w])",
+             name);
+  SP_REQUIRE(pl->h > 0 && pl->w > 0 && pl->tile_h > 0 && pl->tile_w > 0, "%s: dims must be positive", name);
+  const struct { const char *axis; int total, tile, stride, n; } ax[2] = {{"y", pl->h, pl->tile_h, pl->stride_y, pl->n_ty},
+                                                                          {"x", pl->w, pl->tile_w, pl->stride_x, pl->n_tx}};
+  for (const auto &a : ax) {
+    SP_REQUIRE(a.tile <= a.total, "%s: %s (total, tile, stride) = (%d, %d, %d): the tile exceeds the total", name, a.axis, a.total,
+               a.tile, a.stride);
+    SP_REQUIRE(a.stride >= 1 && a.stride <= a.tile, "%s: %s (total, tile, stride) = (%d, %d, %d): stride must be from 1 to the tile",
+               name, a.axis, a.total, a.tile, a.stride);
+    SP_REQUIRE((a.total - a.tile) % a.stride == 0,
+               "%s: %s (total, tile, stride) = (%d, %d, %d): the total is not the tile plus a whole number of strides", name, a.axis,
+               a.total, a.tile, a.stride);
+    SP_REQUIRE(a.n == (a.total - a.tile) / a.stride + 1, "%s: n_t%s=%d, the plan of %s (total, tile, stride) = (%d, %d, %d) has %d tiles",
+               name, a.axis, a.n, a.axis, a.total, a.tile, a.stride, (a.total - a.tile) / a.stride + 1);
+  }
+  if (int rc = check_noise(name, state, eps_cond, eps_uncond, ld_eps, guidance, ld_guidance, out, sigma, channels, batch,
+                           pl->frames_total, pl->h, pl->w, pl->window, pl->stride, pl->n_win, pl->wf, noise_scale, seeds, step, t))
+    return rc;
+  t->tg = TileGeom{pl->w, pl->tile_h, pl->tile_w, pl->stride_y, pl->stride_x, pl->n_ty, pl->n_tx, pl->wy, pl->wx};
+  // four pixels per thread where they also share a row, their covering tiles and adjacent eps rows inside every tile; one
+  // tile that is the whole frame keeps the form of the _windows_ functions, and with it their bytes
+  t->wide = t->wide && ((pl->w % 4 == 0 && pl->tile_w % 4 == 0 && pl->stride_x % 4 == 0) || (pl->n_ty == 1 && pl->n_tx == 1));
   return SP_OK;
 }
 
@@ -291,6 +369,30 @@ extern "C" int sp_dpmpp2m_sde_step_f16(const void *state, const void *eps_cond, 
   Tail t;
   if (int rc = check_noise("sp_dpmpp2m_sde_step_f16", state, eps_cond, eps_uncond, ld_eps, guidance, ld_guidance, out_state, sigma, 8,
                            batch, frames_total, h, w, window, stride, n_win, weights, noise_scale, seeds, step, &t))
+    return rc;
+  return dpmpp2m_step(t, a, b, c1, c2, stream);
+}
+
+extern "C" size_t sp_tile_plan_size(void) { return sizeof(sp_tile_plan); }
+
+extern "C" int sp_euler_step_tiles_f16(const sp_tile_plan *plan, const void *latent, const void *eps_cond, const void *eps_uncond,
+                                       int64_t ld_eps, const float *guidance, int64_t ld_guidance, void *out, float sigma,
+                                       float sigma_next_or_down, int batch, float noise_scale, const uint64_t *seeds,
+                                       uint32_t step, void *stream) {
+  Tail t;
+  if (int rc = check_tiles("sp_euler_step_tiles_f16", plan, latent, eps_cond, eps_uncond, ld_eps, guidance, ld_guidance, out, sigma, 4,
+                           batch, noise_scale, seeds, step, &t))
+    return rc;
+  return euler_step(t, sigma, sigma_next_or_down, stream);
+}
+
+extern "C" int sp_dpmpp2m_step_tiles_f16(const sp_tile_plan *plan, const void *state, const void *eps_cond, const void *eps_uncond,
+                                         int64_t ld_eps, const float *guidance, int64_t ld_guidance, void *out_state, float sigma,
+                                         float a, float b, float c1, float c2, int batch, float noise_scale,
+                                         const uint64_t *seeds, uint32_t step, void *stream) {
+  Tail t;
+  if (int rc = check_tiles("sp_dpmpp2m_step_tiles_f16", plan, state, eps_cond, eps_uncond, ld_eps, guidance, ld_guidance, out_state, sigma,
+                           8, batch, noise_scale, seeds, step, &t))
     return rc;
   return dpmpp2m_step(t, a, b, c1, c2, stream);
 }

@@ -44,6 +44,17 @@ class GemmDesc(ctypes.Structure):
     ]
 
 
+class TilePlan(ctypes.Structure):
+    """Mirror of ``struct sp_tile_plan`` (include/svdpipe.h)."""
+
+    _fields_ = [
+        ("frames_total", ctypes.c_int), ("window", ctypes.c_int), ("stride", ctypes.c_int), ("n_win", ctypes.c_int),
+        ("h", ctypes.c_int), ("w", ctypes.c_int), ("tile_h", ctypes.c_int), ("tile_w", ctypes.c_int),
+        ("stride_y", ctypes.c_int), ("stride_x", ctypes.c_int), ("n_ty", ctypes.c_int), ("n_tx", ctypes.c_int),
+        ("wf", ctypes.c_void_p), ("wy", ctypes.c_void_p), ("wx", ctypes.c_void_p),
+    ]
+
+
 # name -> (restype, argtypes); every symbol declared in include/svdpipe.h
 _P, _I, _L, _F, _Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
 _U = ctypes.c_uint32
@@ -85,6 +96,10 @@ SIGNATURES = {
     "sp_euler_ancestral_step_f16": (_I, [_P, _P, _P, _L, _P, _L, _P, _F, _F, _I, _I, _I, _I, _I, _I, _I, _P, _F, _P, _U, _P]),
     "sp_dpmpp2m_sde_step_f16": (_I, [_P, _P, _P, _L, _P, _L, _P, _F, _F, _F, _F, _F, _I, _I, _I, _I, _I, _I, _I, _P, _F, _P, _U,
                                      _P]),
+    "sp_tile_plan_size": (_Z, []),
+    "sp_euler_step_tiles_f16": (_I, [ctypes.POINTER(TilePlan), _P, _P, _P, _L, _P, _L, _P, _F, _F, _I, _F, _P, _U, _P]),
+    "sp_dpmpp2m_step_tiles_f16": (_I, [ctypes.POINTER(TilePlan), _P, _P, _P, _L, _P, _L, _P, _F, _F, _F, _F, _F, _I, _F, _P, _U,
+                                       _P]),
     "sp_randn_f16": (_I, [_P, _P, _F, _I, _I, _I, _I, _U, _U, _P]),
     "sp_philox_blocks_u32": (_I, [_P, _P, _I, _L, _U, _U, _P]),
     "sp_concat_channels_f16": (_I, [_P, _I, _P, _I, _P, _L, _P]),
@@ -165,6 +180,9 @@ def load():
         if lib.sp_gemm_desc_size() != ctypes.sizeof(GemmDesc):
             raise RuntimeError(f"GemmDesc mirrors {ctypes.sizeof(GemmDesc)} bytes, the library's sp_gemm_desc has "
                                f"{lib.sp_gemm_desc_size()}: rebuild the library or update hip/__init__.py")
+        if lib.sp_tile_plan_size() != ctypes.sizeof(TilePlan):
+            raise RuntimeError(f"TilePlan mirrors {ctypes.sizeof(TilePlan)} bytes, the library's sp_tile_plan has "
+                               f"{lib.sp_tile_plan_size()}: rebuild the library or update hip/__init__.py")
         _lib = lib
     return _lib
 

@@ -1068,6 +1068,64 @@ def dpmpp2m_sde_step(state, eps_cond, eps_uncond, guidance, out_state, *, ld_eps
     return out_state
 
 
+class TileRecord:
+    """A ``models.tile_plan.TilePlan`` as the kernels take it: the ``sp_tile_plan`` record and the three weight tables on the
+    device, which it keeps alive."""
+
+    def __init__(self, plan, device):
+        from . import TilePlan
+        self.plan = plan
+        self.wf, self.wy, self.wx = (torch.from_numpy(t).to(device).contiguous() for t in (plan.wf, plan.wy, plan.wx))
+        fr, ay, ax = plan.frames, plan.y, plan.x
+        self.desc = TilePlan(frames_total=fr.frames_total, window=fr.window, stride=fr.stride, n_win=fr.n_win,
+                             h=ay.frames_total, w=ax.frames_total, tile_h=ay.window, tile_w=ax.window, stride_y=ay.stride,
+                             stride_x=ax.stride, n_ty=ay.n_win, n_tx=ax.n_win, wf=self.wf.data_ptr(), wy=self.wy.data_ptr(),
+                             wx=self.wx.data_ptr())
+
+
+def _tile_args(name, tensors, channels, batch, rec, eps_cond, eps_uncond, ld_eps, noise_scale, seeds):
+    """Shapes the tiles tails cannot see through raw pointers; returns the seeds pointer."""
+    d = rec.desc
+    for what, t in tensors.items():
+        if _f16(t, what).shape != (batch, channels, d.frames_total, d.h, d.w) or not t.is_contiguous():
+            raise ValueError(f"{name}: {what} must be a contiguous ({batch}, {channels}, {d.frames_total}, {d.h}, {d.w}) tensor; "
+                             f"got {tuple(t.shape)}, strides {tuple(t.stride())}")
+    n_patch = d.n_win * d.n_ty * d.n_tx
+    rows = n_patch * batch * d.window * d.tile_h * d.tile_w
+    for what, t in (("eps_cond", eps_cond), ("eps_uncond", eps_uncond)):
+        if t is not None and (_f16(t, what).numel() != rows * ld_eps or not t.is_contiguous()):
+            raise ValueError(f"{name}: {what} must hold [n_patch={n_patch}][B={batch}][window={d.window}]"
+                             f"[{d.tile_h * d.tile_w}][ld_eps={ld_eps}] contiguous values; got {tuple(t.shape)}")
+    if seeds is None and noise_scale != 0.0:
+        raise ValueError(f"{name}: noise_scale={noise_scale} needs the videos' seeds")
+    return None if seeds is None else _seeds(seeds, batch, name)
+
+
+def euler_step_tiles(latent, eps_cond, eps_uncond, guidance, out, *, plan, ld_eps, sigma, sigma_next, b, ld_guidance=0,
+                     noise_scale=0.0, seeds=None, step=0):
+    """The Euler update of ``latent`` (B,4,F_total,H,W) behind the eps rows of the patches of ``plan`` (a ``TileRecord``):
+    frame windows times overlapping spatial tiles, ``[n_patch][B][window][tile_h*tile_w][ld_eps]``.  ``noise_scale != 0`` is the
+    Euler ancestral update (``sigma_next`` is then sigma_down) with the noise of ``seeds`` and ``step``
+    (``sp_euler_step_tiles_f16``)."""
+    sp = _tile_args("euler_step_tiles", {"latent": latent, "out": out}, 4, b, plan, eps_cond, eps_uncond, ld_eps, noise_scale, seeds)
+    _check(load().sp_euler_step_tiles_f16(ctypes.byref(plan.desc), latent.data_ptr(), eps_cond.data_ptr(), _ptr(eps_uncond), ld_eps,
+                                          _ptr(guidance), int(ld_guidance), out.data_ptr(), sigma, sigma_next, b, noise_scale, sp,
+                                          int(step), _stream()), "sp_euler_step_tiles_f16")
+    return out
+
+
+def dpmpp2m_step_tiles(state, eps_cond, eps_uncond, guidance, out_state, *, plan, ld_eps, sigma, a, b, c1, c2, batch,
+                       ld_guidance=0, noise_scale=0.0, seeds=None, step=0):
+    """``dpmpp2m_step`` (``noise_scale != 0``: ``dpmpp2m_sde_step``) of the 8-channel ``state`` (B,8,F_total,H,W) behind the eps
+    rows of the patches of ``plan``; layouts as for ``euler_step_tiles`` (``sp_dpmpp2m_step_tiles_f16``)."""
+    sp = _tile_args("dpmpp2m_step_tiles", {"state": state, "out_state": out_state}, 8, batch, plan, eps_cond, eps_uncond, ld_eps,
+                    noise_scale, seeds)
+    _check(load().sp_dpmpp2m_step_tiles_f16(ctypes.byref(plan.desc), state.data_ptr(), eps_cond.data_ptr(), _ptr(eps_uncond),
+                                            ld_eps, _ptr(guidance), int(ld_guidance), out_state.data_ptr(), sigma, a, b, c1, c2,
+                                            batch, noise_scale, sp, int(step), _stream()), "sp_dpmpp2m_step_tiles_f16")
+    return out_state
+
+
 def randn(out, seeds, *, scale=1.0, step=0, purpose=0):
     """``out`` (B,4,F,H,W) fp16 = ``scale * z``: video ``b``'s normals of (``seeds[b]``, ``step``, ``purpose``), whatever it is
     batched with (``sp_randn_f16``; purpose 0 = the initial latent, 1 = a sampler step's noise)."""

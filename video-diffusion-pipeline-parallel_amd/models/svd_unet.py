@@ -27,7 +27,7 @@ import torch
 import torch.nn as nn
 
 from ..hip import ops
-from . import euler_schedule, solver_schedule, window_plan
+from . import euler_schedule, solver_schedule, tile_plan, window_plan
 from .unet_hip import SVDUNetHIP
 from .unet_spec import UNetConfig, random_state_dict
 
@@ -113,6 +113,9 @@ class StableVideoUNet(nn.Module):
         windows_per_call: int = 1,
         eta: float = 1.0,
         s_noise: float = 1.0,
+        tile_size=None,
+        tile_stride=None,
+        tile_weights: str = "triangle",
     ) -> None:
         """``batched_cfg`` (extension): run the unconditional and conditional passes of
         classifier-free guidance as ONE batch-2 UNet forward instead of two sequential passes
@@ -134,8 +137,29 @@ class StableVideoUNet(nn.Module):
         W frames, ``window_stride`` apart (``models/window_plan.py``), and ONE sampler update follows behind all windows' eps
         rows, blended per frame with ``window_weights`` ("triangle": a window counts most at its centre; "uniform").
         ``windows_per_call`` windows are stacked as extra batch rows of one UNet call.  None: every path is the unwindowed
-        one."""
+        one.
+
+        ``tile_size=(th, tw)``, ``tile_stride=(sy, sx)`` (extension; latent cells): large frames by
+        spatial co-denoising.  ``forward`` then accepts a latent whose H x W exceed the tile -- the size the model was trained
+        at -- and a conditioning whose ``image_latents`` have the LARGE size: every step runs the UNet on overlapping tiles
+        (``models/tile_plan.py``), each conditioned on the crop of the image latents at its own position (the CLIP embedding and
+        the added-time ids are shared), and ONE sampler update follows behind all patches' eps rows, blended per pixel with
+        the separable ``tile_weights``.  With ``window_stride`` the patches are frame windows times tiles;
+        ``windows_per_call`` then counts patches.  None: today's paths."""
         super().__init__()
+        if (tile_size is None) != (tile_stride is None):
+            raise ValueError(f"tile_size and tile_stride go together (both pairs of latent cells, or both None); got "
+                             f"tile_size={tile_size}, tile_stride={tile_stride}")
+        if tile_weights not in tile_plan.WEIGHTS:
+            raise ValueError(f"tile_weights must be one of {tile_plan.WEIGHTS}; got {tile_weights!r}")
+        self.tile_size = self.tile_stride = None
+        if tile_size is not None:
+            self.tile_size, self.tile_stride = tile_plan._pair("tile_size", tile_size), tile_plan._pair("tile_stride", tile_stride)
+            for name, t, st in zip("yx", self.tile_size, self.tile_stride):
+                if t < 1 or not 1 <= st <= t:
+                    raise ValueError(f"tile plan, {name} (tile={t}, stride={st}): tile must be at least 1 and stride from 1 to tile")
+        self.tile_weights = tile_weights
+        self._tile_plans: dict = {}      # (frames_total, window, H, W) -> ops.TileRecord
         if window_stride is not None and int(window_stride) < 1:
             raise ValueError(f"window_stride must be a positive frame count or None; got {window_stride}")
         if window_weights not in window_plan.WEIGHTS:
@@ -242,6 +266,9 @@ class StableVideoUNet(nn.Module):
         window_weights: str = "triangle",
         eta: float = 1.0,
         s_noise: float = 1.0,
+        tile_size=None,
+        tile_stride=None,
+        tile_weights: str = "triangle",
         **kwargs,
     ) -> "StableVideoUNet":
         """Load ``<model_id>/unet/diffusion_pytorch_model*.safetensors`` from a LOCAL directory.
@@ -291,21 +318,24 @@ class StableVideoUNet(nn.Module):
         if timesteps is None:
             timesteps = cls._default_timestep_schedule(num_steps=25)
         return cls(unet=SVDUNetHIP(cfg, sd, device), timesteps=timesteps, dtype=torch_dtype, sampler=sampler,
-                   window_stride=window_stride, window_weights=window_weights, eta=eta, s_noise=s_noise)
+                   window_stride=window_stride, window_weights=window_weights, eta=eta, s_noise=s_noise,
+                   tile_size=tile_size, tile_stride=tile_stride, tile_weights=tile_weights)
 
     @classmethod
     def from_random_init(cls, timesteps: Sequence[int], *, config: UNetConfig | None = None, seed: int = 0,
                          device="cuda", fp8_attention: bool | None = None,
                          long_attention: bool | None = None, sampler: str = "euler",
                          window_stride: int | None = None, window_weights: str = "triangle", eta: float = 1.0,
-                         s_noise: float = 1.0) -> "StableVideoUNet":
+                         s_noise: float = 1.0, tile_size=None, tile_stride=None,
+                         tile_weights: str = "triangle") -> "StableVideoUNet":
         """Random weights of the exact SVD architecture (benchmarks / tests; no checkpoint needed)."""
         cfg = config or UNetConfig.svd()
         sd = random_state_dict(cfg, seed=seed, device=device, dtype=torch.float16)
         unet = SVDUNetHIP(cfg, sd, device, fp8_attention=fp8_attention, long_attention=long_attention)
         del sd
         return cls(unet=unet, timesteps=timesteps, sampler=sampler, window_stride=window_stride,
-                   window_weights=window_weights, eta=eta, s_noise=s_noise)
+                   window_weights=window_weights, eta=eta, s_noise=s_noise, tile_size=tile_size, tile_stride=tile_stride,
+                   tile_weights=tile_weights)
 
     def enable_graphs(self, enabled: bool = True) -> None:
         """Replay each diffusion step from a captured HIP graph (one graph per step index and latent shape).
@@ -539,6 +569,8 @@ class StableVideoUNet(nn.Module):
         elif tuple(cond.image_latents.shape) != sample_shape:
             raise ValueError(f"image_latents {tuple(cond.image_latents.shape)} do not match the latent "
                              f"{sample_shape} (set_conditioning was called for another batch / frame count / size)")
+        if self.tile_size is not None:                         # ValueError naming (total, tile, stride) of the axis
+            self._tile_plan(latent.shape[2], frames, latent.shape[3], latent.shape[4])
         emb = cond.image_embeddings
         if emb.dim() != 3 or emb.shape[0] != latent.shape[0] or emb.shape[1] != 1 \
                 or emb.shape[2] != self.unet.cfg.cross_attention_dim:
@@ -609,6 +641,8 @@ class StableVideoUNet(nn.Module):
 
     def _forward_eager(self, latent: torch.Tensor, step: int, cond: VideoConditioning | None = None) -> torch.Tensor:
         cond = self._cond if cond is None else cond
+        if self.tile_size is not None:
+            return self._forward_tiles(latent, step, cond)
         if self.window_stride is not None:
             return self._forward_windows(latent, step, cond)
         if self.state_channels == 8:
@@ -711,3 +745,69 @@ class StableVideoUNet(nn.Module):
                                             batch=b, **common)
         return ops.euler_step_windows(state, eps_c, eps_u, guidance, out, sigma=sigma,
                                       sigma_next=self._sigma_host[step + 1], b=b, **common)
+
+    # ------------------------------------------------------------------ large frames: overlapping spatial tiles
+    def _tile_plan(self, frames_total: int, window: int, h: int, w: int):
+        """The ``ops.TileRecord`` (plan, tables on the device) of a latent of ``frames_total`` x ``h`` x ``w`` cut into frame
+        windows of ``window`` (one window without ``window_stride``) times tiles of ``tile_size``."""
+        key = (int(frames_total), int(window), int(h), int(w))
+        rec = self._tile_plans.get(key)
+        if rec is None:
+            stride = self.window_stride if self.window_stride is not None else window
+            pl = tile_plan.plan(h, w, self.tile_size, self.tile_stride, self.tile_weights, frames_total=frames_total,
+                                window=window, window_stride=stride, window_weights=self.window_weights)
+            rec = self._tile_plans[key] = ops.TileRecord(pl, self.unet.device)
+        return rec
+
+    @staticmethod
+    def _patch_conditioning(cond: VideoConditioning, part, th: int, tw: int) -> VideoConditioning:
+        """The conditioning of one UNet call on the patches ``part`` stacked as ``[patch][video]`` batch rows: every patch's crop
+        of the image latents at its own position; the embeddings and the added-time ids repeated."""
+        def rep(t):
+            return t if len(part) == 1 else torch.cat([t] * len(part), dim=0)
+
+        def crops(t):
+            return torch.cat([t[:, :, :, y0:y0 + th, x0:x0 + tw] for *_, y0, x0 in part], dim=0).contiguous()
+
+        guided = cond.guided
+        return dataclasses.replace(
+            cond, image_embeddings=rep(cond.image_embeddings), image_latents=crops(cond.image_latents),
+            added_ids32=cond.added_ids32 if cond.added_ids32.dim() == 1 else rep(cond.added_ids32),
+            uncond_embeddings=rep(cond.uncond_embeddings) if guided else None,
+            uncond_image_latents=crops(cond.uncond_image_latents) if guided else None)
+
+    def _forward_tiles(self, state: torch.Tensor, step: int, cond: VideoConditioning) -> torch.Tensor:
+        """One step of a latent of F_total x H x W as n_patch = n_win * n_ty * n_tx patches (frame windows times spatial tiles):
+        the UNet passes of the plain step on every patch's slice (``windows_per_call`` patches of all B videos per call, each
+        conditioned on its own crop), each call's eps rows stored to its slice of one [n_patch][B][W][th*tw][4] buffer per pass,
+        then ONE tail behind them (``sp_euler_step_tiles_f16`` / ``sp_dpmpp2m_step_tiles_f16``).  All four samplers take the
+        stored-eps route, as for windows."""
+        b, _, ft, h, w = state.shape
+        win = cond.num_frames if self.window_stride is not None else ft
+        rec = self._tile_plan(ft, win, h, w)
+        th, tw = rec.plan.tile
+        patches = rec.plan.patches()
+        sigma = self._sigma_host[step]
+        in_scale = 1.0 / math.sqrt(sigma * sigma + 1.0)
+        x = state if self.state_channels == 4 else state[:, :4]
+        ld_eps = self.unet.cfg.out_channels
+        rows = b * win * th * tw                                # eps rows of one patch of all videos
+        eps_c = torch.empty((len(patches) * rows, ld_eps), dtype=torch.float16, device=state.device)
+        eps_u = torch.empty_like(eps_c) if cond.guided else None
+        for k0 in range(0, len(patches), self.windows_per_call):
+            part = patches[k0:k0 + self.windows_per_call]
+            # [patch][video] batch rows: the layout of the eps buffer
+            xs = torch.cat([x[:, :, f0:f0 + win, y0:y0 + th, x0:x0 + tw] for _, _, _, f0, y0, x0 in part], dim=0).contiguous()
+            dst = slice(k0 * rows, (k0 + len(part)) * rows)
+            self._unet_passes(xs, self._patch_conditioning(cond, part, th, tw), step, in_scale,
+                              eps_out=(eps_c[dst], eps_u[dst] if cond.guided else None))
+        out = torch.empty_like(state)
+        common = dict(plan=rec, ld_eps=ld_eps, sigma=sigma, ld_guidance=cond.guidance_ld)
+        if self.stochastic:                                    # the noise of element (f, y, x), whichever patches cover it
+            common.update(seeds=cond.noise_seeds, step=step, noise_scale=self._noise_coef[step][-1])
+        guidance = cond.guidance32 if cond.guided else None
+        if self.state_channels == 8:
+            a, b_, c1, c2 = (self._noise_coef if self.stochastic else self._solver_coef)[step][:4]
+            return ops.dpmpp2m_step_tiles(state, eps_c, eps_u, guidance, out, a=a, b=b_, c1=c1, c2=c2, batch=b, **common)
+        sigma_next = self._noise_coef[step][0] if self.stochastic else self._sigma_host[step + 1]
+        return ops.euler_step_tiles(state, eps_c, eps_u, guidance, out, sigma_next=sigma_next, b=b, **common)

@@ -15,6 +15,14 @@ receive all ``--num-frames`` frames:
     python -m vdpp_amd.modes.generate --random-init --input-image in.png --num-frames 28 --window-frames 14 \
         --window-stride 7 --output out.gif
 
+``--tile-height TH --tile-width TW --tile-stride-y SY --tile-stride-x SX`` (pixels, multiples of 8) make frames larger than the
+model's native size: ``--height`` / ``--width`` are then the total, every step denoises the large latent as overlapping tiles of
+TH x TW fused in the sampler update (``StableVideoUNet(tile_size=, tile_stride=)``), each tile conditioned
+on its own crop of the image latents; decode, ``--interpolate`` and every output format receive the one large latent:
+
+    python -m vdpp_amd.modes.generate --random-init --input-image in.png --height 576 --width 2048 --tile-height 576 \
+        --tile-width 1024 --tile-stride-y 576 --tile-stride-x 512 --output out.gif
+
 Every rank builds the conditioning from the file itself -- the image kernels, CLIP and the VAE encoder are deterministic
 and the augmentation noise comes from a seeded CPU generator, so nothing is broadcast (the reference encodes on every rank
 as well, ref ``:250-300``).  The steps go through ``run_pipeline_latents`` as in ``production.py``; the rank that ends up
@@ -66,6 +74,16 @@ def parse_args(argv=None) -> argparse.Namespace:
                         "number of strides")
     p.add_argument("--window-weights", type=str, default="triangle", choices=["triangle", "uniform"],
                    help="how the windows covering a frame are blended: weighted most at a window's centre, or equally")
+    p.add_argument("--tile-height", type=int, default=None,
+                   help="large frames: the model's native height in pixels; --height is then the total, denoised as "
+                        "overlapping tiles (needs --tile-width, --tile-stride-y and --tile-stride-x; multiples of 8)")
+    p.add_argument("--tile-width", type=int, default=None, help="the model's native width in pixels; --width is then the total")
+    p.add_argument("--tile-stride-y", type=int, default=None,
+                   help="pixels between the tops of consecutive tiles, from 8 to --tile-height; --height must be the tile "
+                        "height plus a whole number of strides")
+    p.add_argument("--tile-stride-x", type=int, default=None, help="the same along the width")
+    p.add_argument("--tile-weights", type=str, default="triangle", choices=["triangle", "uniform"],
+                   help="how the tiles covering a pixel are blended: weighted most at a tile's centre, or equally")
     p.add_argument("--total-steps", type=int, default=25)
     p.add_argument("--sampler", type=str, default="euler", choices=["euler", "dpmpp_2m", "euler_a", "dpmpp_2m_sde"],
                    help="euler: the reference's first-order update; dpmpp_2m: DPM-Solver++(2M), second order at one UNet "
@@ -127,7 +145,34 @@ def parse_args(argv=None) -> argparse.Namespace:
             lo, hi = window_plan.legal_totals(args.num_frames, w, st)
             p.error(f"--num-frames {args.num_frames} is not --window-frames {w} plus a whole number of strides of {st}: "
                     f"the nearest legal totals are {lo} and {hi}")
+    tiles = (args.tile_height, args.tile_width, args.tile_stride_y, args.tile_stride_x)
+    if any(v is not None for v in tiles) and any(v is None for v in tiles):
+        p.error("--tile-height, --tile-width, --tile-stride-y and --tile-stride-x go together")
+    if args.tile_height is not None:
+        from ..models import tile_plan
+
+        if any(v % 8 for v in tiles):
+            p.error("--tile-height, --tile-width, --tile-stride-y and --tile-stride-x must be multiples of 8")
+        for axis, flag, total, t, st in (("y", "height", args.height, args.tile_height, args.tile_stride_y),
+                                         ("x", "width", args.width, args.tile_width, args.tile_stride_x)):
+            if t < 8 or not 8 <= st <= t:
+                p.error(f"--tile-stride-{axis} {st} must be from 8 to --tile-{flag} {t}")
+            if total < t:
+                p.error(f"--{flag} {total} is less than --tile-{flag} {t}: the total must be at least one tile; "
+                        f"the nearest legal totals are {t} and {t + st}")
+            if (total - t) % st:
+                lo, hi = tile_plan.legal_totals(total // 8, t // 8, st // 8)
+                p.error(f"--{flag} {total} is not --tile-{flag} {t} plus a whole number of strides of {st}: "
+                        f"the nearest legal totals are {8 * lo} and {8 * hi}")
     return args
+
+
+def tile_arguments(args) -> dict:
+    """``tile_size`` / ``tile_stride`` / ``tile_weights`` of ``StableVideoUNet`` in latent cells; empty without tiles."""
+    if args.tile_height is None:
+        return {}
+    return dict(tile_size=(args.tile_height // 8, args.tile_width // 8),
+                tile_stride=(args.tile_stride_y // 8, args.tile_stride_x // 8), tile_weights=args.tile_weights)
 
 
 def sample_output_path(path: str, index: int, num_samples: int) -> str:
@@ -166,7 +211,7 @@ def _build_engines(args, timesteps, device):
         vcfg = VAEDecoderConfig.tiny(64) if args.tiny else VAEDecoderConfig.svd()
         model = StableVideoUNet.from_random_init(timesteps, config=ucfg, seed=args.seed, device=device, sampler=args.sampler,
                                                  window_stride=args.window_stride, window_weights=args.window_weights,
-                                                 eta=args.eta, s_noise=args.s_noise)
+                                                 eta=args.eta, s_noise=args.s_noise, **tile_arguments(args))
         clip = CLIPVisionHIP(spec, clip_random_state_dict(spec, seed=args.seed + 1, device=device), device)
         enc = ImageEncoderHIP(vcfg, random_encoder_state_dict(vcfg, seed=args.seed + 2, device=device), device)
         return model, clip, enc, lambda: TemporalDecoderHIP(vcfg, random_state_dict(vcfg, seed=args.seed + 3, device=device),
@@ -175,7 +220,7 @@ def _build_engines(args, timesteps, device):
 
     model = StableVideoUNet.from_pretrained(args.model_id, timesteps=timesteps, device=device, sampler=args.sampler,
                                             window_stride=args.window_stride, window_weights=args.window_weights,
-                                            eta=args.eta, s_noise=args.s_noise)
+                                            eta=args.eta, s_noise=args.s_noise, **tile_arguments(args))
     clip, enc, dec = load_edge_engines(args.model_id, device)
     return model, clip, enc, lambda: dec
 
@@ -227,6 +272,11 @@ def main(argv=None) -> None:
 
                 shape = torch.Size(window_plan.noise_shape(1, args.num_frames, args.height, args.width, args.window_frames,
                                                            args.window_stride))
+            elif args.tile_height is not None:
+                from ..models import tile_plan
+
+                shape = torch.Size(tile_plan.noise_shape(1, args.num_frames, args.height, args.width, args.tile_height,
+                                                         args.tile_width, args.tile_stride_y, args.tile_stride_x))
             else:
                 shape = torch.Size((1, 4, args.num_frames, args.height // 8, args.width // 8))
             # what a stage boundary carries: the sample, and with dpmpp_2m the solver's history behind it (8 channels)
