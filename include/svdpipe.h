@@ -468,6 +468,13 @@ int sp_softmax_rows_f16(void *x, int64_t ld, int64_t rows, int cols, void *strea
 int sp_gemm_f32out_f16(const void *a, int64_t lda, const void *w, void *d, int m, int n, int k, const void *zero_page,
                        void *stream);
 int sp_softmax_rows_f32(const float *x, int64_t ld, void *out, int64_t ldo, int64_t rows, int cols, float scale, void *stream);
+/* sp_softmax_rows_f32 for rows of any length: the same arguments and the same contract (fp32 statistics, nothing clamped, a
+ * NaN stays a NaN, out may be x itself with ldo = 2*ld), with `cols` a multiple of 4 from 4 to 16,777,216 (2^24).  The row
+ * is not held in registers but streamed three times (maximum, sum, store) in pieces of 256 x 4 logits, with the register
+ * kernel's assignment of elements to threads and its order of accumulation and reduction: for cols <= 16,384 it returns the
+ * bytes of sp_softmax_rows_f32.  Frames of more than 16,384 cells in the VAE's mid-block attention (models/vae_hip.py). */
+int sp_softmax_rows_long_f32(const float *x, int64_t ld, void *out, int64_t ldo, int64_t rows, int cols, float scale,
+                             void *stream);
 /* Both ends of one decoder call work on `n` consecutive entries g = flat0 .. flat0+n-1 of the flattened (batch, frame)
  * list of a video tensor with F frames per batch item (generate_video_demo.py:162-181 cuts that flat list into chunks
  * of decode_chunk_size); entry g is batch item g / F, frame g % F, and element (g, channel c, pixel p) of the tensor

@@ -6,6 +6,9 @@
 //                         512-wide attention (scores come out of sp_gemm_f16 already scaled by 1/sqrt(C)).  One
 //                         workgroup per row, the row lives in registers (packed fp16), fp32 statistics.  HBM-bound:
 //                         one read + one write of the matrix.
+//   softmax_rows_f32_kernel      : the same from fp32 logits to fp16 probabilities, optionally over the front of the logits' rows.
+//   softmax_rows_long_f32_kernel : that for rows beyond 16,384 columns: the row streamed three times instead of held in
+//                         registers, the same bytes where both apply (frames of more than 16,384 cells).
 //   pack_latent_kernel  : a chunk of latent frames / scaling_factor -> channels-last rows (the decoder's input).
 //   frames_out_kernel   : time_conv_out -- Conv3d(3 -> 3, kernel (3,1,1), zero padding in time) -- on the channels-last
 //                         rows conv_out wrote, stored straight into the video tensor the caller returns.  HBM-bound.
@@ -70,6 +73,74 @@ __global__ __launch_bounds__(256) void softmax_rows_f32_kernel(const float *__re
     if (o < oc) {
       const f16x4 w = {(f16)(v[i][0] * inv), (f16)(v[i][1] * inv), (f16)(v[i][2] * inv), (f16)(v[i][3] * inv)};
       *(f16x4 *)(orow + o * 4) = w;
+    }
+  }
+}
+
+// The same softmax for rows too long for registers: the row is streamed three times in pieces of 256 x 4 logits (the
+// maximum, the sum of the exponentials, the exponentials again, scaled and stored); the second and third reads find the row
+// in L2 / MALL.  Thread `tid` owns pieces o = tid + i*256, i ascending, and accumulates in that order, and the wave and
+// four-wave reductions are the register kernel's: for cols <= 16,384 the bytes are those of softmax_rows_f32_kernel (the
+// third pass recomputes exp2(fma(x, scale_log2e, nm)) from the same operands, so it gets the value the sum saw).
+// x and out are not __restrict__: they may be the same memory.
+//
+// In place (out == x, ldo == 2*ld): the four probabilities of piece o take 8 bytes at byte 8*o of the row, the second or
+// first half of logit piece o/2.  The third pass works in groups of LONG_U iterations: every thread loads the group's pieces
+// into registers, the workgroup meets at a barrier, then every thread stores.  Group g holds logit pieces
+// [256*LONG_U*g, 256*LONG_U*(g+1)) and its stores land on logit pieces [128*LONG_U*g, 128*LONG_U*(g+1)).  For g = 0 those are
+// pieces of the group itself, which the barrier says every thread already holds in registers; for g >= 1,
+// 128*LONG_U*(g+1) <= 256*LONG_U*g, so they are pieces that earlier groups consumed.  No store reaches a piece of a later
+// group, so a thread that runs ahead into the next group's loads reads logits nobody has overwritten, and the first two
+// passes are over (the barriers of their reductions) before the first store.
+constexpr int LONG_U = 4;
+__global__ __launch_bounds__(256) void softmax_rows_long_f32_kernel(const float *x, int64_t ld, f16 *out, int64_t ldo, int cols,
+                                                                    float scale_log2e) {
+  __shared__ float red[8];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float *row = x + (int64_t)blockIdx.x * ld;
+  f16 *orow = out + (int64_t)blockIdx.x * ldo;
+  const int oc = cols >> 2;                       // 16-byte pieces of four logits
+  float mx = -3.0e38f;
+#pragma unroll 4
+  for (int o = tid; o < oc; o += 256) {
+    const f32x4 v = *(const f32x4 *)(row + (int64_t)o * 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) mx = fmaxf(mx, v[e]);
+  }
+  mx = wave_max(mx);
+  if (lane == 0) red[wave] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  const float nm = -mx * scale_log2e;
+  float s = 0.f;
+#pragma unroll 4
+  for (int o = tid; o < oc; o += 256) {
+    const f32x4 v = *(const f32x4 *)(row + (int64_t)o * 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) s += __builtin_amdgcn_exp2f(fmaf(v[e], scale_log2e, nm));
+  }
+  s = wave_sum(s);
+  if (lane == 0) red[4 + wave] = s;
+  __syncthreads();
+  const float inv = 1.0f / ((red[4] + red[5]) + (red[6] + red[7]));     // fixed order: deterministic
+  for (int o0 = tid; o0 < oc + tid; o0 += 256 * LONG_U) {               // (o0 - tid < oc: the same trip count in every thread)
+    f32x4 v[LONG_U];
+#pragma unroll
+    for (int u = 0; u < LONG_U; ++u) {
+      const int o = o0 + u * 256;
+      if (o < oc) v[u] = *(const f32x4 *)(row + (int64_t)o * 4);
+    }
+    __syncthreads();                             // every thread holds the group's logits: see the in-place argument above
+#pragma unroll
+    for (int u = 0; u < LONG_U; ++u) {
+      const int o = o0 + u * 256;
+      if (o < oc) {
+        f32x4 t;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) t[e] = __builtin_amdgcn_exp2f(fmaf(v[u][e], scale_log2e, nm));
+        const f16x4 w = {(f16)(t[0] * inv), (f16)(t[1] * inv), (f16)(t[2] * inv), (f16)(t[3] * inv)};
+        *(f16x4 *)(orow + (int64_t)o * 4) = w;
+      }
     }
   }
 }
@@ -279,6 +350,23 @@ extern "C" int sp_softmax_rows_f32(const float *x, int64_t ld, void *out, int64_
   else
     hipLaunchKernelGGL(softmax_rows_f32_kernel<16>, dim3((unsigned)rows), dim3(256), 0, s, x, ld, (f16 *)out, ldo, cols, sl);
   SP_CHECK_LAUNCH("sp_softmax_rows_f32");
+  return SP_OK;
+}
+
+extern "C" int sp_softmax_rows_long_f32(const float *x, int64_t ld, void *out, int64_t ldo, int64_t rows, int cols, float scale,
+                                        void *stream) {
+  SP_REQUIRE(x && out, "sp_softmax_rows_long_f32: null pointer");
+  SP_REQUIRE(rows > 0 && rows <= 0x7fffffff && cols >= 4 && cols % 4 == 0 && cols <= (1 << 24) && ld >= cols && ld % 4 == 0 &&
+                 ldo >= cols && ldo % 4 == 0,
+             "sp_softmax_rows_long_f32: rows=%lld cols=%d ld=%lld ldo=%lld unsupported (cols a multiple of 4, <= 16777216)",
+             (long long)rows, cols, (long long)ld, (long long)ldo);
+  // in place = the probabilities of row r overwrite the front of row r's logits: rows must not overlap other rows' logits
+  SP_REQUIRE((const void *)x != (const void *)out || ldo == 2 * ld,
+             "sp_softmax_rows_long_f32: in place needs ldo == 2 * ld (fp16 row pitch in halves = fp32 row pitch in bytes / 2)");
+  SP_CLEAR_STALE_ERROR();
+  hipLaunchKernelGGL(softmax_rows_long_f32_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, x, ld, (f16 *)out,
+                     ldo, cols, scale * 1.4426950408889634f);
+  SP_CHECK_LAUNCH("sp_softmax_rows_long_f32");
   return SP_OK;
 }
 

@@ -107,6 +107,7 @@ SIGNATURES = {
     "sp_softmax_rows_f16": (_I, [_P, _L, _L, _I, _P]),
     "sp_gemm_f32out_f16": (_I, [_P, _L, _P, _P, _I, _I, _I, _P, _P]),
     "sp_softmax_rows_f32": (_I, [_P, _L, _P, _L, _L, _I, _F, _P]),
+    "sp_softmax_rows_long_f32": (_I, [_P, _L, _P, _L, _L, _I, _F, _P]),
     "sp_vae_pack_latent_f16": (_I, [_P, _P, _F, _L, _I, _I, _L, _L, _L, _I, _I, _I, _P]),
     "sp_vae_frames_out_f16": (_I, [_P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _L, _I, _L, _L, _L, _P]),
     "sp_vae_frames_out_u8": (_I, [_P, _L, _P, _P, _P, _I, _I, _I, _I, _L, _P]),

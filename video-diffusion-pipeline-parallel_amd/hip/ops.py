@@ -394,6 +394,19 @@ def softmax_rows_f32(x32, out16, *, rows, cols, scale=1.0, ld=None, ldo=None):
     return out16
 
 
+def softmax_rows_long_f32(x32, out16, *, rows, cols, scale=1.0, ld=None, ldo=None):
+    """``softmax_rows_f32`` for rows of any length (``sp_softmax_rows_long_f32``): the row is streamed, not held in registers,
+    so ``cols`` goes up to 2^24; up to 16,384 columns the bytes are ``softmax_rows_f32``'s.  In place as there."""
+    ld = int(ld if ld is not None else x32.stride(0))
+    ldo = int(ldo if ldo is not None else out16.stride(0))
+    if x32.dtype != torch.float32 or not x32.is_cuda or out16.dtype != torch.float16 or not out16.is_cuda:
+        raise TypeError("x32 must be float32 and out16 float16, both on a HIP device")
+    with _Timed("softmax_rows", 0.0, (3 * 4.0 + 2.0) * rows * cols):
+        _check(load().sp_softmax_rows_long_f32(x32.data_ptr(), ld, out16.data_ptr(), ldo, rows, cols, float(scale), _stream()),
+               "sp_softmax_rows_long_f32")
+    return out16
+
+
 def video_strides(t, layout):
     """(sb, sc, sf) element strides of a contiguous video tensor: "bcfhw" = (B,C,F,H,W), "nchw" = (B*F,C,H,W)."""
     if layout == "bcfhw":

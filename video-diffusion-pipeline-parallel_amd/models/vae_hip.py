@@ -20,7 +20,9 @@ score matrix of one frame (170 MB at 9,216 tokens) is the only large scratch and
 Since round 5 the logits stay fp32 into the softmax wherever a frame has a multiple of 256 tokens
 (``sp_gemm_f32out_f16`` + ``sp_softmax_rows_f32``, the probabilities overwrite the front of each row's logits), so that
 trained weights whose logits exceed fp16's range or precision are handled the way the reference's fp32 upcast handles them;
-other token counts keep fp16 scores with a saturating softmax.
+other token counts keep fp16 scores with a saturating softmax.  Frames of more than 16,384 tokens (a multiple of 256) run the
+fp32 composition over blocks of query rows with a softmax that streams its rows (``sp_softmax_rows_long_f32``): the scratch
+is ``[R][tokens]``, never more than the native decode's matrix (``attn_row_blocks``).
 
 Precision: fp16 storage / fp32 accumulation throughout.  The reference upcasts this VAE to fp32
 (``force_upcast``, ``generate_video_demo.py:171-175``) because fp16 activations of the trained decoder can overflow;
@@ -188,6 +190,22 @@ def random_encoder_state_dict(cfg: VAEDecoderConfig, seed: int = 0, device="cpu"
 
 
 # ---------------------------------------------------------------------------------------------- engine
+ATTN_LONG_FROM = 16384                  # tokens per frame that sp_softmax_rows_f32 / _f16 hold in registers
+ATTN_SCRATCH_ELEMS = 9216 * 9216        # the [tokens][tokens] fp32 matrix of the native 576 x 1024 decode (340 MB)
+MAX_ROWS = 0x7fffffff                   # the contraction kernels count the rows of an activation in an int
+
+
+def attn_row_blocks(hw: int, cap_elems: int = ATTN_SCRATCH_ELEMS):
+    """Query-row blocks of the mid-block attention above ``ATTN_LONG_FROM`` tokens: ``(R, [(r0, r1), ...])``.  ``R`` is the
+    largest multiple of 256 with ``R * hw <= cap_elems`` (the fp32 score scratch is ``[R][hw]``), at least 256 even where
+    that exceeds the cap and at most ``hw`` rounded up to 256; the blocks ``[r0, r1)`` are consecutive, ``R`` rows each but
+    the last, and cover rows 0 .. hw-1 exactly once, in order."""
+    if hw <= 0 or cap_elems <= 0:
+        raise ValueError(f"attn_row_blocks: hw={hw} and cap_elems={cap_elems} must be positive")
+    r = max(256, min(cap_elems // hw // 256, (hw + 255) // 256) * 256)
+    return r, [(r0, min(r0 + r, hw)) for r0 in range(0, hw, r)]
+
+
 class _VAEKernels:
     """Kernel helpers shared by the decoder and the encoder engines."""
 
@@ -201,6 +219,10 @@ class _VAEKernels:
         # selects the round-3 composition with fp16 scores everywhere (A/B, tests)
         self.fp32_scores = __import__("os").environ.get("VDPP_VAE_FP16_SCORES") != "1"
         self.gn_from_epilogue = __import__("os").environ.get("VDPP_GN_EPILOGUE", "1") != "0"
+        # frames of more tokens than this take the row-blocked attention with the streaming softmax (_run_attn);
+        # VDPP_VAE_LONG_ATTN_FROM=0 sends every frame there (A/B, tests), attn_scratch_elems caps its fp32 score scratch
+        self.attn_long_from = int(__import__("os").environ.get("VDPP_VAE_LONG_ATTN_FROM", ATTN_LONG_FROM))
+        self.attn_scratch_elems = ATTN_SCRATCH_ELEMS
         return dev
 
     def _attn(self, sd, p, c):
@@ -250,18 +272,44 @@ class _VAEKernels:
                       silu=silu, ws=ws)
         return y
 
+    def _check_tokens(self, hw):
+        """The token counts the mid-block attention takes, checked before anything is launched."""
+        if hw % 64:
+            raise ValueError(f"mid-block attention: H*W = {hw} tokens per image must be a multiple of 64")
+        if hw > self.attn_long_from and hw % 256:
+            raise ValueError(f"mid-block attention: H*W = {hw} tokens per image: frames above {ATTN_LONG_FROM:,} cells need "
+                             f"(H/8)*(W/8) to be a multiple of 256 (the fp32 logits leave the contraction in 256-column "
+                             f"tiles)")
+
     def _run_attn(self, p, x: _Act, n_img, hw) -> _Act:
         """diffusers ``Attention(heads=1, dim_head=C, norm_num_groups=32, residual_connection=True)`` per image."""
         c, m = p["c"], n_img * hw
-        if hw % 64:
-            raise ValueError(f"mid-block attention: H*W = {hw} tokens per image must be a multiple of 64")
+        self._check_tokens(hw)
         t = self._gn(p["norm"], x, n_img, hw, False)
         q = self._gemm(p["q"], t, m).t
         k = self._gemm(p["k"], t, m).t
         o = self._buf(m, c)
         vt = self._buf(c, hw)
         scale = 1.0 / math.sqrt(c)
-        if hw % 256 == 0 and c % 64 == 0 and self.fp32_scores:
+        if hw > self.attn_long_from:
+            # Frames beyond what the register softmax holds (16,384 tokens): the same fp32-logit composition over blocks of R
+            # query rows, so that the score scratch is [R][tokens] (at most attn_scratch_elems, whatever the frame) and the
+            # softmax streams its rows (sp_softmax_rows_long_f32, in place like the register kernel).  A query row's output
+            # depends on no other query row: the blocks compute what one [tokens][tokens] pass would.  (fp32 logits whatever
+            # fp32_scores says: the fp16-score softmax holds its row in registers too and stops at 16,384 columns.)
+            rows_max, blocks = attn_row_blocks(hw, self.attn_scratch_elems)
+            scores32 = torch.empty((rows_max, hw), dtype=torch.float32, device=self.device)
+            probs = scores32.view(torch.float16)                                          # [R][2*hw] halves, same memory
+            for i in range(n_img):
+                r = slice(i * hw, (i + 1) * hw)
+                ops.gemm(p["wv"], t[r], vt, m=c, n=hw, cin=c)                             # V^T = W_v X^T   [C][tokens]
+                for r0, r1 in blocks:
+                    b, nr = slice(i * hw + r0, i * hw + r1), r1 - r0
+                    ops.gemm_f32out(q[b], k[r], scores32, m=nr, n=hw, k=c)                # S = Q[block] K^T (fp32)
+                    ops.softmax_rows_long_f32(scores32, probs, rows=nr, cols=hw, scale=scale, ld=hw, ldo=2 * hw)
+                    ops.gemm(probs[:nr, :hw], vt, o[b], m=nr, n=c, cin=hw, lda=2 * hw, bias=p["bv"])   # O[block] = P V + b_v
+            del scores32, probs
+        elif hw % 256 == 0 and c % 64 == 0 and self.fp32_scores:
             # Logits in fp32 all the way into the softmax (round 5; the reference runs this VAE in fp32 because trained
             # weights overflow fp16, generate_video_demo.py:171-175): Q K^T leaves the contraction as raw fp32 sums, the
             # softmax scales, normalises and writes the fp16 probabilities over the front of each row's logits, and the
@@ -390,6 +438,7 @@ class TemporalDecoderHIP(_VAEKernels):
         if z.dtype != torch.float16 or z.device != self.device or not z.is_contiguous():
             raise TypeError("decode expects a contiguous float16 tensor on this decoder's device")
         bf, c, h, w = z.shape
+        self._check_call_size(bf, h, w, "decode")
         out = torch.empty((bf, 3, 8 * h, 8 * w), dtype=torch.float16, device=self.device)
         hw, ohw = h * w, 64 * h * w
         self._decode_chunk(z, (num_frames * c * hw, hw, c * hw), out, (num_frames * 3 * ohw, ohw, 3 * ohw), flat0=0, n=bf,
@@ -438,6 +487,21 @@ class TemporalDecoderHIP(_VAEKernels):
             raise ValueError("decode_chunk_size must be positive")
         if latents.dtype != torch.float16 or latents.device != self.device or not latents.is_contiguous():
             raise TypeError("decode_latents expects a contiguous float16 tensor on this decoder's device")
+        b, _, f, h, w = latents.shape
+        self._check_call_size(min(decode_chunk_size, b * f), h, w, "decode_latents")
+
+    def _check_call_size(self, n, h, w, what):
+        """One decoder call on ``n`` latent frames of h x w cells, refused before anything is launched where a kernel could
+        not address it.  Every kernel of a call forms addresses in 64 bits (gemm_ps.hip's 32-bit buffer offsets are kept
+        to tensors below 2^31 bytes by its own route check), so tensors beyond 2^32 bytes are fine; what is 32 bits wide is
+        the ROW index of the contraction kernels (``sp_gemm_desc.m``), and the last level has n * 64*h*w rows.  The chunk
+        size is the reference's semantics (the temporal layers see one chunk at a time), so it is never changed here."""
+        self._check_tokens(h * w)
+        if n * 64 * h * w > MAX_ROWS:
+            fit = MAX_ROWS // (64 * h * w)
+            raise ValueError(f"{what}: {n} frames of {8 * h} x {8 * w} pixels per decoder call are {n * 64 * h * w:,} rows at "
+                             f"the last level, more than the contraction kernels count (2^31 - 1); the largest "
+                             f"decode_chunk_size that fits is {fit}" + ("" if fit else " (not even one frame fits)"))
 
     def _decode_chunks(self, latents, out, out_strides, decode_chunk_size):
         """The reference's chunk walk over the flattened (B, F) list (ref :178-184), one decoder call per chunk."""
@@ -523,6 +587,11 @@ class ImageEncoderHIP(_VAEKernels):
             raise ValueError(f"image height/width must be multiples of {f}, num_frames positive")
         if ((h // f) * (w // f)) % 64:
             raise ValueError("mid-block attention: (H/8)*(W/8) tokens must be a multiple of 64")
+        self._check_tokens((h // f) * (w // f))
+        if n * h * w > MAX_ROWS:
+            raise ValueError(f"encode_image_latents: {n} images of {h} x {w} pixels are {n * h * w:,} rows at the first level, "
+                             f"more than the contraction kernels count (2^31 - 1); encode at most {MAX_ROWS // (h * w)} "
+                             f"images per call")
         rows = self._buf(n * h * w, self.conv_in.cin)
         ops.vae_image_pack(image, rows, batch=n, h=h, w=w, cpad=self.conv_in.cin, flip=True)
         x = self._gemm(self.conv_in, rows, n * h * w, conv=(n, h, w, h, w, 1, 0))
