@@ -487,6 +487,23 @@ def test_one_tile_equals_the_untiled_model_bit_for_bit(sampler):
             assert torch.equal(tiled(state, step), plain(state, step)), f"guidance {guidance}, step {step}"
 
 
+@pytest.mark.parametrize("sampler", ["euler", "dpmpp_2m", "euler_a", "dpmpp_2m_sde"])
+def test_whole_frame_tile_equals_the_windowed_model_bit_for_bit(sampler):
+    """``window_stride`` with ``tile_size = tile_stride`` = the frame is the windowed model: three windows of 4 frames in a
+    latent of 6, one tile each; the tiles tail and the crops that are the whole frame give the bytes of the windows tail (with
+    noise: of the stochastic entries with the window table), two videos, guided per video and not, at steps 0 and 7."""
+    window, ft, h, w = 4, 6, 8, 16
+    windowed, tiled = _model(sampler, window_stride=2), _model(sampler, window_stride=2, tile_size=(h, w), tile_stride=(h, w))
+    g, emb, img = _conditioning(window, h, w, nb=2)
+    for guidance in (None, [3.0, 1.5]):
+        cond = windowed.prepare_conditioning(emb, img, guidance_scale=guidance, num_frames=window, noise_seed=[5, 6])
+        for step in (0, 7):
+            state = _state(windowed, g, 2, ft, h, w)
+            want = windowed(state, step, conditioning=cond)
+            assert torch.isfinite(want).all()
+            assert torch.equal(tiled(state, step, conditioning=cond), want), f"guidance {guidance}, step {step}"
+
+
 def test_tile_arguments_and_error_texts():
     from vdpp_amd.models.svd_unet import StableVideoUNet
     hip = _engine()

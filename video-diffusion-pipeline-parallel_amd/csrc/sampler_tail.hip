@@ -195,106 +195,111 @@ void launch(const Tail &t, void *stream) {
   else launch_form<MODE, false>(t, stream);
 }
 
-// Everything all entry points refuse; on success fills the call (but for the step's own constants in t->k).  `windows`: the
-// entry takes a plan and a weight table; the others give the plan of one window that is the whole latent, and no weights.
-int check(const char *name, const void *state, const void *eps_cond, const void *eps_uncond, int64_t ld_eps,
-          const float *guidance, int64_t ld_guidance, void *out, float sigma, int channels, int batch, int frames_total, int h,
-          int w, bool windows, int window, int stride, int n_win, const float *weights, Tail *t) {
+// The plan of an entry that takes none: the frame windows with their table `wf`, and one tile that is the whole frame.  No
+// table is one set of eps rows, which check() holds to one window that is the whole latent; its stride is then the window.
+sp_tile_plan frame_plan(int frames_total, int h, int w, int window, int stride, int n_win, const float *wf) {
+  return sp_tile_plan{frames_total, window, wf ? stride : window, n_win, h, w, h, w, h, w, 1, 1, wf, nullptr, nullptr};
+}
+
+struct Noise {
+  float scale;
+  const uint64_t *seeds;
+  uint32_t step;
+};
+
+// Everything the entry points refuse; on success fills the call (but for the step's own constants in t->k).  `tables`: the
+// weight tables the entry's form takes, 0 (one set of eps rows), 1 (frame windows: wf) or 3 (tiles: wf, wy, wx).  `noise`:
+// the noise arguments of an entry that has them.
+int check(const char *name, const sp_tile_plan *pl, int tables, const void *state, const void *eps_cond, const void *eps_uncond,
+          int64_t ld_eps, const float *guidance, int64_t ld_guidance, void *out, float sigma, int channels, int batch,
+          const Noise *noise, Tail *t) {
+  SP_REQUIRE(pl, "%s: null plan", name);
+  SP_REQUIRE(tables < 3 || (pl->wf && pl->wy && pl->wx),
+             "%s: null table (the plan's normalised wf [n_win][window], wy [n_ty][tile_h], wx [n_tx][tile_w])", name);
   SP_REQUIRE(state && eps_cond && out, "%s: null pointer", name);
-  SP_REQUIRE(!windows || weights, "%s: null weights (the normalised [n_win][window] table of the window plan)", name);
+  SP_REQUIRE(pl->wf || (tables == 0 && pl->n_win == 1 && pl->window == pl->frames_total),
+             "%s: null weights (the normalised [n_win][window] table of the window plan)", name);
   SP_REQUIRE(!eps_uncond || guidance, "%s: CFG needs a guidance vector", name);
   SP_REQUIRE(ld_eps >= 4 && ld_eps % 4 == 0, "%s: ld_eps must be a multiple of 4", name);
-  SP_REQUIRE(batch > 0 && frames_total > 0 && window > 0 && h > 0 && w > 0, "%s: dims must be positive", name);
-  SP_REQUIRE(window <= frames_total, "%s: window=%d exceeds frames_total=%d", name, window, frames_total);
-  SP_REQUIRE(stride >= 1 && stride <= window, "%s: stride=%d must be from 1 to window (%d)", name, stride, window);
-  SP_REQUIRE((frames_total - window) % stride == 0,
-             "%s: frames_total=%d is not window (%d) plus a whole number of strides (%d)", name, frames_total, window, stride);
-  SP_REQUIRE(n_win == (frames_total - window) / stride + 1, "%s: n_win=%d, the plan of (%d, %d, %d) has %d windows", name,
-             n_win, frames_total, window, stride, (frames_total - window) / stride + 1);
-  SP_REQUIRE(ld_guidance == 0 || ld_guidance >= window,
-             "%s: ld_guidance=%lld must be 0 (one shared row) or >= the frames of a window (%d)", name, (long long)ld_guidance, window);
+  SP_REQUIRE(batch > 0 && pl->frames_total > 0 && pl->window > 0 && pl->h > 0 && pl->w > 0 && pl->tile_h > 0 && pl->tile_w > 0,
+             "%s: dims must be positive", name);
+  // per axis the same rule: 1 <= stride <= tile <= total, the total the tile plus whole strides, n the count that gives
+  // (the frames axis is named without the word "stride", so that only the refusals about its stride carry it)
+  char frames[64], y[80], x[80];
+  snprintf(frames, sizeof(frames), "frames_total=%d, window=%d", pl->frames_total, pl->window);
+  snprintf(y, sizeof(y), "y (total, tile, stride) = (%d, %d, %d)", pl->h, pl->tile_h, pl->stride_y);
+  snprintf(x, sizeof(x), "x (total, tile, stride) = (%d, %d, %d)", pl->w, pl->tile_w, pl->stride_x);
+  const struct { const char *axis, *tile, *stride, *count; int total, t, s, n; } axes[3] = {
+      {frames, "window", "stride", "n_win", pl->frames_total, pl->window, pl->stride, pl->n_win},
+      {y, "tile", "stride_y", "n_ty", pl->h, pl->tile_h, pl->stride_y, pl->n_ty},
+      {x, "tile", "stride_x", "n_tx", pl->w, pl->tile_w, pl->stride_x, pl->n_tx}};
+  for (const auto &a : axes) {
+    const char *axis = a.axis;
+    SP_REQUIRE(a.t <= a.total, "%s: %s: the %s exceeds the total", name, axis, a.tile);
+    SP_REQUIRE(a.s >= 1 && a.s <= a.t, "%s: %s: stride must be from 1 to the %s (%s=%d)", name, axis, a.tile, a.stride, a.s);
+    SP_REQUIRE((a.total - a.t) % a.s == 0, "%s: %s: the total is not the %s plus a whole number of strides (%s=%d)", name, axis,
+               a.tile, a.stride, a.s);
+    SP_REQUIRE(a.n == (a.total - a.t) / a.s + 1, "%s: %s=%d, the plan of %s, %d apart, has %d %ss", name, a.count, a.n, axis, a.s,
+               (a.total - a.t) / a.s + 1, a.tile);
+  }
+  SP_REQUIRE(ld_guidance == 0 || ld_guidance >= pl->window,
+             "%s: ld_guidance=%lld must be 0 (one shared row) or >= the frames of a window (%d)", name, (long long)ld_guidance,
+             pl->window);
   SP_REQUIRE(sigma > 0.f, "%s: sigma must be positive", name);
-  const int64_t hw = (int64_t)h * w;
-  const int64_t bytes = (int64_t)batch * frames_total * hw * channels * (int64_t)sizeof(f16);
+  const int64_t hw = (int64_t)pl->h * pl->w;
+  const int64_t bytes = (int64_t)batch * pl->frames_total * hw * channels * (int64_t)sizeof(f16);
   const uintptr_t s0 = (uintptr_t)state, o0 = (uintptr_t)out;
   SP_REQUIRE(s0 == o0 || s0 + (uintptr_t)bytes <= o0 || o0 + (uintptr_t)bytes <= s0,
              "%s: out must be the input itself or not overlap it", name);
   const float s2 = sigma * sigma + 1.0f;
-  *t = Tail{name, (const f16 *)state, (const f16 *)eps_cond, (const f16 *)eps_uncond, guidance, weights, ld_eps, ld_guidance, hw,
-            (f16 *)out, SamplerCoef{-sigma / sqrtf(s2), 1.0f / s2}, WindowPlan{frames_total, window, stride, n_win, batch}, TileGeom{},
-            // four pixels per thread where every plane access stays 8-byte aligned
-            hw % 4 == 0 && s0 % 8 == 0 && o0 % 8 == 0, nullptr, 0u};
+  // four pixels per thread where every plane access stays 8-byte aligned and the four share a row, their covering tiles and
+  // adjacent eps rows inside every tile; one tile that is the whole frame has the frame's pixels in order, across rows too
+  const bool wide = hw % 4 == 0 && s0 % 8 == 0 && o0 % 8 == 0 &&
+                    ((pl->w % 4 == 0 && pl->tile_w % 4 == 0 && pl->stride_x % 4 == 0) || (pl->n_ty == 1 && pl->n_tx == 1));
+  *t = Tail{name, (const f16 *)state, (const f16 *)eps_cond, (const f16 *)eps_uncond, guidance, pl->wf, ld_eps, ld_guidance, hw,
+            (f16 *)out, SamplerCoef{-sigma / sqrtf(s2), 1.0f / s2},
+            WindowPlan{pl->frames_total, pl->window, pl->stride, pl->n_win, batch},
+            TileGeom{pl->w, pl->tile_h, pl->tile_w, pl->stride_y, pl->stride_x, pl->n_ty, pl->n_tx, pl->wy, pl->wx}, wide, nullptr, 0u};
+  if (!noise) return SP_OK;
+  SP_REQUIRE(noise->scale >= 0.f && noise->scale <= 3.402823466e38f, "%s: noise_scale = %g must be finite and not negative", name,
+             (double)noise->scale);
+  SP_REQUIRE(noise->scale == 0.f || noise->seeds, "%s: null seeds with noise_scale = %g (one 64-bit seed per video, on the device)",
+             name, (double)noise->scale);
+  SP_REQUIRE((uintptr_t)noise->seeds % 8 == 0, "%s: seeds must be 8-byte aligned", name);
+  SP_REQUIRE(noise_fits(pl->frames_total, hw), "%s: 4*frames_total*h*w = 4*%d*%lld exceeds 2^34, the noise address' range", name,
+             pl->frames_total, (long long)hw);
+  t->k.n = noise->scale; t->seeds = noise->seeds; t->step = noise->step;
   return SP_OK;
 }
 
-// The stochastic entries: check() with the unwindowed form spelled as weights == NULL, n_win == 1, window == frames_total,
-// then the noise arguments.
-int check_noise(const char *name, const void *state, const void *eps_cond, const void *eps_uncond, int64_t ld_eps,
-                const float *guidance, int64_t ld_guidance, void *out, float sigma, int channels, int batch, int frames_total,
-                int h, int w, int window, int stride, int n_win, const float *weights, float noise_scale,
-                const uint64_t *seeds, uint32_t step, Tail *t) {
-  const bool whole = !weights && n_win == 1 && window == frames_total;
-  if (int rc = check(name, state, eps_cond, eps_uncond, ld_eps, guidance, ld_guidance, out, sigma, channels, batch, frames_total,
-                     h, w, !whole, window, whole ? window : stride, n_win, weights, t))
+// The two updates behind check(): the Euler step to sigma_next (Euler ancestral: to sigma_down) and the 2M step.
+int euler_tail(const char *name, const sp_tile_plan *pl, int tables, const void *latent, const void *eps_cond,
+               const void *eps_uncond, int64_t ld_eps, const float *guidance, int64_t ld_guidance, void *out, float sigma,
+               float sigma_next, int batch, const Noise *noise, void *stream) {
+  Tail t;
+  if (int rc = check(name, pl, tables, latent, eps_cond, eps_uncond, ld_eps, guidance, ld_guidance, out, sigma, 4, batch, noise, &t))
     return rc;
-  SP_REQUIRE(noise_scale >= 0.f && noise_scale <= 3.402823466e38f, "%s: noise_scale = %g must be finite and not negative", name,
-             (double)noise_scale);
-  SP_REQUIRE(noise_scale == 0.f || seeds, "%s: null seeds with noise_scale = %g (one 64-bit seed per video, on the device)",
-             name, (double)noise_scale);
-  SP_REQUIRE((uintptr_t)seeds % 8 == 0, "%s: seeds must be 8-byte aligned", name);
-  SP_REQUIRE(noise_fits(frames_total, t->hw), "%s: 4*frames_total*h*w = 4*%d*%lld exceeds 2^34, the noise address' range", name,
-             frames_total, (long long)t->hw);
-  t->k.n = noise_scale; t->seeds = seeds; t->step = step;
-  return SP_OK;
-}
-
-// The tiles entries: the plan record, its two space triples, then check_noise() on the frame triple and everything else.
-int check_tiles(const char *name, const sp_tile_plan *pl, const void *state, const void *eps_cond, const void *eps_uncond,
-                int64_t ld_eps, const float *guidance, int64_t ld_guidance, void *out, float sigma, int channels, int batch,
-                float noise_scale, const uint64_t *seeds, uint32_t step, Tail *t) {
-  SP_REQUIRE(pl, "%s: null plan", name);
-  SP_REQUIRE(pl->wf && pl->wy && pl->wx, "%s: null table (the plan's normalised wf [n_win][window], wy [n_ty][tile_h], wx [n_tx][tile_w])",
-             name);
-  SP_REQUIRE(pl->h > 0 && pl->w > 0 && pl->tile_h > 0 && pl->tile_w > 0, "%s: dims must be positive", name);
-  const struct { const char *axis; int total, tile, stride, n; } ax[2] = {{"y", pl->h, pl->tile_h, pl->stride_y, pl->n_ty},
-                                                                          {"x", pl->w, pl->tile_w, pl->stride_x, pl->n_tx}};
-  for (const auto &a : ax) {
-    SP_REQUIRE(a.tile <= a.total, "%s: %s (total, tile, stride) = (%d, %d, %d): the tile exceeds the total", name, a.axis, a.total,
-               a.tile, a.stride);
-    SP_REQUIRE(a.stride >= 1 && a.stride <= a.tile, "%s: %s (total, tile, stride) = (%d, %d, %d): stride must be from 1 to the tile",
-               name, a.axis, a.total, a.tile, a.stride);
-    SP_REQUIRE((a.total - a.tile) % a.stride == 0,
-               "%s: %s (total, tile, stride) = (%d, %d, %d): the total is not the tile plus a whole number of strides", name, a.axis,
-               a.total, a.tile, a.stride);
-    SP_REQUIRE(a.n == (a.total - a.tile) / a.stride + 1, "%s: n_t%s=%d, the plan of %s (total, tile, stride) = (%d, %d, %d) has %d tiles",
-               name, a.axis, a.n, a.axis, a.total, a.tile, a.stride, (a.total - a.tile) / a.stride + 1);
-  }
-  if (int rc = check_noise(name, state, eps_cond, eps_uncond, ld_eps, guidance, ld_guidance, out, sigma, channels, batch,
-                           pl->frames_total, pl->h, pl->w, pl->window, pl->stride, pl->n_win, pl->wf, noise_scale, seeds, step, t))
-    return rc;
-  t->tg = TileGeom{pl->w, pl->tile_h, pl->tile_w, pl->stride_y, pl->stride_x, pl->n_ty, pl->n_tx, pl->wy, pl->wx};
-  // four pixels per thread where they also share a row, their covering tiles and adjacent eps rows inside every tile; one
-  // tile that is the whole frame keeps the form of the _windows_ functions, and with it their bytes
-  t->wide = t->wide && ((pl->w % 4 == 0 && pl->tile_w % 4 == 0 && pl->stride_x % 4 == 0) || (pl->n_ty == 1 && pl->n_tx == 1));
-  return SP_OK;
-}
-
-int euler_step(Tail &t, float sigma, float sigma_next, void *stream) {
   t.k.inv_sigma = 1.0f / sigma; t.k.dt = sigma_next - sigma;
   SP_CLEAR_STALE_ERROR();
   launch<EULER>(t, stream);
-  SP_CHECK_LAUNCH(t.name);
+  SP_CHECK_LAUNCH(name);
   return SP_OK;
 }
 
-int dpmpp2m_step(Tail &t, float a, float b, float c1, float c2, void *stream) {
-  SP_REQUIRE(a >= 0.f && a < 1.f, "%s: a = sigma'/sigma = %g must be in [0, 1)", t.name, (double)a);
-  SP_REQUIRE(c2 >= 0.f, "%s: c2 = %g must not be negative", t.name, (double)c2);
+int dpmpp2m_tail(const char *name, const sp_tile_plan *pl, int tables, const void *state, const void *eps_cond,
+                 const void *eps_uncond, int64_t ld_eps, const float *guidance, int64_t ld_guidance, void *out_state, float sigma,
+                 float a, float b, float c1, float c2, int batch, const Noise *noise, void *stream) {
+  Tail t;
+  if (int rc = check(name, pl, tables, state, eps_cond, eps_uncond, ld_eps, guidance, ld_guidance, out_state, sigma, 8, batch, noise,
+                     &t))
+    return rc;
+  SP_REQUIRE(a >= 0.f && a < 1.f, "%s: a = sigma'/sigma = %g must be in [0, 1)", name, (double)a);
+  SP_REQUIRE(c2 >= 0.f, "%s: c2 = %g must not be negative", name, (double)c2);
   t.k.a = a; t.k.b = b; t.k.c1 = c1; t.k.c2 = c2;
   SP_CLEAR_STALE_ERROR();
   if (c2 != 0.f) launch<SECOND_ORDER>(t, stream);
   else launch<FIRST_ORDER>(t, stream);
-  SP_CHECK_LAUNCH(t.name);
+  SP_CHECK_LAUNCH(name);
   return SP_OK;
 }
 
@@ -303,11 +308,9 @@ int dpmpp2m_step(Tail &t, float a, float b, float c1, float c2, void *stream) {
 extern "C" int sp_euler_step_rows_f16(const void *latent, const void *eps_cond, const void *eps_uncond, int64_t ld_eps,
                                       const float *guidance, int64_t ld_guidance, void *out, float sigma, float sigma_next,
                                       int b, int frames, int h, int w, void *stream) {
-  Tail t;
-  if (int rc = check("sp_euler_step_rows_f16", latent, eps_cond, eps_uncond, ld_eps, guidance, ld_guidance, out, sigma, 4, b, frames, h, w, false,
-                     frames, frames, 1, nullptr, &t))
-    return rc;
-  return euler_step(t, sigma, sigma_next, stream);
+  const sp_tile_plan pl = frame_plan(frames, h, w, frames, frames, 1, nullptr);
+  return euler_tail("sp_euler_step_rows_f16", &pl, 0, latent, eps_cond, eps_uncond, ld_eps, guidance, ld_guidance, out, sigma,
+                    sigma_next, b, nullptr, stream);
 }
 
 extern "C" int sp_euler_step_f16(const void *latent, const void *eps_cond, const void *eps_uncond, int64_t ld_eps,
@@ -320,33 +323,27 @@ extern "C" int sp_euler_step_f16(const void *latent, const void *eps_cond, const
 extern "C" int sp_dpmpp2m_step_rows_f16(const void *state, const void *eps_cond, const void *eps_uncond, int64_t ld_eps,
                                         const float *guidance, int64_t ld_guidance, void *out_state, float sigma, float a,
                                         float b, float c1, float c2, int batch, int frames, int h, int w, void *stream) {
-  Tail t;
-  if (int rc = check("sp_dpmpp2m_step_rows_f16", state, eps_cond, eps_uncond, ld_eps, guidance, ld_guidance, out_state, sigma, 8, batch, frames, h, w,
-                     false, frames, frames, 1, nullptr, &t))
-    return rc;
-  return dpmpp2m_step(t, a, b, c1, c2, stream);
+  const sp_tile_plan pl = frame_plan(frames, h, w, frames, frames, 1, nullptr);
+  return dpmpp2m_tail("sp_dpmpp2m_step_rows_f16", &pl, 0, state, eps_cond, eps_uncond, ld_eps, guidance, ld_guidance, out_state,
+                      sigma, a, b, c1, c2, batch, nullptr, stream);
 }
 
 extern "C" int sp_euler_step_windows_f16(const void *latent, const void *eps_cond, const void *eps_uncond, int64_t ld_eps,
                                          const float *guidance, int64_t ld_guidance, void *out, float sigma,
                                          float sigma_next, int b, int frames_total, int h, int w, int window, int stride,
                                          int n_win, const float *weights, void *stream) {
-  Tail t;
-  if (int rc = check("sp_euler_step_windows_f16", latent, eps_cond, eps_uncond, ld_eps, guidance, ld_guidance, out, sigma, 4, b, frames_total, h, w,
-                     true, window, stride, n_win, weights, &t))
-    return rc;
-  return euler_step(t, sigma, sigma_next, stream);
+  const sp_tile_plan pl = frame_plan(frames_total, h, w, window, stride, n_win, weights);
+  return euler_tail("sp_euler_step_windows_f16", &pl, 1, latent, eps_cond, eps_uncond, ld_eps, guidance, ld_guidance, out, sigma,
+                    sigma_next, b, nullptr, stream);
 }
 
 extern "C" int sp_dpmpp2m_step_windows_f16(const void *state, const void *eps_cond, const void *eps_uncond, int64_t ld_eps,
                                            const float *guidance, int64_t ld_guidance, void *out_state, float sigma, float a,
                                            float b, float c1, float c2, int batch, int frames_total, int h, int w, int window,
                                            int stride, int n_win, const float *weights, void *stream) {
-  Tail t;
-  if (int rc = check("sp_dpmpp2m_step_windows_f16", state, eps_cond, eps_uncond, ld_eps, guidance, ld_guidance, out_state, sigma, 8, batch, frames_total,
-                     h, w, true, window, stride, n_win, weights, &t))
-    return rc;
-  return dpmpp2m_step(t, a, b, c1, c2, stream);
+  const sp_tile_plan pl = frame_plan(frames_total, h, w, window, stride, n_win, weights);
+  return dpmpp2m_tail("sp_dpmpp2m_step_windows_f16", &pl, 1, state, eps_cond, eps_uncond, ld_eps, guidance, ld_guidance, out_state,
+                      sigma, a, b, c1, c2, batch, nullptr, stream);
 }
 
 extern "C" int sp_euler_ancestral_step_f16(const void *latent, const void *eps_cond, const void *eps_uncond, int64_t ld_eps,
@@ -354,11 +351,10 @@ extern "C" int sp_euler_ancestral_step_f16(const void *latent, const void *eps_c
                                            float sigma_down, int b, int frames_total, int h, int w, int window, int stride,
                                            int n_win, const float *weights, float noise_scale, const uint64_t *seeds,
                                            uint32_t step, void *stream) {
-  Tail t;
-  if (int rc = check_noise("sp_euler_ancestral_step_f16", latent, eps_cond, eps_uncond, ld_eps, guidance, ld_guidance, out, sigma, 4, b,
-                           frames_total, h, w, window, stride, n_win, weights, noise_scale, seeds, step, &t))
-    return rc;
-  return euler_step(t, sigma, sigma_down, stream);
+  const sp_tile_plan pl = frame_plan(frames_total, h, w, window, stride, n_win, weights);
+  const Noise noise{noise_scale, seeds, step};
+  return euler_tail("sp_euler_ancestral_step_f16", &pl, weights ? 1 : 0, latent, eps_cond, eps_uncond, ld_eps, guidance,
+                    ld_guidance, out, sigma, sigma_down, b, &noise, stream);
 }
 
 extern "C" int sp_dpmpp2m_sde_step_f16(const void *state, const void *eps_cond, const void *eps_uncond, int64_t ld_eps,
@@ -366,11 +362,10 @@ extern "C" int sp_dpmpp2m_sde_step_f16(const void *state, const void *eps_cond, 
                                        float b, float c1, float c2, int batch, int frames_total, int h, int w, int window,
                                        int stride, int n_win, const float *weights, float noise_scale, const uint64_t *seeds,
                                        uint32_t step, void *stream) {
-  Tail t;
-  if (int rc = check_noise("sp_dpmpp2m_sde_step_f16", state, eps_cond, eps_uncond, ld_eps, guidance, ld_guidance, out_state, sigma, 8,
-                           batch, frames_total, h, w, window, stride, n_win, weights, noise_scale, seeds, step, &t))
-    return rc;
-  return dpmpp2m_step(t, a, b, c1, c2, stream);
+  const sp_tile_plan pl = frame_plan(frames_total, h, w, window, stride, n_win, weights);
+  const Noise noise{noise_scale, seeds, step};
+  return dpmpp2m_tail("sp_dpmpp2m_sde_step_f16", &pl, weights ? 1 : 0, state, eps_cond, eps_uncond, ld_eps, guidance, ld_guidance,
+                      out_state, sigma, a, b, c1, c2, batch, &noise, stream);
 }
 
 extern "C" size_t sp_tile_plan_size(void) { return sizeof(sp_tile_plan); }
@@ -379,20 +374,16 @@ extern "C" int sp_euler_step_tiles_f16(const sp_tile_plan *plan, const void *lat
                                        int64_t ld_eps, const float *guidance, int64_t ld_guidance, void *out, float sigma,
                                        float sigma_next_or_down, int batch, float noise_scale, const uint64_t *seeds,
                                        uint32_t step, void *stream) {
-  Tail t;
-  if (int rc = check_tiles("sp_euler_step_tiles_f16", plan, latent, eps_cond, eps_uncond, ld_eps, guidance, ld_guidance, out, sigma, 4,
-                           batch, noise_scale, seeds, step, &t))
-    return rc;
-  return euler_step(t, sigma, sigma_next_or_down, stream);
+  const Noise noise{noise_scale, seeds, step};
+  return euler_tail("sp_euler_step_tiles_f16", plan, 3, latent, eps_cond, eps_uncond, ld_eps, guidance, ld_guidance, out, sigma,
+                    sigma_next_or_down, batch, &noise, stream);
 }
 
 extern "C" int sp_dpmpp2m_step_tiles_f16(const sp_tile_plan *plan, const void *state, const void *eps_cond, const void *eps_uncond,
                                          int64_t ld_eps, const float *guidance, int64_t ld_guidance, void *out_state, float sigma,
                                          float a, float b, float c1, float c2, int batch, float noise_scale,
                                          const uint64_t *seeds, uint32_t step, void *stream) {
-  Tail t;
-  if (int rc = check_tiles("sp_dpmpp2m_step_tiles_f16", plan, state, eps_cond, eps_uncond, ld_eps, guidance, ld_guidance, out_state, sigma,
-                           8, batch, noise_scale, seeds, step, &t))
-    return rc;
-  return dpmpp2m_step(t, a, b, c1, c2, stream);
+  const Noise noise{noise_scale, seeds, step};
+  return dpmpp2m_tail("sp_dpmpp2m_step_tiles_f16", plan, 3, state, eps_cond, eps_uncond, ld_eps, guidance, ld_guidance, out_state,
+                      sigma, a, b, c1, c2, batch, &noise, stream);
 }

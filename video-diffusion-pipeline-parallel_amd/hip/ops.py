@@ -959,74 +959,6 @@ class ClockStamps:
         return sum(r for r, _ in mid) / len(mid), sum(s for _, s in mid) / len(mid), len(mid)
 
 
-def euler_step(latent, eps_cond, eps_uncond, guidance, out, *, ld_eps, sigma, sigma_next, b, frames, h, w,
-               ld_guidance=0):
-    """``ld_guidance``: ``guidance`` is fp32 [B][ld_guidance], one row of per-frame scales per video; 0 = one [F] row
-    shared by every video (``sp_euler_step_rows_f16``)."""
-    _check(load().sp_euler_step_rows_f16(latent.data_ptr(), eps_cond.data_ptr(), _ptr(eps_uncond), ld_eps, _ptr(guidance),
-                                         int(ld_guidance), out.data_ptr(), sigma, sigma_next, b, frames, h, w, _stream()),
-           "sp_euler_step_rows_f16")
-    return out
-
-
-def dpmpp2m_step(state, eps_cond, eps_uncond, guidance, out_state, *, ld_eps, sigma, a, b, c1, c2, batch, frames, h, w,
-                 ld_guidance=0):
-    """DPM-Solver++(2M) update of the 8-channel ``state`` (B,8,F,H,W: sample ++ previous denoised estimate) into
-    ``out_state`` (may be ``state`` itself); ``guidance`` / ``ld_guidance`` as for ``euler_step``
-    (``sp_dpmpp2m_step_rows_f16``)."""
-    for name, t in (("state", state), ("out_state", out_state)):
-        if _f16(t, name).shape != (batch, 8, frames, h, w) or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous ({batch}, 8, {frames}, {h}, {w}) tensor; got {tuple(t.shape)}, "
-                             f"strides {tuple(t.stride())}")
-    _check(load().sp_dpmpp2m_step_rows_f16(state.data_ptr(), eps_cond.data_ptr(), _ptr(eps_uncond), ld_eps, _ptr(guidance),
-                                           int(ld_guidance), out_state.data_ptr(), sigma, a, b, c1, c2, batch, frames, h, w,
-                                           _stream()), "sp_dpmpp2m_step_rows_f16")
-    return out_state
-
-
-def _window_args(name, tensors, channels, batch, frames_total, h, w, eps_cond, eps_uncond, ld_eps, window, n_win, weights):
-    """Shapes the window tails cannot see through raw pointers (``tensors``: name -> the stepped tensor and its output)."""
-    for what, t in tensors.items():
-        if _f16(t, what).shape != (batch, channels, frames_total, h, w) or not t.is_contiguous():
-            raise ValueError(f"{name}: {what} must be a contiguous ({batch}, {channels}, {frames_total}, {h}, {w}) tensor; "
-                             f"got {tuple(t.shape)}, strides {tuple(t.stride())}")
-    rows = n_win * batch * window * h * w
-    for what, t in (("eps_cond", eps_cond), ("eps_uncond", eps_uncond)):
-        if t is not None and (_f16(t, what).numel() != rows * ld_eps or not t.is_contiguous()):
-            raise ValueError(f"{name}: {what} must hold [n_win={n_win}][B={batch}][window={window}][{h * w}][ld_eps={ld_eps}] "
-                             f"contiguous values; got {tuple(t.shape)}")
-    if weights.dtype != torch.float32 or weights.numel() != n_win * window or not weights.is_contiguous():
-        raise ValueError(f"{name}: weights must be a contiguous float32 [{n_win}][{window}] table; got {weights.dtype} "
-                         f"{tuple(weights.shape)}")
-
-
-def euler_step_windows(latent, eps_cond, eps_uncond, guidance, out, *, ld_eps, sigma, sigma_next, b, frames_total, h, w,
-                       window, stride, n_win, weights, ld_guidance=0):
-    """The Euler update of ``latent`` (B,4,F_total,H,W) behind the eps rows of ``n_win`` overlapping frame windows
-    (``[n_win][B][window][H*W][ld_eps]``), blended with ``weights`` (fp32 ``[n_win][window]``, ``models.window_plan.plan``);
-    ``guidance`` is indexed by the position in the window (``sp_euler_step_windows_f16``)."""
-    _window_args("euler_step_windows", {"latent": latent, "out": out}, 4, b, frames_total, h, w, eps_cond, eps_uncond, ld_eps,
-                 window, n_win, weights)
-    _check(load().sp_euler_step_windows_f16(latent.data_ptr(), eps_cond.data_ptr(), _ptr(eps_uncond), ld_eps, _ptr(guidance),
-                                            int(ld_guidance), out.data_ptr(), sigma, sigma_next, b, frames_total, h, w,
-                                            window, stride, n_win, weights.data_ptr(), _stream()),
-           "sp_euler_step_windows_f16")
-    return out
-
-
-def dpmpp2m_step_windows(state, eps_cond, eps_uncond, guidance, out_state, *, ld_eps, sigma, a, b, c1, c2, batch,
-                         frames_total, h, w, window, stride, n_win, weights, ld_guidance=0):
-    """``dpmpp2m_step`` of the 8-channel ``state`` (B,8,F_total,H,W) behind the eps rows of ``n_win`` overlapping frame
-    windows; layouts as for ``euler_step_windows`` (``sp_dpmpp2m_step_windows_f16``)."""
-    _window_args("dpmpp2m_step_windows", {"state": state, "out_state": out_state}, 8, batch, frames_total, h, w, eps_cond,
-                 eps_uncond, ld_eps, window, n_win, weights)
-    _check(load().sp_dpmpp2m_step_windows_f16(state.data_ptr(), eps_cond.data_ptr(), _ptr(eps_uncond), ld_eps,
-                                              _ptr(guidance), int(ld_guidance), out_state.data_ptr(), sigma, a, b, c1, c2,
-                                              batch, frames_total, h, w, window, stride, n_win, weights.data_ptr(),
-                                              _stream()), "sp_dpmpp2m_step_windows_f16")
-    return out_state
-
-
 def _seeds(seeds, batch: int, name: str):
     """The per-video noise seeds of a stochastic tail: int64 ``[batch]`` on the device (the kernels read them as uint64)."""
     if seeds.dtype != torch.int64 or not seeds.is_cuda or seeds.shape != (batch,) or not seeds.is_contiguous():
@@ -1035,21 +967,83 @@ def _seeds(seeds, batch: int, name: str):
     return seeds.data_ptr()
 
 
-def _noise_tail_args(name, tensors, channels, batch, frames_total, h, w, eps_cond, eps_uncond, ld_eps, window, stride, n_win,
-                     weights, noise_scale, seeds):
-    """``(window, stride, n_win, weights pointer, seeds pointer)`` of a stochastic tail; ``weights=None`` is the unwindowed
-    form (one window that is the whole latent)."""
+def _tail(entry, name, stepped, *, channels, batch, dims, patch, eps, guidance, ld_eps, ld_guidance, consts, rest=(), lead=(),
+          weights=None, noise=None):
+    """One sampler-tail call ``entry(*lead, input, eps_cond, eps_uncond, ld_eps, guidance, ld_guidance, output, *consts, batch,
+    *rest[, noise_scale, seeds, step], stream)`` behind the checks of what the kernels cannot see through raw pointers.
+    ``stepped``: name -> tensor of the stepped tensor and of its output, each contiguous ``(batch, channels, *dims)`` with
+    ``dims = (frames_total, h, w)``; ``patch = (n_patch, window, tile_h, tile_w)``: the eps buffers hold
+    ``[n_patch][B][window][tile_h*tile_w][ld_eps]``; ``weights``: the ``[n_patch][window]`` table of an entry that takes frame
+    windows as arguments; ``noise = (noise_scale, seeds, step)`` of an entry that takes them."""
+    n_patch, window, tile_h, tile_w = patch
+    eps_cond, eps_uncond = eps
+    for what, t in stepped.items():
+        if _f16(t, what).shape != (batch, channels, *dims) or not t.is_contiguous():
+            raise ValueError(f"{name}: {what} must be a contiguous ({batch}, {channels}, {dims[0]}, {dims[1]}, {dims[2]}) tensor; "
+                             f"got {tuple(t.shape)}, strides {tuple(t.stride())}")
+    for what, t in (("eps_cond", eps_cond), ("eps_uncond", eps_uncond)):
+        if t is not None and (_f16(t, what).numel() != n_patch * batch * window * tile_h * tile_w * ld_eps or not t.is_contiguous()):
+            raise ValueError(f"{name}: {what} must hold [n_patch={n_patch}][B={batch}][window={window}][{tile_h * tile_w}]"
+                             f"[ld_eps={ld_eps}] contiguous values; got {tuple(t.shape)}")
+    if weights is not None and (weights.dtype != torch.float32 or weights.numel() != n_patch * window or not weights.is_contiguous()):
+        raise ValueError(f"{name}: weights must be a contiguous float32 [{n_patch}][{window}] table; got {weights.dtype} "
+                         f"{tuple(weights.shape)}")
+    if noise is not None:
+        noise_scale, seeds, step = noise
+        if seeds is None and noise_scale != 0.0:
+            raise ValueError(f"{name}: noise_scale={noise_scale} needs the videos' seeds")
+        rest = (*rest, noise_scale, None if seeds is None else _seeds(seeds, batch, name), int(step))
+    src, out = stepped.values()
+    _check(getattr(load(), entry)(*lead, src.data_ptr(), eps_cond.data_ptr(), _ptr(eps_uncond), ld_eps, _ptr(guidance),
+                                  int(ld_guidance), out.data_ptr(), *consts, batch, *rest, _stream()), entry)
+    return out
+
+
+def _windows(frames_total, h, w, window, stride, n_win, weights):
+    """``(patch, rest)`` of an entry that takes frame windows as arguments; ``weights=None``: one window that is the whole latent."""
     if weights is None:
         window, stride, n_win = frames_total, frames_total, 1
-        for what, t in tensors.items():
-            if _f16(t, what).shape != (batch, channels, frames_total, h, w) or not t.is_contiguous():
-                raise ValueError(f"{name}: {what} must be a contiguous ({batch}, {channels}, {frames_total}, {h}, {w}) tensor; "
-                                 f"got {tuple(t.shape)}, strides {tuple(t.stride())}")
-    else:
-        _window_args(name, tensors, channels, batch, frames_total, h, w, eps_cond, eps_uncond, ld_eps, window, n_win, weights)
-    if seeds is None and noise_scale != 0.0:
-        raise ValueError(f"{name}: noise_scale={noise_scale} needs the videos' seeds")
-    return window, stride, n_win, _ptr(weights), None if seeds is None else _seeds(seeds, batch, name)
+    return (n_win, window, h, w), (frames_total, h, w, window, stride, n_win, _ptr(weights))
+
+
+def euler_step(latent, eps_cond, eps_uncond, guidance, out, *, ld_eps, sigma, sigma_next, b, frames, h, w,
+               ld_guidance=0):
+    """``ld_guidance``: ``guidance`` is fp32 [B][ld_guidance], one row of per-frame scales per video; 0 = one [F] row
+    shared by every video (``sp_euler_step_rows_f16``)."""
+    return _tail("sp_euler_step_rows_f16", "euler_step", {"latent": latent, "out": out}, channels=4, batch=b, dims=(frames, h, w),
+                 patch=(1, frames, h, w), eps=(eps_cond, eps_uncond), guidance=guidance, ld_eps=ld_eps, ld_guidance=ld_guidance,
+                 consts=(sigma, sigma_next), rest=(frames, h, w))
+
+
+def dpmpp2m_step(state, eps_cond, eps_uncond, guidance, out_state, *, ld_eps, sigma, a, b, c1, c2, batch, frames, h, w,
+                 ld_guidance=0):
+    """DPM-Solver++(2M) update of the 8-channel ``state`` (B,8,F,H,W: sample ++ previous denoised estimate) into
+    ``out_state`` (may be ``state`` itself); ``guidance`` / ``ld_guidance`` as for ``euler_step``
+    (``sp_dpmpp2m_step_rows_f16``)."""
+    return _tail("sp_dpmpp2m_step_rows_f16", "dpmpp2m_step", {"state": state, "out_state": out_state}, channels=8, batch=batch,
+                 dims=(frames, h, w), patch=(1, frames, h, w), eps=(eps_cond, eps_uncond), guidance=guidance, ld_eps=ld_eps, ld_guidance=ld_guidance,
+                 consts=(sigma, a, b, c1, c2), rest=(frames, h, w))
+
+
+def euler_step_windows(latent, eps_cond, eps_uncond, guidance, out, *, ld_eps, sigma, sigma_next, b, frames_total, h, w,
+                       window, stride, n_win, weights, ld_guidance=0):
+    """The Euler update of ``latent`` (B,4,F_total,H,W) behind the eps rows of ``n_win`` overlapping frame windows
+    (``[n_win][B][window][H*W][ld_eps]``), blended with ``weights`` (fp32 ``[n_win][window]``, ``models.window_plan.plan``);
+    ``guidance`` is indexed by the position in the window (``sp_euler_step_windows_f16``)."""
+    patch, rest = _windows(frames_total, h, w, window, stride, n_win, weights)
+    return _tail("sp_euler_step_windows_f16", "euler_step_windows", {"latent": latent, "out": out}, channels=4, batch=b,
+                 dims=(frames_total, h, w), patch=patch, eps=(eps_cond, eps_uncond), guidance=guidance, ld_eps=ld_eps, ld_guidance=ld_guidance,
+                 consts=(sigma, sigma_next), rest=rest, weights=weights)
+
+
+def dpmpp2m_step_windows(state, eps_cond, eps_uncond, guidance, out_state, *, ld_eps, sigma, a, b, c1, c2, batch,
+                         frames_total, h, w, window, stride, n_win, weights, ld_guidance=0):
+    """``dpmpp2m_step`` of the 8-channel ``state`` (B,8,F_total,H,W) behind the eps rows of ``n_win`` overlapping frame
+    windows; layouts as for ``euler_step_windows`` (``sp_dpmpp2m_step_windows_f16``)."""
+    patch, rest = _windows(frames_total, h, w, window, stride, n_win, weights)
+    return _tail("sp_dpmpp2m_step_windows_f16", "dpmpp2m_step_windows", {"state": state, "out_state": out_state}, channels=8, batch=batch,
+                 dims=(frames_total, h, w), patch=patch, eps=(eps_cond, eps_uncond), guidance=guidance, ld_eps=ld_eps, ld_guidance=ld_guidance,
+                 consts=(sigma, a, b, c1, c2), rest=rest, weights=weights)
 
 
 def euler_ancestral_step(latent, eps_cond, eps_uncond, guidance, out, *, ld_eps, sigma, sigma_down, noise_scale, seeds, step,
@@ -1057,61 +1051,43 @@ def euler_ancestral_step(latent, eps_cond, eps_uncond, guidance, out, *, ld_eps,
     """The Euler ancestral update of ``latent`` (B,4,F_total,H,W): the Euler step to ``sigma_down`` plus ``noise_scale * z``,
     ``z`` the normals of (``seeds[b]``, ``step``, the element) (``sp_euler_ancestral_step_f16``).  ``weights=None``: eps rows
     ``[B][F][H*W][ld_eps]``; else the window arguments of ``euler_step_windows``."""
-    window, stride, n_win, wp, sp = _noise_tail_args("euler_ancestral_step", {"latent": latent, "out": out}, 4, b, frames_total,
-                                                     h, w, eps_cond, eps_uncond, ld_eps, window, stride, n_win, weights,
-                                                     noise_scale, seeds)
-    _check(load().sp_euler_ancestral_step_f16(latent.data_ptr(), eps_cond.data_ptr(), _ptr(eps_uncond), ld_eps, _ptr(guidance),
-                                              int(ld_guidance), out.data_ptr(), sigma, sigma_down, b, frames_total, h, w,
-                                              window, stride, n_win, wp, noise_scale, sp, int(step), _stream()),
-           "sp_euler_ancestral_step_f16")
-    return out
+    patch, rest = _windows(frames_total, h, w, window, stride, n_win, weights)
+    return _tail("sp_euler_ancestral_step_f16", "euler_ancestral_step", {"latent": latent, "out": out}, channels=4, batch=b,
+                 dims=(frames_total, h, w), patch=patch, eps=(eps_cond, eps_uncond), guidance=guidance, ld_eps=ld_eps, ld_guidance=ld_guidance,
+                 consts=(sigma, sigma_down), rest=rest, weights=weights, noise=(noise_scale, seeds, step))
 
 
 def dpmpp2m_sde_step(state, eps_cond, eps_uncond, guidance, out_state, *, ld_eps, sigma, a, b, c1, c2, noise_scale, seeds, step,
                      batch, frames_total, h, w, window=None, stride=None, n_win=None, weights=None, ld_guidance=0):
     """The DPM-Solver++(2M) SDE update of the 8-channel ``state`` (B,8,F_total,H,W): ``dpmpp2m_step`` with ``noise_scale * z``
     added to the sample, not to the stored estimate (``sp_dpmpp2m_sde_step_f16``); windows as for ``euler_ancestral_step``."""
-    window, stride, n_win, wp, sp = _noise_tail_args("dpmpp2m_sde_step", {"state": state, "out_state": out_state}, 8, batch,
-                                                     frames_total, h, w, eps_cond, eps_uncond, ld_eps, window, stride, n_win,
-                                                     weights, noise_scale, seeds)
-    _check(load().sp_dpmpp2m_sde_step_f16(state.data_ptr(), eps_cond.data_ptr(), _ptr(eps_uncond), ld_eps, _ptr(guidance),
-                                          int(ld_guidance), out_state.data_ptr(), sigma, a, b, c1, c2, batch, frames_total, h, w,
-                                          window, stride, n_win, wp, noise_scale, sp, int(step), _stream()),
-           "sp_dpmpp2m_sde_step_f16")
-    return out_state
+    patch, rest = _windows(frames_total, h, w, window, stride, n_win, weights)
+    return _tail("sp_dpmpp2m_sde_step_f16", "dpmpp2m_sde_step", {"state": state, "out_state": out_state}, channels=8, batch=batch,
+                 dims=(frames_total, h, w), patch=patch, eps=(eps_cond, eps_uncond), guidance=guidance, ld_eps=ld_eps, ld_guidance=ld_guidance,
+                 consts=(sigma, a, b, c1, c2), rest=rest, weights=weights, noise=(noise_scale, seeds, step))
 
 
 class TileRecord:
     """A ``models.tile_plan.TilePlan`` as the kernels take it: the ``sp_tile_plan`` record and the three weight tables on the
-    device, which it keeps alive."""
+    device, which it keeps alive.  ``space=False``: a record for the entries that take frame windows as arguments, which read
+    ``wf`` alone; ``wy`` and ``wx`` are not uploaded and stay null (the tiles entries refuse such a record)."""
 
-    def __init__(self, plan, device):
+    def __init__(self, plan, device, space=True):
         from . import TilePlan
         self.plan = plan
-        self.wf, self.wy, self.wx = (torch.from_numpy(t).to(device).contiguous() for t in (plan.wf, plan.wy, plan.wx))
+        self.wf, self.wy, self.wx = (torch.from_numpy(t).to(device).contiguous() if space or i == 0 else None
+                                     for i, t in enumerate((plan.wf, plan.wy, plan.wx)))
         fr, ay, ax = plan.frames, plan.y, plan.x
         self.desc = TilePlan(frames_total=fr.frames_total, window=fr.window, stride=fr.stride, n_win=fr.n_win,
                              h=ay.frames_total, w=ax.frames_total, tile_h=ay.window, tile_w=ax.window, stride_y=ay.stride,
-                             stride_x=ax.stride, n_ty=ay.n_win, n_tx=ax.n_win, wf=self.wf.data_ptr(), wy=self.wy.data_ptr(),
-                             wx=self.wx.data_ptr())
+                             stride_x=ax.stride, n_ty=ay.n_win, n_tx=ax.n_win, wf=self.wf.data_ptr(), wy=_ptr(self.wy),
+                             wx=_ptr(self.wx))
 
 
-def _tile_args(name, tensors, channels, batch, rec, eps_cond, eps_uncond, ld_eps, noise_scale, seeds):
-    """Shapes the tiles tails cannot see through raw pointers; returns the seeds pointer."""
+def _tiles(rec):
+    """``(dims, patch, lead)`` of an entry that takes its plan as a ``TileRecord``."""
     d = rec.desc
-    for what, t in tensors.items():
-        if _f16(t, what).shape != (batch, channels, d.frames_total, d.h, d.w) or not t.is_contiguous():
-            raise ValueError(f"{name}: {what} must be a contiguous ({batch}, {channels}, {d.frames_total}, {d.h}, {d.w}) tensor; "
-                             f"got {tuple(t.shape)}, strides {tuple(t.stride())}")
-    n_patch = d.n_win * d.n_ty * d.n_tx
-    rows = n_patch * batch * d.window * d.tile_h * d.tile_w
-    for what, t in (("eps_cond", eps_cond), ("eps_uncond", eps_uncond)):
-        if t is not None and (_f16(t, what).numel() != rows * ld_eps or not t.is_contiguous()):
-            raise ValueError(f"{name}: {what} must hold [n_patch={n_patch}][B={batch}][window={d.window}]"
-                             f"[{d.tile_h * d.tile_w}][ld_eps={ld_eps}] contiguous values; got {tuple(t.shape)}")
-    if seeds is None and noise_scale != 0.0:
-        raise ValueError(f"{name}: noise_scale={noise_scale} needs the videos' seeds")
-    return None if seeds is None else _seeds(seeds, batch, name)
+    return (d.frames_total, d.h, d.w), (d.n_win * d.n_ty * d.n_tx, d.window, d.tile_h, d.tile_w), (ctypes.byref(d),)
 
 
 def euler_step_tiles(latent, eps_cond, eps_uncond, guidance, out, *, plan, ld_eps, sigma, sigma_next, b, ld_guidance=0,
@@ -1120,23 +1096,20 @@ def euler_step_tiles(latent, eps_cond, eps_uncond, guidance, out, *, plan, ld_ep
     frame windows times overlapping spatial tiles, ``[n_patch][B][window][tile_h*tile_w][ld_eps]``.  ``noise_scale != 0`` is the
     Euler ancestral update (``sigma_next`` is then sigma_down) with the noise of ``seeds`` and ``step``
     (``sp_euler_step_tiles_f16``)."""
-    sp = _tile_args("euler_step_tiles", {"latent": latent, "out": out}, 4, b, plan, eps_cond, eps_uncond, ld_eps, noise_scale, seeds)
-    _check(load().sp_euler_step_tiles_f16(ctypes.byref(plan.desc), latent.data_ptr(), eps_cond.data_ptr(), _ptr(eps_uncond), ld_eps,
-                                          _ptr(guidance), int(ld_guidance), out.data_ptr(), sigma, sigma_next, b, noise_scale, sp,
-                                          int(step), _stream()), "sp_euler_step_tiles_f16")
-    return out
+    dims, patch, lead = _tiles(plan)
+    return _tail("sp_euler_step_tiles_f16", "euler_step_tiles", {"latent": latent, "out": out}, channels=4, batch=b, dims=dims, patch=patch,
+                 eps=(eps_cond, eps_uncond), guidance=guidance, ld_eps=ld_eps, ld_guidance=ld_guidance,
+                 consts=(sigma, sigma_next), lead=lead, noise=(noise_scale, seeds, step))
 
 
 def dpmpp2m_step_tiles(state, eps_cond, eps_uncond, guidance, out_state, *, plan, ld_eps, sigma, a, b, c1, c2, batch,
                        ld_guidance=0, noise_scale=0.0, seeds=None, step=0):
     """``dpmpp2m_step`` (``noise_scale != 0``: ``dpmpp2m_sde_step``) of the 8-channel ``state`` (B,8,F_total,H,W) behind the eps
     rows of the patches of ``plan``; layouts as for ``euler_step_tiles`` (``sp_dpmpp2m_step_tiles_f16``)."""
-    sp = _tile_args("dpmpp2m_step_tiles", {"state": state, "out_state": out_state}, 8, batch, plan, eps_cond, eps_uncond, ld_eps,
-                    noise_scale, seeds)
-    _check(load().sp_dpmpp2m_step_tiles_f16(ctypes.byref(plan.desc), state.data_ptr(), eps_cond.data_ptr(), _ptr(eps_uncond),
-                                            ld_eps, _ptr(guidance), int(ld_guidance), out_state.data_ptr(), sigma, a, b, c1, c2,
-                                            batch, noise_scale, sp, int(step), _stream()), "sp_dpmpp2m_step_tiles_f16")
-    return out_state
+    dims, patch, lead = _tiles(plan)
+    return _tail("sp_dpmpp2m_step_tiles_f16", "dpmpp2m_step_tiles", {"state": state, "out_state": out_state}, channels=8, batch=batch, dims=dims,
+                 patch=patch, eps=(eps_cond, eps_uncond), guidance=guidance, ld_eps=ld_eps, ld_guidance=ld_guidance,
+                 consts=(sigma, a, b, c1, c2), lead=lead, noise=(noise_scale, seeds, step))
 
 
 def randn(out, seeds, *, scale=1.0, step=0, purpose=0):

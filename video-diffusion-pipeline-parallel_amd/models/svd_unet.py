@@ -99,6 +99,11 @@ def _per_video(name: str, value, batch: int) -> list:
     return [value] * batch
 
 
+# how a step runs: keywords of ``StableVideoUNet.__init__``, which alone validates them; the class methods pass them on
+STEP_OPTIONS = ("sampler", "window_stride", "window_weights", "windows_per_call", "eta", "s_noise", "tile_size", "tile_stride",
+                "tile_weights", "batched_cfg")
+
+
 class StableVideoUNet(nn.Module):
     def __init__(
         self,
@@ -159,7 +164,7 @@ class StableVideoUNet(nn.Module):
                 if t < 1 or not 1 <= st <= t:
                     raise ValueError(f"tile plan, {name} (tile={t}, stride={st}): tile must be at least 1 and stride from 1 to tile")
         self.tile_weights = tile_weights
-        self._tile_plans: dict = {}      # (frames_total, window, H, W) -> ops.TileRecord
+        self._step_plans: dict = {}      # (frames_total, window, H, W) -> ops.TileRecord
         if window_stride is not None and int(window_stride) < 1:
             raise ValueError(f"window_stride must be a positive frame count or None; got {window_stride}")
         if window_weights not in window_plan.WEIGHTS:
@@ -169,7 +174,6 @@ class StableVideoUNet(nn.Module):
         self.window_stride = None if window_stride is None else int(window_stride)
         self.window_weights = window_weights
         self.windows_per_call = int(windows_per_call)
-        self._window_plans: dict = {}    # (frames_total, window) -> (plan, its weight table on the device)
         if sampler not in solver_schedule.SAMPLERS:
             raise ValueError(f"sampler must be one of {solver_schedule.SAMPLERS}; got {sampler!r}")
         self.sampler = sampler
@@ -261,20 +265,14 @@ class StableVideoUNet(nn.Module):
         enable_sliced_attention: bool = False,
         attention_slice_size: int | str = "auto",
         device="cuda",
-        sampler: str = "euler",
-        window_stride: int | None = None,
-        window_weights: str = "triangle",
-        eta: float = 1.0,
-        s_noise: float = 1.0,
-        tile_size=None,
-        tile_stride=None,
-        tile_weights: str = "triangle",
         **kwargs,
     ) -> "StableVideoUNet":
         """Load ``<model_id>/unet/diffusion_pytorch_model*.safetensors`` from a LOCAL directory.
 
         The attention toggles of the reference signature are accepted and ignored: the fused HIP
         attention kernels are always on.  A hub name cannot be fetched (no network): ValueError.
+        Of ``kwargs`` the step options (``STEP_OPTIONS``: ``sampler``, ``window_stride``, ``tile_size``, ...) go to
+        ``__init__``, which validates them; the reference's other keywords are accepted and ignored.
         """
         unet_dir = os.path.join(model_id, "unet")
         if not os.path.isdir(unet_dir):
@@ -317,25 +315,23 @@ class StableVideoUNet(nn.Module):
             )
         if timesteps is None:
             timesteps = cls._default_timestep_schedule(num_steps=25)
-        return cls(unet=SVDUNetHIP(cfg, sd, device), timesteps=timesteps, dtype=torch_dtype, sampler=sampler,
-                   window_stride=window_stride, window_weights=window_weights, eta=eta, s_noise=s_noise,
-                   tile_size=tile_size, tile_stride=tile_stride, tile_weights=tile_weights)
+        return cls(unet=SVDUNetHIP(cfg, sd, device), timesteps=timesteps, dtype=torch_dtype,
+                   **{k: v for k, v in kwargs.items() if k in STEP_OPTIONS})
 
     @classmethod
     def from_random_init(cls, timesteps: Sequence[int], *, config: UNetConfig | None = None, seed: int = 0,
                          device="cuda", fp8_attention: bool | None = None,
-                         long_attention: bool | None = None, sampler: str = "euler",
-                         window_stride: int | None = None, window_weights: str = "triangle", eta: float = 1.0,
-                         s_noise: float = 1.0, tile_size=None, tile_stride=None,
-                         tile_weights: str = "triangle") -> "StableVideoUNet":
-        """Random weights of the exact SVD architecture (benchmarks / tests; no checkpoint needed)."""
+                         long_attention: bool | None = None, **step_options) -> "StableVideoUNet":
+        """Random weights of the exact SVD architecture (benchmarks / tests; no checkpoint needed); ``step_options``
+        (``STEP_OPTIONS``) as for ``__init__``."""
+        unknown = sorted(set(step_options) - set(STEP_OPTIONS))
+        if unknown:
+            raise TypeError(f"from_random_init() got an unexpected keyword argument {unknown[0]!r}")
         cfg = config or UNetConfig.svd()
         sd = random_state_dict(cfg, seed=seed, device=device, dtype=torch.float16)
         unet = SVDUNetHIP(cfg, sd, device, fp8_attention=fp8_attention, long_attention=long_attention)
         del sd
-        return cls(unet=unet, timesteps=timesteps, sampler=sampler, window_stride=window_stride,
-                   window_weights=window_weights, eta=eta, s_noise=s_noise, tile_size=tile_size, tile_stride=tile_stride,
-                   tile_weights=tile_weights)
+        return cls(unet=unet, timesteps=timesteps, **step_options)
 
     def enable_graphs(self, enabled: bool = True) -> None:
         """Replay each diffusion step from a captured HIP graph (one graph per step index and latent shape).
@@ -483,41 +479,38 @@ class StableVideoUNet(nn.Module):
                                       added_ids32=self._cond.added_ids32 if added_ids32 is None else added_ids32, euler=euler,
                                       **({} if eps_out is None else {"eps_out": eps_out}))
 
-    def _unet_passes(self, x, cond: VideoConditioning, step, in_scale, *, windows=1, eps_out=None, euler=None):
+    def _unet_passes(self, x, cond: VideoConditioning, step, in_scale, *, eps_out=None, euler=None):
         """The UNet passes of one step on the sample ``x``: the conditional one and, with guidance, the unconditional one,
         as two sequential passes (the reference's order) or, with ``batched_cfg``, as the halves ``[uncond, cond]`` of one
         call.  Returns ``(eps_cond, eps_uncond or None)``.
 
-        ``windows``: ``x`` holds that many frame windows of all videos stacked as ``[window][video]`` batch rows; the
-        conditioning rows are repeated per window.  ``eps_out``: ``(rows for eps_cond, rows for eps_uncond or None)`` to
-        store the passes' eps rows in (a batched call's halves are copied there).  ``euler``: the Euler tail (``latent``,
-        ``out``, ``sigma``, ``sigma_next``) for the epilogue of a sequential conditional pass' last convolution, which applies
-        the guidance mix and the update itself: its eps rows never exist in HBM and ``eps_cond`` is None.  A batched call
-        cannot take it: both eps come back and the tail is the caller's."""
-        def rep(t):
-            return t if windows == 1 else torch.cat([t] * windows, dim=0)
-
-        ids = cond.added_ids32 if cond.added_ids32.dim() == 1 else rep(cond.added_ids32)      # [3], or one row per video
+        ``x`` may hold several patches of all videos stacked as ``[patch][video]`` batch rows, with ``cond`` repeated to match
+        (``_patch_conditioning``).  ``eps_out``: ``(rows for eps_cond, rows for eps_uncond or None)`` to store the passes' eps
+        rows in (a batched call's halves are copied there).  ``euler``: the Euler tail (``latent``, ``out``, ``sigma``,
+        ``sigma_next``) for the epilogue of a sequential conditional pass' last convolution, which applies the guidance mix and
+        the update itself: its eps rows never exist in HBM and ``eps_cond`` is None.  A batched call cannot take it: both eps
+        come back and the tail is the caller's."""
+        ids = cond.added_ids32                                                                # [3], or one row per video
         out_c, out_u = (None, None) if eps_out is None else eps_out
         if not cond.guided:
-            return self._unet_pass(x, rep(cond.image_latents), rep(cond.image_embeddings), in_scale, step, euler=euler,
+            return self._unet_pass(x, cond.image_latents, cond.image_embeddings, in_scale, step, euler=euler,
                                    added_ids32=ids, eps_out=out_c), None
         if self.batched_cfg:
             both = self._unet_pass(torch.cat([x, x], dim=0),
-                                   torch.cat([rep(cond.uncond_image_latents), rep(cond.image_latents)], dim=0),
-                                   torch.cat([rep(cond.uncond_embeddings), rep(cond.image_embeddings)], dim=0), in_scale, step,
+                                   torch.cat([cond.uncond_image_latents, cond.image_latents], dim=0),
+                                   torch.cat([cond.uncond_embeddings, cond.image_embeddings], dim=0), in_scale, step,
                                    added_ids32=ids if ids.dim() == 1 else torch.cat([ids, ids], dim=0))
             half = both.shape[0] // 2
             eps_u, eps_c = both[:half], both[half:]
             if eps_out is not None:
                 eps_u, eps_c = out_u.copy_(eps_u), out_c.copy_(eps_c)
             return eps_c, eps_u
-        eps_u = self._unet_pass(x, rep(cond.uncond_image_latents), rep(cond.uncond_embeddings), in_scale, step,
+        eps_u = self._unet_pass(x, cond.uncond_image_latents, cond.uncond_embeddings, in_scale, step,
                                 added_ids32=ids, eps_out=out_u)
         if euler is not None:
             euler = dict(euler, eps_uncond=eps_u, guidance=cond.guidance32, ld_eps=eps_u.shape[1],
                          ld_guidance=cond.guidance_ld)
-        return self._unet_pass(x, rep(cond.image_latents), rep(cond.image_embeddings), in_scale, step, euler=euler,
+        return self._unet_pass(x, cond.image_latents, cond.image_embeddings, in_scale, step, euler=euler,
                                added_ids32=ids, eps_out=out_c), eps_u
 
     @torch.inference_mode()
@@ -556,11 +549,11 @@ class StableVideoUNet(nn.Module):
         elif latent.dim() != 5 or latent.shape[1] != 4:
             raise ValueError(f"latent must be (B, 4, F, H, W); got {tuple(latent.shape)}")
         sample_shape = (latent.shape[0], 4) + tuple(latent.shape[2:])
-        frames = latent.shape[2]
+        # with window_stride a long latent against a conditioning prepared for one window of W = num_frames frames
+        frames = latent.shape[2] if self.window_stride is None else cond.num_frames
+        # ValueError naming (total, tile, stride) of the axis, or (frames_total, window, stride); the plan's tables reach the device here
+        self._step_plan(latent.shape[2], frames, latent.shape[3], latent.shape[4])
         if self.window_stride is not None:
-            # a long latent against a conditioning prepared for one window of W = num_frames frames
-            frames = cond.num_frames
-            self._window_plan(latent.shape[2], frames)         # ValueError naming (frames_total, window, stride)
             sample_shape = sample_shape[:2] + (frames,) + sample_shape[3:]
             if tuple(cond.image_latents.shape) != sample_shape:
                 raise ValueError(f"image_latents {tuple(cond.image_latents.shape)} do not match one window {sample_shape} of "
@@ -569,8 +562,6 @@ class StableVideoUNet(nn.Module):
         elif tuple(cond.image_latents.shape) != sample_shape:
             raise ValueError(f"image_latents {tuple(cond.image_latents.shape)} do not match the latent "
                              f"{sample_shape} (set_conditioning was called for another batch / frame count / size)")
-        if self.tile_size is not None:                         # ValueError naming (total, tile, stride) of the axis
-            self._tile_plan(latent.shape[2], frames, latent.shape[3], latent.shape[4])
         emb = cond.image_embeddings
         if emb.dim() != 3 or emb.shape[0] != latent.shape[0] or emb.shape[1] != 1 \
                 or emb.shape[2] != self.unet.cfg.cross_attention_dim:
@@ -641,14 +632,8 @@ class StableVideoUNet(nn.Module):
 
     def _forward_eager(self, latent: torch.Tensor, step: int, cond: VideoConditioning | None = None) -> torch.Tensor:
         cond = self._cond if cond is None else cond
-        if self.tile_size is not None:
-            return self._forward_tiles(latent, step, cond)
-        if self.window_stride is not None:
-            return self._forward_windows(latent, step, cond)
-        if self.state_channels == 8:
-            return self._forward_dpmpp_2m(latent, step, cond)
-        if self.sampler == "euler_a":
-            return self._forward_euler_ancestral(latent, step, cond)
+        if self.sampler != "euler" or self.window_stride is not None or self.tile_size is not None:
+            return self._forward_stored_eps(latent, step, cond)
         b, _, f, h, w = latent.shape
         sigma, sigma_next = self._sigma_host[step], self._sigma_host[step + 1]
         out = torch.empty_like(latent)
@@ -660,113 +645,33 @@ class StableVideoUNet(nn.Module):
                            ld_guidance=cond.guidance_ld)
         return out
 
-    def _forward_dpmpp_2m(self, state: torch.Tensor, step: int, cond: VideoConditioning) -> torch.Tensor:
-        """One DPM-Solver++(2M) step of ``state`` (B,8,F,H,W).  The UNet passes are those of the Euler step without its
-        tail: ``conv_out`` stores its four eps channels and ``sp_dpmpp2m_step_rows_f16`` follows with this step's
-        coefficients (host constants, so a captured graph of the step holds them)."""
-        b, _, f, h, w = state.shape
-        sigma = self._sigma_host[step]
-        x = state[:, :4].contiguous()                     # (a view for one video; else a copy of the four sample planes)
-        eps_c, eps_u = self._unet_passes(x, cond, step, 1.0 / math.sqrt(sigma * sigma + 1.0))
-        out = torch.empty_like(state)
-        guidance = cond.guidance32 if eps_u is not None else None
-        if self.sampler == "dpmpp_2m_sde":                # the same step plus n*z from (the videos' seeds, the step index)
-            a, b_, c1, c2, n = self._noise_coef[step]
-            return ops.dpmpp2m_sde_step(state, eps_c, eps_u, guidance, out, ld_eps=eps_c.shape[1], sigma=sigma, a=a, b=b_, c1=c1,
-                                        c2=c2, noise_scale=n, seeds=cond.noise_seeds, step=step, batch=b, frames_total=f, h=h,
-                                        w=w, ld_guidance=cond.guidance_ld)
-        a, b_, c1, c2 = self._solver_coef[step]
-        ops.dpmpp2m_step(state, eps_c, eps_u, guidance, out, ld_eps=eps_c.shape[1],
-                         sigma=sigma, a=a, b=b_, c1=c1, c2=c2, batch=b, frames=f, h=h, w=w, ld_guidance=cond.guidance_ld)
-        return out
-
-    def _forward_euler_ancestral(self, latent: torch.Tensor, step: int, cond: VideoConditioning) -> torch.Tensor:
-        """One Euler ancestral step of ``latent`` (B,4,F,H,W) through the stored-eps route, as 2M takes it: the noise is
-        evaluated in the tail kernel, which ``conv_out``'s fused Euler epilogue is not."""
-        b, _, f, h, w = latent.shape
-        sigma = self._sigma_host[step]
-        sigma_down, n = self._noise_coef[step]
-        eps_c, eps_u = self._unet_passes(latent, cond, step, 1.0 / math.sqrt(sigma * sigma + 1.0))
-        return ops.euler_ancestral_step(latent, eps_c, eps_u, cond.guidance32 if eps_u is not None else None,
-                                        torch.empty_like(latent), ld_eps=eps_c.shape[1], sigma=sigma, sigma_down=sigma_down,
-                                        noise_scale=n, seeds=cond.noise_seeds, step=step, b=b, frames_total=f, h=h, w=w,
-                                        ld_guidance=cond.guidance_ld)
-
-    # ------------------------------------------------------------------ long videos: overlapping frame windows
-    def _window_plan(self, frames_total: int, window: int):
-        """(plan, weight table on the device) of a latent of ``frames_total`` frames cut into windows of ``window``."""
-        key = (int(frames_total), int(window))
-        entry = self._window_plans.get(key)
-        if entry is None:
-            pl = window_plan.plan(frames_total, window, self.window_stride, self.window_weights)
-            entry = self._window_plans[key] = (pl, torch.from_numpy(pl.weights).to(self.unet.device).contiguous())
-        return entry
-
-    def _forward_windows(self, state: torch.Tensor, step: int, cond: VideoConditioning) -> torch.Tensor:
-        """One step of a latent of F_total frames as n_win overlapping windows of W = ``cond.num_frames`` frames: the UNet
-        passes of the unwindowed step on every window's frame slice (``windows_per_call`` windows of all B videos per call,
-        the conditioning rows repeated per window), each call's eps rows stored to its slice of one
-        [n_win][B][W][H*W][4] buffer per pass, then ONE tail behind them (``sp_euler_step_windows_f16`` /
-        ``sp_dpmpp2m_step_windows_f16``).  Both samplers take the stored-eps route: the Euler tail in ``conv_out``'s
-        epilogue cannot see the other windows."""
-        b, _, ft, h, w = state.shape
-        win = cond.num_frames
-        pl, weights = self._window_plan(ft, win)
-        sigma = self._sigma_host[step]
-        in_scale = 1.0 / math.sqrt(sigma * sigma + 1.0)
-        x = state if self.state_channels == 4 else state[:, :4]
-        ld_eps = self.unet.cfg.out_channels
-        rows = b * win * h * w                                  # eps rows of one window of all videos
-        eps_c = torch.empty((pl.n_win * rows, ld_eps), dtype=torch.float16, device=state.device)
-        eps_u = torch.empty_like(eps_c) if cond.guided else None
-        for k0 in range(0, pl.n_win, self.windows_per_call):
-            n = min(self.windows_per_call, pl.n_win - k0)
-            # [window][video] batch rows: the layout of the eps buffer
-            xs = torch.cat([x[:, :, s:s + win] for s in pl.starts[k0:k0 + n]], dim=0).contiguous()
-            dst = slice(k0 * rows, (k0 + n) * rows)
-            self._unet_passes(xs, cond, step, in_scale, windows=n,
-                              eps_out=(eps_c[dst], eps_u[dst] if cond.guided else None))
-        out = torch.empty_like(state)
-        common = dict(ld_eps=ld_eps, h=h, w=w, window=win, stride=pl.stride, n_win=pl.n_win, weights=weights,
-                      frames_total=ft, ld_guidance=cond.guidance_ld)
-        guidance = cond.guidance32 if cond.guided else None
-        if self.stochastic:                                    # the noise of global frame f, whichever windows cover it
-            noise = dict(seeds=cond.noise_seeds, step=step, **common)
-            if self.sampler == "dpmpp_2m_sde":
-                a, b_, c1, c2, n = self._noise_coef[step]
-                return ops.dpmpp2m_sde_step(state, eps_c, eps_u, guidance, out, sigma=sigma, a=a, b=b_, c1=c1, c2=c2,
-                                            noise_scale=n, batch=b, **noise)
-            sigma_down, n = self._noise_coef[step]
-            return ops.euler_ancestral_step(state, eps_c, eps_u, guidance, out, sigma=sigma, sigma_down=sigma_down,
-                                            noise_scale=n, b=b, **noise)
-        if self.sampler == "dpmpp_2m":
-            a, b_, c1, c2 = self._solver_coef[step]
-            return ops.dpmpp2m_step_windows(state, eps_c, eps_u, guidance, out, sigma=sigma, a=a, b=b_, c1=c1, c2=c2,
-                                            batch=b, **common)
-        return ops.euler_step_windows(state, eps_c, eps_u, guidance, out, sigma=sigma,
-                                      sigma_next=self._sigma_host[step + 1], b=b, **common)
-
-    # ------------------------------------------------------------------ large frames: overlapping spatial tiles
-    def _tile_plan(self, frames_total: int, window: int, h: int, w: int):
-        """The ``ops.TileRecord`` (plan, tables on the device) of a latent of ``frames_total`` x ``h`` x ``w`` cut into frame
-        windows of ``window`` (one window without ``window_stride``) times tiles of ``tile_size``."""
+    # ------------------------------------------------------------------ every other step: stored eps rows, then one tail
+    def _step_plan(self, frames_total: int, window: int, h: int, w: int):
+        """The ``ops.TileRecord`` (plan, tables on the device) of a latent of ``frames_total`` x ``h`` x ``w`` cut into patches:
+        frame windows of ``window`` (``window_stride``; without it one window, the whole video) times tiles of ``tile_size``
+        (without it one tile, the whole frame).  None where neither is set: the step is one patch and needs no plan."""
+        if self.window_stride is None and self.tile_size is None:
+            return None
         key = (int(frames_total), int(window), int(h), int(w))
-        rec = self._tile_plans.get(key)
+        rec = self._step_plans.get(key)
         if rec is None:
-            stride = self.window_stride if self.window_stride is not None else window
-            pl = tile_plan.plan(h, w, self.tile_size, self.tile_stride, self.tile_weights, frames_total=frames_total,
-                                window=window, window_stride=stride, window_weights=self.window_weights)
-            rec = self._tile_plans[key] = ops.TileRecord(pl, self.unet.device)
+            size, stride = ((h, w), (h, w)) if self.tile_size is None else (self.tile_size, self.tile_stride)
+            pl = tile_plan.plan(h, w, size, stride, self.tile_weights, frames_total=frames_total, window=window,
+                                window_stride=window if self.window_stride is None else self.window_stride,
+                                window_weights=self.window_weights)
+            rec = self._step_plans[key] = ops.TileRecord(pl, self.unet.device, space=self.tile_size is not None)
         return rec
 
-    @staticmethod
-    def _patch_conditioning(cond: VideoConditioning, part, th: int, tw: int) -> VideoConditioning:
-        """The conditioning of one UNet call on the patches ``part`` stacked as ``[patch][video]`` batch rows: every patch's crop
-        of the image latents at its own position; the embeddings and the added-time ids repeated."""
+    def _patch_conditioning(self, cond: VideoConditioning, part, th: int, tw: int) -> VideoConditioning:
+        """The conditioning of one UNet call on the patches ``part`` stacked as ``[patch][video]`` batch rows: with ``tile_size``
+        every patch's crop of the image latents at its own position, without it the image latents themselves; all rows
+        repeated per patch."""
         def rep(t):
             return t if len(part) == 1 else torch.cat([t] * len(part), dim=0)
 
         def crops(t):
+            if self.tile_size is None:
+                return rep(t)
             return torch.cat([t[:, :, :, y0:y0 + th, x0:x0 + tw] for *_, y0, x0 in part], dim=0).contiguous()
 
         guided = cond.guided
@@ -776,38 +681,70 @@ class StableVideoUNet(nn.Module):
             uncond_embeddings=rep(cond.uncond_embeddings) if guided else None,
             uncond_image_latents=crops(cond.uncond_image_latents) if guided else None)
 
-    def _forward_tiles(self, state: torch.Tensor, step: int, cond: VideoConditioning) -> torch.Tensor:
-        """One step of a latent of F_total x H x W as n_patch = n_win * n_ty * n_tx patches (frame windows times spatial tiles):
-        the UNet passes of the plain step on every patch's slice (``windows_per_call`` patches of all B videos per call, each
-        conditioned on its own crop), each call's eps rows stored to its slice of one [n_patch][B][W][th*tw][4] buffer per pass,
-        then ONE tail behind them (``sp_euler_step_tiles_f16`` / ``sp_dpmpp2m_step_tiles_f16``).  All four samplers take the
-        stored-eps route, as for windows."""
+    def _forward_stored_eps(self, state: torch.Tensor, step: int, cond: VideoConditioning) -> torch.Tensor:
+        """One step by the stored-eps route: the UNet passes leave their eps rows in HBM and ONE tail kernel follows with this
+        step's coefficients (host constants, so a captured graph of the step holds them).  Every sampler but plain Euler takes
+        it -- ``conv_out``'s fused Euler epilogue knows neither the solver's history nor the noise -- and so does every step
+        with a plan, whose tail must see all patches: a latent of F_total x H x W as n_patch = n_win * n_ty * n_tx patches
+        (frame windows of W = ``cond.num_frames`` frames times spatial tiles), the passes on every patch's slice
+        (``windows_per_call`` patches of all B videos per call, each conditioned on its own crop), each call's eps rows stored
+        to its slice of one [n_patch][B][W][th*tw][4] buffer per pass."""
         b, _, ft, h, w = state.shape
-        win = cond.num_frames if self.window_stride is not None else ft
-        rec = self._tile_plan(ft, win, h, w)
-        th, tw = rec.plan.tile
-        patches = rec.plan.patches()
         sigma = self._sigma_host[step]
         in_scale = 1.0 / math.sqrt(sigma * sigma + 1.0)
-        x = state if self.state_channels == 4 else state[:, :4]
-        ld_eps = self.unet.cfg.out_channels
-        rows = b * win * th * tw                                # eps rows of one patch of all videos
-        eps_c = torch.empty((len(patches) * rows, ld_eps), dtype=torch.float16, device=state.device)
-        eps_u = torch.empty_like(eps_c) if cond.guided else None
-        for k0 in range(0, len(patches), self.windows_per_call):
-            part = patches[k0:k0 + self.windows_per_call]
-            # [patch][video] batch rows: the layout of the eps buffer
-            xs = torch.cat([x[:, :, f0:f0 + win, y0:y0 + th, x0:x0 + tw] for _, _, _, f0, y0, x0 in part], dim=0).contiguous()
-            dst = slice(k0 * rows, (k0 + len(part)) * rows)
-            self._unet_passes(xs, self._patch_conditioning(cond, part, th, tw), step, in_scale,
-                              eps_out=(eps_c[dst], eps_u[dst] if cond.guided else None))
-        out = torch.empty_like(state)
-        common = dict(plan=rec, ld_eps=ld_eps, sigma=sigma, ld_guidance=cond.guidance_ld)
-        if self.stochastic:                                    # the noise of element (f, y, x), whichever patches cover it
-            common.update(seeds=cond.noise_seeds, step=step, noise_scale=self._noise_coef[step][-1])
-        guidance = cond.guidance32 if cond.guided else None
-        if self.state_channels == 8:
-            a, b_, c1, c2 = (self._noise_coef if self.stochastic else self._solver_coef)[step][:4]
-            return ops.dpmpp2m_step_tiles(state, eps_c, eps_u, guidance, out, a=a, b=b_, c1=c1, c2=c2, batch=b, **common)
-        sigma_next = self._noise_coef[step][0] if self.stochastic else self._sigma_host[step + 1]
-        return ops.euler_step_tiles(state, eps_c, eps_u, guidance, out, sigma_next=sigma_next, b=b, **common)
+        win = ft if self.window_stride is None else cond.num_frames
+        plan = self._step_plan(ft, win, h, w)
+        if plan is None:                                  # (a view for one video; else a copy of the four sample planes)
+            x = state[:, :4].contiguous() if self.state_channels == 8 else state
+            eps_c, eps_u = self._unet_passes(x, cond, step, in_scale)
+        else:
+            x = self.sample_of(state)
+            th, tw = plan.plan.tile
+            patches = plan.plan.patches()
+            rows = b * win * th * tw                          # eps rows of one patch of all videos
+            eps_c = torch.empty((len(patches) * rows, self.unet.cfg.out_channels), dtype=torch.float16, device=state.device)
+            eps_u = torch.empty_like(eps_c) if cond.guided else None
+            for k0 in range(0, len(patches), self.windows_per_call):
+                part = patches[k0:k0 + self.windows_per_call]
+                # [patch][video] batch rows: the layout of the eps buffer
+                xs = torch.cat([x[:, :, f0:f0 + win, y0:y0 + th, x0:x0 + tw] for _, _, _, f0, y0, x0 in part], dim=0).contiguous()
+                dst = slice(k0 * rows, (k0 + len(part)) * rows)
+                self._unet_passes(xs, self._patch_conditioning(cond, part, th, tw), step, in_scale,
+                                  eps_out=(eps_c[dst], eps_u[dst] if cond.guided else None))
+        return self._tail(state, eps_c, eps_u, torch.empty_like(state), step, cond, plan)
+
+    def _tail(self, state, eps_c, eps_u, out, step: int, cond: VideoConditioning, plan) -> torch.Tensor:
+        """The sampler update of ``state`` into ``out`` behind the stored eps rows.  The sampler gives the step's constants; what
+        the model was configured with gives the entry: the tiles entries with ``tile_size``; else the stochastic entries, with
+        the window arguments where ``window_stride`` is set; else the windows entries; else the rows entries."""
+        b, _, ft, h, w = state.shape
+        solver = self.state_channels == 8
+        if solver:                                        # (a, b, c1, c2), with noise (a, b, c1, c2, n)
+            coef = (self._noise_coef if self.stochastic else self._solver_coef)[step]
+            consts = dict(a=coef[0], b=coef[1], c1=coef[2], c2=coef[3], batch=b)
+        else:                                             # the sigma the Euler step goes to; with noise (sigma_down, n)
+            coef = self._noise_coef[step] if self.stochastic else (self._sigma_host[step + 1],)
+            sigma_to, consts = coef[0], dict(b=b)
+        # the noise of element (f, y, x), whichever patches cover it
+        noise = dict(noise_scale=coef[-1], seeds=cond.noise_seeds, step=step) if self.stochastic else {}
+        args = (state, eps_c, eps_u, cond.guidance32 if eps_u is not None else None, out)
+        kw = dict(ld_eps=eps_c.shape[1], sigma=self._sigma_host[step], ld_guidance=cond.guidance_ld, **consts, **noise)
+        if self.tile_size is not None:
+            if solver:
+                return ops.dpmpp2m_step_tiles(*args, plan=plan, **kw)
+            return ops.euler_step_tiles(*args, plan=plan, sigma_next=sigma_to, **kw)
+        kw.update(h=h, w=w)
+        if plan is not None:                              # window_stride alone: the frame half of the plan as arguments
+            fr = plan.plan.frames
+            kw.update(window=fr.window, stride=fr.stride, n_win=fr.n_win, weights=plan.wf)
+        if self.stochastic:
+            if solver:
+                return ops.dpmpp2m_sde_step(*args, frames_total=ft, **kw)
+            return ops.euler_ancestral_step(*args, frames_total=ft, sigma_down=sigma_to, **kw)
+        if plan is not None:
+            if solver:
+                return ops.dpmpp2m_step_windows(*args, frames_total=ft, **kw)
+            return ops.euler_step_windows(*args, frames_total=ft, sigma_next=sigma_to, **kw)
+        if solver:
+            return ops.dpmpp2m_step(*args, frames=ft, **kw)
+        return ops.euler_step(*args, frames=ft, sigma_next=sigma_to, **kw)
