@@ -13,38 +13,19 @@ on CPU tensors and yields its list of launches.  Per configuration the tests ass
 Nothing is launched and nothing is computed; every tensor of a forward is kept alive in the log, so addresses identify
 buffers."""
 import collections
-import types
 
 import pytest
 import torch
 
-from vdpp_amd.hip import ops
+from tests import launch_recorder
 from vdpp_amd.models import common, unet_hip, vae_hip
 from vdpp_amd.models.unet_spec import UNetConfig, random_state_dict
-
-Launch = collections.namedtuple("Launch", "name args kw")
 
 
 @pytest.fixture
 def log(monkeypatch):
     """The list of launches; the engines build and run on the CPU while it is active."""
-    launches = []
-
-    def recorder(name):
-        def f(*a, **k):
-            launches.append(Launch(name, a, k))
-            return 1024 if name.endswith("_bytes") else a[2] if name == "gemm" else None
-        return f
-
-    for name in dir(ops):
-        if isinstance(getattr(ops, name), types.FunctionType) and not name.startswith("_") \
-                and name not in ("zero_page", "last_error"):
-            monkeypatch.setattr(ops, name, recorder(name))
-    monkeypatch.setattr(common, "hip_device", lambda device, engine: torch.device(device))
-    stream = types.SimpleNamespace(cuda_stream=0, synchronize=lambda: None)
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: stream)
-    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: False)
-    return launches
+    return launch_recorder.install(monkeypatch.setattr)
 
 
 def counts(log):

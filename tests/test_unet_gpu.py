@@ -718,13 +718,14 @@ def test_config5_shape_fp8_attention_agrees_with_fp16():
     CPU oracle is out of reach, so the check is agreement of one diffusion step with spatial attention on fp8-e4m3
     MFMA against the same step on the fp16 kernels (which the oracle pins at reduced size), on the UPDATE the step
     applies.  Tolerance 3e-2 relative L2, plus determinism of the fp8 route."""
+    from vdpp_amd.models import common
     from vdpp_amd.models.svd_unet import StableVideoUNet
 
     ts = StableVideoUNet._default_timestep_schedule(30)
-    m16 = StableVideoUNet.from_random_init(ts, seed=0, device=DEV)
+    m16 =StableVideoUNet.from_random_init(ts, seed=0, device=DEV)
     u8 = type(m16.unet).__new__(type(m16.unet))
     u8.__dict__.update(m16.unet.__dict__)               # same packed weights, no second 3 GB copy
-    u8.fp8_attention, u8._fp8_ws, u8._gn_ws = True, {}, None
+    u8.fp8_attention, u8._scratch = True, common.StreamScratch(u8.device)
     m8 = StableVideoUNet(unet=u8, timesteps=ts)
     assert not m16.unet.fp8_attention
     for m in (m16, m8):

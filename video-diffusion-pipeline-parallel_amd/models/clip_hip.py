@@ -107,12 +107,12 @@ def random_state_dict(spec: CLIPVisionSpec, seed: int = 0, device="cpu", dtype=t
     return sd
 
 
-class CLIPVisionHIP:
+class CLIPVisionHIP(common._Engine):
     """``CLIPVisionModelWithProjection.forward(pixel_values).image_embeds`` on a HIP device."""
 
     def __init__(self, spec: CLIPVisionSpec, state_dict: dict, device):
-        self.spec = spec
-        self.device = dev = common.hip_device(device, "CLIPVisionHIP")
+        super().__init__(device)
+        self.spec, dev = spec, self.device
         c, heads = spec.hidden_size, spec.num_attention_heads
         if c % 64 or spec.intermediate_size % 64 or c % heads or (c // heads) % 8 or c // heads > 128:
             raise ValueError("unsupported widths: hidden/intermediate multiples of 64, head width a multiple of 8 <= 128")
@@ -150,35 +150,19 @@ class CLIPVisionHIP:
         self.post_ln = _Norm(sd, "post_layernorm", dev, spec.layer_norm_eps)
         self.proj_w = W.pack_linear(state_dict["visual_projection.weight"]).to(dev)   # (projection_dim, C), no bias
 
-    def _buf(self, rows, c):
-        return torch.empty((rows, c), dtype=torch.float16, device=self.device)
-
-    def _gemm(self, layer: _Dense, a, m, **kw):
-        out = kw.pop("out", None)
-        if out is None:
-            out = self._buf(m, layer.n)
-        ops.gemm(a, layer.w, out, m=m, n=layer.n, cin=layer.cin, bias=layer.bias, lda=a.shape[1],
-                 ln_colsum=layer.colsum, **kw)
-        return out
-
-    def _ln_stats(self, layer: _Dense, x):
-        st = torch.empty((x.shape[0], 2), dtype=torch.float32, device=self.device)
-        ops.ln_stats(x, st, rows=x.shape[0], c=x.shape[1], eps=layer.ln_eps)
-        return st
-
     def _run_layer(self, L, x, b, seq):
         """One pre-LayerNorm encoder layer on the hidden state ``x`` [b*seq][C] -> the next hidden state."""
         sp = self.spec
         c, heads = sp.hidden_size, sp.num_attention_heads
         m, hd = b * seq, c // heads
-        qkv = self._gemm(L["qkv"], x, m, ln_stats=self._ln_stats(L["qkv"], x))
+        qkv = self._dense(L["qkv"], x, m, ln_stats=self._ln_pass(L["qkv"], x)).t
         o = self._buf(m, c)
         ops.attn_small(qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:], o, ldq=3 * c, ldk=3 * c, ldv=3 * c, ldo=c, batch=b,
                        seq=seq, heads=heads, head_dim=hd, scale=1.0 / math.sqrt(hd))
-        x = self._gemm(L["out"], o, m, res1=x, r1scale=1.0)
-        f = self._gemm(L["fc1"], x, m, ln_stats=self._ln_stats(L["fc1"], x))
+        x = self._dense(L["out"], o, m, res1=x, r1scale=1.0).t
+        f = self._dense(L["fc1"], x, m, ln_stats=self._ln_pass(L["fc1"], x)).t
         ops.gelu(f, f, quick=sp.hidden_act == "quick_gelu")
-        return self._gemm(L["fc2"], f, m, res1=x, r1scale=1.0)
+        return self._dense(L["fc2"], f, m, res1=x, r1scale=1.0).t
 
     def __call__(self, pixel_values):
         """pixel_values: fp16 (B, 3, image_size, image_size), already resized / normalised by the CLIPImageProcessor

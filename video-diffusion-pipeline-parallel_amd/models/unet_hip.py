@@ -100,7 +100,7 @@ class _Skips:
         return cat if cat.gn_part is not None and cat.gn_part_b is not None else _Act(cat.t)
 
 
-class SVDUNetHIP:
+class SVDUNetHIP(common._Engine):
     # fp8 attention pays a quantise pass over q/k/v: below ~1k tokens per frame (the 576- and 144-token levels) the
     # fp16 kernel is faster (tools/bench_attn.py: 46 vs 56 us at 576 tokens, 1907 vs 1580 us at 9216)
     FP8_MIN_SEQ = 1024
@@ -120,27 +120,18 @@ class SVDUNetHIP:
         most ~1.1-1.25x the ordinary kernel on data where that happens all the time (after 64 flagged waves the remaining
         workgroups hand their blocks to the ordinary kernel at once: csrc/attention_long.hip, DESIGN.md section 3;
         ``tools/long_attn_flags.py`` counts the cases on a given set of weights)."""
-        self.cfg = cfg
+        super().__init__(device)        # (with the switches of the statistics hand-off: VDPP_GN_EPILOGUE, _RES, VDPP_LN_OUT_WIDE)
+        self.cfg, dev = cfg, self.device
         self.fp8_attention = (os.environ.get("VDPP_FP8_ATTN") == "1") if fp8_attention is None else bool(fp8_attention)
         self.long_attention = (os.environ.get("VDPP_LONG_ATTN", "1") != "0") if long_attention is None else bool(long_attention)
         # the 16 transformer-entry GroupNorms folded into proj_in where a frame is whole tiles (VDPP_FOLD_GN=0: never)
         self.fold_groupnorm = os.environ.get("VDPP_FOLD_GN", "1") != "0"
-        # statistics of a resnet's second norms (norm2 / temporal norm2: inputs without a residual) out of the producing
-        # convolution's epilogue where a frame is whole 256-row tiles (VDPP_GN_EPILOGUE=0: always the statistics pass)
-        self.gn_from_epilogue = os.environ.get("VDPP_GN_EPILOGUE", "1") != "0"
-        # ... also for outputs that residuals are added to (the final tile is rebuilt in LDS and summed there); 0: only
-        # the no-residual producers (sums straight from the accumulators)
-        self.gn_epilogue_residual = os.environ.get("VDPP_GN_EPILOGUE_RES", "1") != "0"
         # a resnet's 1x1 shortcut convolution as an extra linear tap of its second 3x3 convolution (levels with more rows
         # than the split-K / small-tile routes take: the fused contraction runs on the 256-row ping-pong tiles)
         self.fold_shortcut = os.environ.get("VDPP_FOLD_SHORTCUT", "1") != "0"
-        # LayerNorm row statistics from the producing contraction's epilogue also for rows of three / four column tiles
-        # (1,280 channels at the 576-token level)
-        self.ln_out_wide = os.environ.get("VDPP_LN_OUT_WIDE", "1") != "0"
         # the up blocks' "nearest x2, then 3x3" convolutions as four 2x2 phase convolutions with pre-summed weights (K = 4*C
         # instead of 9*C; _upsample_plan has the rule).  VDPP_UPSAMPLE_PHASES=0: always the nine-tap gather
         self.upsample_phases = os.environ.get("VDPP_UPSAMPLE_PHASES", "1") != "0"
-        self.device = dev = common.hip_device(device, "SVDUNetHIP")
         sd = state_dict
         self._temb_w, self._temb_b, self._temb_n = [], [], 0
         self._xf_all = []
@@ -197,22 +188,14 @@ class SVDUNetHIP:
         self.temb_b = torch.cat(self._temb_b, dim=0).contiguous()
         del self._temb_w, self._temb_b
         self._group_small_gemvs()
-        self._gn_ws = None
-        self._sk_ws = {}
         self._pos_cache = {}
-        self._fp8_ws = {}
-        self._long_ws = {}
 
     def release_stream_state(self) -> None:
-        """Drop every per-stream scratch buffer (GroupNorm partials, split-K slabs, fp8 operands).  They are keyed by
-        the raw handle of the HIP stream a forward ran on, and a destroyed stream's handle can be handed out again: a
-        caller that creates streams per run calls this when it retires them (``StableVideoUNet.clear_conditioning`` and
-        ``enable_graphs(False)`` do), otherwise the streams must outlive the model.  The next forward on any stream
-        simply allocates again."""
-        self._gn_ws = None
-        self._sk_ws = {}
-        self._fp8_ws = {}
-        self._long_ws = {}
+        """Drop every per-stream scratch buffer (``common.StreamScratch``).  They are keyed by the raw handle of the HIP
+        stream a forward ran on, and a destroyed stream's handle can be handed out again: a caller that creates streams
+        per run calls this when it retires them (``StableVideoUNet.clear_conditioning`` and ``enable_graphs(False)`` do),
+        otherwise the streams must outlive the model.  The next forward on any stream simply allocates again."""
+        self._scratch.clear()
 
     # ------------------------------------------------------------------ weight packing
     def _reg_temb(self, sd, p):
@@ -353,96 +336,18 @@ class SVDUNetHIP:
         )
 
     # ------------------------------------------------------------------ kernel helpers
-    def _buf(self, rows, c):
-        return torch.empty((rows, c), dtype=torch.float16, device=self.device)
-
-    def _gemm(self, r: _Run, layer: _Dense, a, *, m=None, conv=None, ln_next=None, ln_out=None, **kw) -> _Act:
-        """One contraction on the plain tensor ``a``; returns its output with the statistics the epilogue left.
-        ``ln_next``: the contraction that will consume this output through a folded LayerNorm.  Where one tile spans a
-        whole output row (256 / 320 channels: level 0) the epilogue leaves that LayerNorm's (mean, rstd) in the returned
-        record and _ln_stats takes them from there instead of reading the tensor again (512 / 640 channels, level 1: two
-        tiles per row, their sums meet in a 16-byte-per-row scratch).  ``ln_out``: the caller has decided that already
-        and the statistics go there (_ff_pair: a chunk's rows of the whole tensor's statistics)."""
+    def _gemm(self, r: _Run, layer: _Dense, a, *, m=None, gn_next=False, **kw) -> _Act:
+        """``common._Engine._dense`` at the level ``r`` stands on.  ``gn_next``: this output goes straight into a GroupNorm
+        (no residual in between) whose instances are whole frames."""
         m = r.m if m is None else m
-        out = kw.pop("out", None)
-        # ``w_groups`` = (w_f [instances][n][c] fp16, bias_f [instances][n] fp32, rows per instance): a GroupNorm folded
-        # into this linear layer (ops.groupnorm_fold_linear) -- every instance's rows meet their own scaled weights
-        w_groups = kw.pop("w_groups", None)
-        weight, bias = kw.pop("weight", layer.w), layer.bias      # (``weight``: another pack of the layer's weights)
-        if w_groups is not None:
-            weight, bias = w_groups[0], None
-            kw.update(bias2=w_groups[1], bias2_rows=w_groups[2], w_group_rows=w_groups[2],
-                      w_group_stride=w_groups[0].shape[1] * w_groups[0].shape[2])
-        ws = r.sk_ws if m <= self.SPLITK_MAX_ROWS else None
-        # ``gn_next``: this output goes straight into a GroupNorm (no residual in between): where the tiles allow it the
-        # epilogue leaves per-tile column sums in the returned record and _gn folds them instead of reading the tensor again
-        gn_part = None
-        if kw.pop("gn_next", False) and self.gn_from_epilogue and m % 256 == 0 and layer.n == layer.n_true \
-                and not layer.geglu and (layer.n % 320 == 0 or layer.n % 256 == 0) and r.hw % 256 == 0 \
-                and layer.colsum is None and ln_next is None and "euler" not in kw and w_groups is None \
-                and (self.gn_epilogue_residual or (kw.get("res1") is None and kw.get("res2") is None)):
-            gn_part = torch.empty((m // 256, 2, layer.n, 2), dtype=torch.float32, device=self.device)
-            kw.update(gn_part=gn_part)
-        st = ln_out
-        if st is None and ln_next is not None and self._ln_out_ok(layer, m) and "euler" not in kw:
-            st = torch.empty((m, 2), dtype=torch.float32, device=self.device)
-        if st is not None:
-            kw.update(ln_out=st, ln_out_eps=ln_next.ln_eps)
-            tiles = layer.n_true // (320 if layer.n_true % 320 == 0 else 256)
-            ws = torch.empty((m, 2 * tiles), dtype=torch.float32, device=self.device) if tiles > 1 else None
-        if out is None:
-            out = self._buf(m, layer.n_true)
-        elif out.shape != (m, layer.n_true):
-            raise RuntimeError(f"destination {tuple(out.shape)} does not match the contraction's output ({m}, {layer.n_true})")
-        # operands may be column slices of wider row-major buffers (the halves of a concatenation buffer): row pitches
-        # come from the tensors
-        for key, ld in (("res1", "ldr1"), ("res2", "ldr2")):
-            if kw.get(key) is not None:
-                kw.setdefault(ld, kw[key].stride(0))
-        n_store = layer.n_true if (layer.n_true != (layer.n // 2 if layer.geglu else layer.n)) else 0
-        temporal = (r.f, r.hw) if layer.mode == ops.A_TEMPORAL3 else None
-        if layer.colsum is not None and "ln_stats" not in kw:
-            raise RuntimeError("this contraction carries a folded LayerNorm: pass ln_stats")
-        ops.gemm(a, weight, out, m=m, n=layer.n, cin=layer.cin, mode=layer.mode, conv=conv, temporal=temporal,
-                 bias=bias, geglu=layer.geglu, n_store=n_store, ldd=out.stride(0), lda=a.stride(0),
-                 ln_colsum=layer.colsum, workspace=ws, **kw)
-        return _Act(out, gn_part=gn_part, ln_stats=st, ln_eps=ln_next.ln_eps if st is not None else None)
-
-    def _ln_out_ok(self, layer: _Dense, m: int) -> bool:
-        """Can this contraction's epilogue leave the next LayerNorm's row statistics?  A row = one or two column tiles at
-        any row count; three or four (1,024 / 1,280 channels: the 576-token level) only where the large ping-pong tiles
-        are what the contraction runs on anyway (more rows than the small-tile / split-K routes take)."""
-        if layer.n != layer.n_true or layer.geglu:
-            return False
-        return layer.n_true in (256, 320, 512, 640) or (self.ln_out_wide and layer.n_true in (768, 960, 1024, 1280)
-                                                        and m > self.SPLITK_MAX_ROWS)
-
-    def _ln_stats(self, layer: _Dense, x: _Act):
-        """(mean, rstd) per row of x for the LayerNorm folded into ``layer``: left by x's producer, or a pass over x."""
-        if x.ln_stats is not None and x.ln_eps == layer.ln_eps:
-            return x.ln_stats
-        return self._ln_pass(layer, x.t)
-
-    def _ln_pass(self, layer: _Dense, x, **kw):
-        st = torch.empty((x.shape[0], 2), dtype=torch.float32, device=self.device)
-        ops.ln_stats(x, st, rows=x.shape[0], c=x.shape[1], eps=layer.ln_eps, **kw)
-        return st
+        return self._dense(layer, a, m, temporal=(r.f, r.hw) if layer.mode == ops.A_TEMPORAL3 else None,
+                           frame_rows=r.hw if gn_next else 0,
+                           workspace=r.sk_ws if m <= self.SPLITK_MAX_ROWS else None, **kw)
 
     def _gn(self, r: _Run, norm: _Norm, a: _Act, *, temporal: bool, silu: bool):
-        """GroupNorm of ``a`` -> plain tensor.  Where a's producer left its column sums (for a concatenation buffer: both
-        producers, an up block's first norm) and an instance is whole 256-row tiles, they replace the statistics pass."""
-        x, c, groups = a.t, a.t.shape[1], self.cfg.norm_groups
+        """GroupNorm of ``a`` per frame, or (``temporal``) per video -> plain tensor."""
         inst, rows = (r.b, r.f * r.hw) if temporal else (r.b * r.f, r.hw)
-        y = self._buf(x.shape[0], c)
-        if a.gn_part is not None and rows % 256 == 0:
-            stats = torch.empty((inst, groups, 2), dtype=torch.float32, device=self.device)
-            cat = dict(part_b=a.gn_part_b, c_a=a.c_a) if a.gn_part_b is not None else {}
-            ops.groupnorm_tile_sums(x, a.gn_part, norm.g, norm.b, y, instances=inst, rows=rows, c=c, groups=groups,
-                                    eps=norm.eps, silu=silu, stats=stats, ldx=x.stride(0), **cat)
-            return y
-        ops.groupnorm(x, norm.g, norm.b, y, instances=inst, rows=rows, c=c, groups=groups,
-                      eps=norm.eps, silu=silu, ws=r.gn_ws, ldx=x.stride(0))
-        return y
+        return self._groupnorm(norm, a, inst, rows, silu, ws=r.gn_ws)
 
     def _upsample_plan(self, us: _Dense, n_img, hin, win):
         """(phases, sums) for the upsampling convolution of ``n_img`` images of ``hin`` x ``win``: run it as four 2x2 phase
@@ -483,7 +388,7 @@ class SVDUNetHIP:
                 and r.m % 256 == 0:
             # the shortcut convolution rides in conv2's K loop (sp_gemm_desc.a2): no skip tensor, and no residual in front of
             # the temporal block's first norm (its column sums then come straight from the accumulators)
-            s = self._gemm(r, p["c2sc"], t, conv=geom, a2=x, cin2=p["c2sc"].cin2, lda2=x.stride(0), gn_next=True)
+            s = self._gemm(r, p["c2sc"], t, conv=geom, a2=x, cin2=p["c2sc"].cin2, gn_next=True)
         else:
             skip = x if p["sc"] is None else self._gemm(r, p["sc"], x).t
             s = self._gemm(r, p["c2"], t, conv=geom, res1=skip, r1scale=1.0, gn_next=True)
@@ -517,19 +422,11 @@ class SVDUNetHIP:
             ops.attn_temporal(q, k, v, o, ldq=3 * c, ldk=3 * c, ldv=3 * c, ldo=c, batch=r.b, frames=r.f, hw=r.hw,
                               heads=heads)
         elif self.fp8_attention and r.hw >= self.FP8_MIN_SEQ:
-            need = ops.attn_fp8_ws_bytes(r.b * r.f, r.hw, heads)
-            skey = torch.cuda.current_stream(self.device).cuda_stream     # one scratch per HIP stream
-            ws = self._fp8_ws.get(skey)
-            if ws is None or ws.numel() < need:
-                ws = self._fp8_ws[skey] = torch.empty(need, dtype=torch.uint8, device=self.device)
+            ws = self._scratch.get("fp8", ops.attn_fp8_ws_bytes(r.b * r.f, r.hw, heads))
             ops.attn_spatial_fp8(q, k, v, o, ws, ldq=3 * c, ldk=3 * c, ldv=3 * c, ldo=c, batch=r.b * r.f, seq=r.hw,
                                  heads=heads)
         elif self.long_attention and r.hw >= self.LONG_ATTENTION_MIN_SEQ and r.hw % 256 == 0:
-            need = ops.attn_long_ws_bytes(r.b * r.f, r.hw, heads)
-            skey = torch.cuda.current_stream(self.device).cuda_stream     # one set of flag words per HIP stream
-            ws = self._long_ws.get(skey)
-            if ws is None or ws.numel() < need:
-                ws = self._long_ws[skey] = torch.empty(need, dtype=torch.uint8, device=self.device)
+            ws = self._scratch.get("long", ops.attn_long_ws_bytes(r.b * r.f, r.hw, heads))
             ops.attn_spatial_long(q, k, v, o, ws, ldq=3 * c, ldk=3 * c, ldv=3 * c, ldo=c, batch=r.b * r.f, seq=r.hw,
                                   heads=heads)
         else:
@@ -638,25 +535,14 @@ class SVDUNetHIP:
         if h % 8 or w % 8:
             raise ValueError("latent height/width must be multiples of 8 (three stride-2 levels)")
         temb_dim, c0 = cfg.time_embed_dim, cfg.block_out_channels[0]
+        # GroupNorm partial-sum scratch for the widest norm of the net (an up resnet's concatenation buffer)
         max_c = 2 * max(cfg.block_out_channels)
-        ws_bytes = ops.groupnorm_ws_bytes(b * frames, frames * h * w, max_c, cfg.norm_groups)
-        # GroupNorm partial-sum scratch: one per HIP stream, forwards on different streams may overlap in time
-        if self._gn_ws is None:
-            self._gn_ws = {}
-        skey = torch.cuda.current_stream(dev).cuda_stream
-        gn_ws = self._gn_ws.get(skey)
-        if gn_ws is None or gn_ws.numel() < ws_bytes:
-            gn_ws = self._gn_ws[skey] = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-
-        # split-K scratch for the levels with at most SPLITK_MAX_ROWS rows (up to 8 fp32 slabs of rows x channels), per stream
-        sk_bytes = 0
-        for lvl, c in enumerate(cfg.block_out_channels):
-            rows = b * frames * (h >> min(lvl, 3)) * (w >> min(lvl, 3))
-            if rows <= self.SPLITK_MAX_ROWS:
-                sk_bytes = max(sk_bytes, 8 * rows * c * 4)
-        sk_ws = self._sk_ws.get(skey)
-        if sk_bytes and (sk_ws is None or sk_ws.numel() < sk_bytes):
-            sk_ws = self._sk_ws[skey] = torch.empty(sk_bytes, dtype=torch.uint8, device=dev)
+        gn_ws = self._scratch.get("gn", ops.groupnorm_ws_bytes(b * frames, frames * h * w, max_c, cfg.norm_groups))
+        # split-K scratch for the levels with at most SPLITK_MAX_ROWS rows (up to 8 fp32 slabs of rows x channels)
+        level_rows = [b * frames * (h >> min(lvl, 3)) * (w >> min(lvl, 3)) for lvl in range(len(cfg.block_out_channels))]
+        sk_bytes = max([8 * rows * c * 4 for rows, c in zip(level_rows, cfg.block_out_channels)
+                        if rows <= self.SPLITK_MAX_ROWS], default=0)
+        sk_ws = self._scratch.get("splitk", sk_bytes) if sk_bytes else None
 
         # ---- embeddings: M = 1 GEMVs when the batch shares timestep and ids, else one row per video
         nt, nids = t_value.numel(), added_ids32.numel()

@@ -32,6 +32,7 @@ with the random weights available here that cannot be probed, see DESIGN.md sect
 from __future__ import annotations
 
 import math
+import os
 from dataclasses import dataclass
 from typing import Iterator, Sequence
 
@@ -206,24 +207,22 @@ def attn_row_blocks(hw: int, cap_elems: int = ATTN_SCRATCH_ELEMS):
     return r, [(r0, min(r0 + r, hw)) for r0 in range(0, hw, r)]
 
 
-class _VAEKernels:
-    """Kernel helpers shared by the decoder and the encoder engines."""
+class _VAEKernels(common._Engine):
+    """What the decoder and the encoder engines share beyond ``common._Engine``: the mid-block attention."""
 
-    def _init_common(self, cfg, device):
+    def __init__(self, cfg, device):
+        super().__init__(device)
         self.cfg = cfg
-        self.device = dev = common.hip_device(device, type(self).__name__)
         if any(v % 64 for v in cfg.block_out_channels):
             raise ValueError("block_out_channels must be multiples of 64 (MFMA K-steps)")
-        self._ws = {}
+        self.gn_epilogue_residual = True         # (the VAE has no switch for column sums behind a residual)
         # mid-block attention logits in fp32 wherever the token count allows (a multiple of 256); VDPP_VAE_FP16_SCORES=1
         # selects the round-3 composition with fp16 scores everywhere (A/B, tests)
-        self.fp32_scores = __import__("os").environ.get("VDPP_VAE_FP16_SCORES") != "1"
-        self.gn_from_epilogue = __import__("os").environ.get("VDPP_GN_EPILOGUE", "1") != "0"
+        self.fp32_scores = os.environ.get("VDPP_VAE_FP16_SCORES") != "1"
         # frames of more tokens than this take the row-blocked attention with the streaming softmax (_run_attn);
         # VDPP_VAE_LONG_ATTN_FROM=0 sends every frame there (A/B, tests), attn_scratch_elems caps its fp32 score scratch
-        self.attn_long_from = int(__import__("os").environ.get("VDPP_VAE_LONG_ATTN_FROM", ATTN_LONG_FROM))
+        self.attn_long_from = int(os.environ.get("VDPP_VAE_LONG_ATTN_FROM", ATTN_LONG_FROM))
         self.attn_scratch_elems = ATTN_SCRATCH_ELEMS
-        return dev
 
     def _attn(self, sd, p, c):
         dev = self.device
@@ -231,46 +230,6 @@ class _VAEKernels:
                     k=_Dense.linear(sd, p + ".to_k", dev),
                     wv=sd[p + ".to_v.weight"].to(dev, torch.float16).contiguous(),      # A operand of V^T = W_v X^T
                     bv=_f32(sd[p + ".to_v.bias"], dev), out=_Dense.linear(sd, p + ".to_out.0", dev))
-
-    def _buf(self, rows, c):
-        return torch.empty((rows, c), dtype=torch.float16, device=self.device)
-
-    def _gemm(self, layer: _Dense, a, m, *, conv=None, temporal=None, gn_rows=0, **kw) -> _Act:
-        """One contraction on the plain tensor ``a``.  ``gn_rows`` > 0: the output goes straight into a GroupNorm whose
-        instances are multiples of that many rows (a frame): where the tiles allow it (256- / 320-wide column tiles, whole
-        256-row tiles per frame) the epilogue leaves per-tile column sums in the returned record and ``_gn`` folds them
-        instead of reading the tensor again (round 5, ``sp_gemm_desc.gn_part``; the 128-channel level has no such tiles)."""
-        out = kw.pop("out", None)
-        if out is None:
-            out = self._buf(m, layer.n_true)
-        n_store = layer.n_true if layer.n_true != layer.n else 0
-        part = None
-        if (gn_rows and self.gn_from_epilogue and gn_rows % 256 == 0 and m % 256 == 0 and n_store == 0
-                and (layer.n % 256 == 0 or layer.n % 320 == 0)):
-            part = torch.empty((m // 256, 2, layer.n, 2), dtype=torch.float32, device=self.device)
-            kw.update(gn_part=part)
-        ops.gemm(a, layer.w, out, m=m, n=layer.n, cin=layer.cin, mode=layer.mode, conv=conv, temporal=temporal,
-                 bias=layer.bias, n_store=n_store, ldd=layer.n_true, lda=a.shape[1], **kw)
-        return _Act(out, gn_part=part)
-
-    def _gn(self, norm: _Norm, a: _Act, inst, rows, silu):
-        """GroupNorm of ``a`` -> plain tensor; the column sums a's producer left replace the statistics pass."""
-        x, c = a.t, a.t.shape[1]
-        if a.gn_part is not None and rows % 256 == 0:
-            y = self._buf(x.shape[0], c)
-            stats = torch.empty((inst, self.cfg.norm_groups, 2), dtype=torch.float32, device=self.device)
-            ops.groupnorm_tile_sums(x, a.gn_part, norm.g, norm.b, y, instances=inst, rows=rows, c=c, groups=self.cfg.norm_groups,
-                                    eps=norm.eps, silu=silu, stats=stats)
-            return y
-        need = ops.groupnorm_ws_bytes(inst, rows, c, self.cfg.norm_groups)
-        key = torch.cuda.current_stream(self.device).cuda_stream
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            ws = self._ws[key] = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=self.device)
-        y = self._buf(x.shape[0], c)
-        ops.groupnorm(x, norm.g, norm.b, y, instances=inst, rows=rows, c=c, groups=self.cfg.norm_groups, eps=norm.eps,
-                      silu=silu, ws=ws)
-        return y
 
     def _check_tokens(self, hw):
         """The token counts the mid-block attention takes, checked before anything is launched."""
@@ -285,9 +244,9 @@ class _VAEKernels:
         """diffusers ``Attention(heads=1, dim_head=C, norm_num_groups=32, residual_connection=True)`` per image."""
         c, m = p["c"], n_img * hw
         self._check_tokens(hw)
-        t = self._gn(p["norm"], x, n_img, hw, False)
-        q = self._gemm(p["q"], t, m).t
-        k = self._gemm(p["k"], t, m).t
+        t = self._groupnorm(p["norm"], x, n_img, hw, False)
+        q = self._dense(p["q"], t, m).t
+        k = self._dense(p["k"], t, m).t
         o = self._buf(m, c)
         vt = self._buf(c, hw)
         scale = 1.0 / math.sqrt(c)
@@ -333,7 +292,7 @@ class _VAEKernels:
                 ops.gemm(scores, vt, o[r], m=hw, n=c, cin=hw, bias=p["bv"])                # O = P V + b_v
             del scores
         del vt, q, k, t
-        return self._gemm(p["out"], o, m, res1=x.t, r1scale=1.0, gn_rows=hw)
+        return self._dense(p["out"], o, m, res1=x.t, r1scale=1.0, frame_rows=hw)
 
 
 class TemporalDecoderHIP(_VAEKernels):
@@ -341,7 +300,8 @@ class TemporalDecoderHIP(_VAEKernels):
     vae checkpoint with the prefix stripped (or ``random_state_dict``)."""
 
     def __init__(self, cfg: VAEDecoderConfig, state_dict: dict, device):
-        dev = self._init_common(cfg, device)
+        super().__init__(cfg, device)
+        dev = self.device
         sd = state_dict
         ch = list(cfg.block_out_channels)
         c = ch[-1]
@@ -386,18 +346,18 @@ class TemporalDecoderHIP(_VAEKernels):
         blended by the (switched) AlphaBlender."""
         hw, m = h * w, b * f * h * w
         geom = (b * f, h, w, h, w, 1, 0)
-        t = self._gn(p["n1"], x, b * f, hw, True)
-        t = self._gemm(p["c1"], t, m, conv=geom, gn_rows=hw)
-        t = self._gn(p["n2"], t, b * f, hw, True)
-        skip = x if p["sc"] is None else self._gemm(p["sc"], x.t, m)
-        s = self._gemm(p["c2"], t, m, conv=geom, res1=skip.t, r1scale=1.0, gn_rows=hw)
+        t = self._groupnorm(p["n1"], x, b * f, hw, True)
+        t = self._dense(p["c1"], t, m, conv=geom, frame_rows=hw)
+        t = self._groupnorm(p["n2"], t, b * f, hw, True)
+        skip = x if p["sc"] is None else self._dense(p["sc"], x.t, m)
+        s = self._dense(p["c2"], t, m, conv=geom, res1=skip.t, r1scale=1.0, frame_rows=hw)
         del t, skip
-        t = self._gn(p["tn1"], s, b, f * hw, True)
-        t = self._gemm(p["tc1"], t, m, temporal=(f, hw), gn_rows=hw)
-        t = self._gn(p["tn2"], t, b, f * hw, True)
+        t = self._groupnorm(p["tn1"], s, b, f * hw, True)
+        t = self._dense(p["tc1"], t, m, temporal=(f, hw), frame_rows=hw)
+        t = self._groupnorm(p["tn2"], t, b, f * hw, True)
         # (1-sig)*s + sig*(s + conv2(t)) = s + sig*conv2(t)
-        return self._gemm(p["tc2"], t, m, temporal=(f, hw), oscale=p["temporal_weight"], res1=s.t, r1scale=1.0,
-                          gn_rows=hw if gn_next else 0)
+        return self._dense(p["tc2"], t, m, temporal=(f, hw), oscale=p["temporal_weight"], res1=s.t, r1scale=1.0,
+                           frame_rows=hw if gn_next else 0)
 
     # ------------------------------------------------------------------ public
     def _decode_chunk(self, src, src_strides, dst, dst_strides, *, flat0, n, frames_per_item, batch, frames, h, w,
@@ -410,7 +370,7 @@ class TemporalDecoderHIP(_VAEKernels):
                             strides=src_strides, h=h, w=w, cpad=self.conv_in.cin)
         b, f = batch, frames
         m = n * h * w
-        x = self._gemm(self.conv_in, rows, m, conv=(n, h, w, h, w, 1, 0), gn_rows=h * w)
+        x = self._dense(self.conv_in, rows, m, conv=(n, h, w, h, w, 1, 0), frame_rows=h * w)
         x = self._run_res(self.mid[0], x, b, f, h, w)
         x = self._run_attn(self.mid[1], x, n, h * w)
         x = self._run_res(self.mid[2], x, b, f, h, w)
@@ -419,10 +379,10 @@ class TemporalDecoderHIP(_VAEKernels):
                 # (a level's last resnet feeds the upsampling convolution: no norm behind it)
                 x = self._run_res(p, x, b, f, h, w, gn_next=not (us is not None and j == len(res) - 1))
             if us is not None:
-                x = self._gemm(us, x.t, n * 4 * h * w, conv=(n, h, w, 2 * h, 2 * w, 1, 1), gn_rows=4 * h * w)
+                x = self._dense(us, x.t, n * 4 * h * w, conv=(n, h, w, 2 * h, 2 * w, 1, 1), frame_rows=4 * h * w)
                 h, w = 2 * h, 2 * w
-        x = self._gn(self.norm_out, x, n, h * w, True)
-        x = self._gemm(self.conv_out, x, n * h * w, conv=(n, h, w, h, w, 1, 0)).t
+        x = self._groupnorm(self.norm_out, x, n, h * w, True)
+        x = self._dense(self.conv_out, x, n * h * w, conv=(n, h, w, h, w, 1, 0)).t
         if dst_strides is None:
             ops.vae_frames_out_u8(x, self.tco_w, self.tco_b, dst, batch=b, frames=f, h=h, w=w, flat0=flat0)
         else:
@@ -527,7 +487,8 @@ class ImageEncoderHIP(_VAEKernels):
     time (fp32, rounded once), keeping only the four mean channels that ``mode()`` returns."""
 
     def __init__(self, cfg: VAEDecoderConfig, state_dict: dict, device):
-        dev = self._init_common(cfg, device)
+        super().__init__(cfg, device)
+        dev = self.device
         sd = dict(state_dict)
         ch = list(cfg.block_out_channels)
         lc = cfg.latent_channels
@@ -567,11 +528,11 @@ class ImageEncoderHIP(_VAEKernels):
 
     def _run_res2d(self, p, x: _Act, n, h, w) -> _Act:
         m, geom = n * h * w, (n, h, w, h, w, 1, 0)
-        t = self._gn(p["n1"], x, n, h * w, True)
-        t = self._gemm(p["c1"], t, m, conv=geom)
-        t = self._gn(p["n2"], t, n, h * w, True)
-        skip = x if p["sc"] is None else self._gemm(p["sc"], x.t, m)
-        return self._gemm(p["c2"], t, m, conv=geom, res1=skip.t, r1scale=1.0)
+        t = self._groupnorm(p["n1"], x, n, h * w, True)
+        t = self._dense(p["c1"], t, m, conv=geom)
+        t = self._groupnorm(p["n2"], t, n, h * w, True)
+        skip = x if p["sc"] is None else self._dense(p["sc"], x.t, m)
+        return self._dense(p["c2"], t, m, conv=geom, res1=skip.t, r1scale=1.0)
 
     def encode_image_latents(self, image, num_frames: int):
         """image: fp16 (B, 3, H, W) in [-1, 1], noise augmentation already added (ref :126-136).  Returns the
@@ -594,18 +555,18 @@ class ImageEncoderHIP(_VAEKernels):
                              f"images per call")
         rows = self._buf(n * h * w, self.conv_in.cin)
         ops.vae_image_pack(image, rows, batch=n, h=h, w=w, cpad=self.conv_in.cin, flip=True)
-        x = self._gemm(self.conv_in, rows, n * h * w, conv=(n, h, w, h, w, 1, 0))
+        x = self._dense(self.conv_in, rows, n * h * w, conv=(n, h, w, h, w, 1, 0))
         for res, ds in self.down:
             for p in res:
                 x = self._run_res2d(p, x, n, h, w)
             if ds is not None:
-                x = self._gemm(ds, x.t, n * (h // 2) * (w // 2), conv=(n, h, w, h // 2, w // 2, 2, 0))
+                x = self._dense(ds, x.t, n * (h // 2) * (w // 2), conv=(n, h, w, h // 2, w // 2, 2, 0))
                 h, w = h // 2, w // 2
         x = self._run_res2d(self.mid[0], x, n, h, w)
         x = self._run_attn(self.mid[1], x, n, h * w)
         x = self._run_res2d(self.mid[2], x, n, h, w)
-        x = self._gn(self.norm_out, x, n, h * w, True)
-        x = self._gemm(self.conv_out, x, n * h * w, conv=(n, h, w, h, w, 1, 0)).t
+        x = self._groupnorm(self.norm_out, x, n, h * w, True)
+        x = self._dense(self.conv_out, x, n * h * w, conv=(n, h, w, h, w, 1, 0)).t
         out = torch.empty((n, self.cfg.latent_channels, num_frames, h, w), dtype=torch.float16, device=self.device)
         ops.vae_latent_out(x, out, batch=n, channels=self.cfg.latent_channels, frames=num_frames, h=h, w=w, flip=True)
         return out
