@@ -318,6 +318,26 @@ int sp_attn_spatial_fp8(const void *q, const void *k, const void *v, void *o, in
                         int64_t ldv, int64_t ldo, int batch, int seq, int heads, float scale,
                         void *workspace, int64_t workspace_bytes, const void *zero_page, void *stream);
 
+/* Fused single-head attention with a WIDE head (csrc/attention_wide.hip), per image b of a batch:
+ *   O[b] = softmax(scale * Q[b].K[b]^T).V[b] (+ bias)
+ * the mid-block attention of the VAE (diffusers Attention(heads=1, dim_head=C)), in one kernel and without a score
+ * matrix.  q, k, v, o: fp16 rows [batch*seq][head_dim] with row pitches ldq, ldk, ldv, ldo in elements (>= head_dim,
+ * multiples of 8; the rows may be columns of wider buffers), 16-byte aligned; image b owns rows b*seq .. (b+1)*seq-1.
+ * head_dim: 128, 256 or 512.  seq, batch: any positive counts (ragged key tiles and query blocks included).
+ * bias: fp32 [head_dim], 16-byte aligned, added in fp32 before the store (softmax rows sum to one, so this is b_v of
+ * V = X.W_v^T + b_v), or NULL.  scale: positive and finite.
+ * Numerical contract: logits are fp32 MFMA sums, never rounded to fp16 or clamped; online softmax statistics (running
+ * maximum and sum per row, exp2 with scale*log2(e) folded in) are fp32; probabilities are rounded to fp16 only as the
+ * operand of P.V; outputs accumulate in fp32 and are divided by the row sum once.  Finite inputs give finite outputs
+ * whatever the logits' magnitude.
+ * Tails: a key row at or beyond seq is read from row seq-1 of the same image and contributes exactly 0; a query row at
+ * or beyond seq is not stored.  No read or write touches a row outside [b*seq, (b+1)*seq) of its image, or a column
+ * outside [0, head_dim).
+ * Refused without a launch: null q/k/v/o, another head_dim, batch or seq <= 0, a pitch below head_dim or no multiple of 8,
+ * misaligned pointers, a scale that is not positive and finite. */
+int sp_attn_wide_f16(const void *q, const void *k, const void *v, void *o, int64_t ldq, int64_t ldk, int64_t ldv,
+                     int64_t ldo, const float *bias, int batch, int seq, int head_dim, float scale, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Layout / elementwise glue around the UNet (svd_unet.py:382-439).
  * ------------------------------------------------------------------------------------------- */

@@ -301,6 +301,15 @@ def attn_spatial(q, k, v, o, *, ldq, ldk, ldv, ldo, batch, seq, heads, scale=0.1
     return o
 
 
+def attn_wide(q, k, v, o, *, ldq, ldk, ldv, ldo, batch, seq, head_dim, scale, bias=None):
+    """Fused single-head attention with head_dim 128 / 256 / 512 (csrc/attention_wide.hip): fp32 logits and softmax
+    statistics, no score matrix; ``bias``: optional fp32 [head_dim] added to the output rows."""
+    with _Timed("attn_wide", 4.0 * batch * seq * seq * head_dim):
+        _check(load().sp_attn_wide_f16(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), ldq, ldk, ldv, ldo,
+                                       _ptr(bias), batch, seq, head_dim, scale, _stream()), "sp_attn_wide_f16")
+    return o
+
+
 def attn_long_ws_bytes(batch, seq, heads) -> int:
     return int(load().sp_attn_long_ws_bytes(batch, seq, heads))
 

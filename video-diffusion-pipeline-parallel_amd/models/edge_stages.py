@@ -44,7 +44,7 @@ def _read_local_checkpoint(model_dir: str, subfolder: str) -> tuple[dict, dict]:
     return sd, cfg
 
 
-def load_edge_engines(model_dir: str, device="cuda"):
+def load_edge_engines(model_dir: str, device="cuda", vae_attention=None):
     """``(clip, vae_encoder, vae_decoder)`` from a local Stable Video Diffusion checkpoint directory, as the reference's
     demo loads them by id (``CLIPVisionModelWithProjection.from_pretrained(.., subfolder="image_encoder")``,
     ``AutoencoderKLTemporalDecoder.from_pretrained(.., subfolder="vae")``: ref ``scripts/generate_video_demo.py:248-262``)."""
@@ -66,8 +66,10 @@ def load_edge_engines(model_dir: str, device="cuda"):
                            block_out_channels=tuple(vcfg.get("block_out_channels", v.block_out_channels)),
                            layers_per_block=vcfg.get("layers_per_block", v.layers_per_block),
                            scaling_factor=vcfg.get("scaling_factor", v.scaling_factor))
-    enc = ImageEncoderHIP(cfg, {k: t for k, t in vsd.items() if k.startswith(("encoder.", "quant_conv."))}, device)
-    dec = TemporalDecoderHIP(cfg, {k[len("decoder."):]: t for k, t in vsd.items() if k.startswith("decoder.")}, device)
+    enc = ImageEncoderHIP(cfg, {k: t for k, t in vsd.items() if k.startswith(("encoder.", "quant_conv."))}, device,
+                          attention=vae_attention)
+    dec = TemporalDecoderHIP(cfg, {k[len("decoder."):]: t for k, t in vsd.items() if k.startswith("decoder.")}, device,
+                             attention=vae_attention)
     return clip, enc, dec
 
 

@@ -210,9 +210,14 @@ def attn_row_blocks(hw: int, cap_elems: int = ATTN_SCRATCH_ELEMS):
 class _VAEKernels(common._Engine):
     """What the decoder and the encoder engines share beyond ``common._Engine``: the mid-block attention."""
 
-    def __init__(self, cfg, device):
+    def __init__(self, cfg, device, attention=None):
         super().__init__(device)
         self.cfg = cfg
+        # mid-block attention: "composed" (contractions + row softmax through a score matrix, the default) or "fused"
+        # (sp_attn_wide_f16: one kernel, no score matrix, any token count); VDPP_VAE_ATTENTION overrides the argument
+        self.attention = os.environ.get("VDPP_VAE_ATTENTION") or attention or "composed"
+        if self.attention not in ("composed", "fused"):
+            raise ValueError(f"attention must be 'composed' or 'fused', got {self.attention!r}")
         if any(v % 64 for v in cfg.block_out_channels):
             raise ValueError("block_out_channels must be multiples of 64 (MFMA K-steps)")
         self.gn_epilogue_residual = True         # (the VAE has no switch for column sums behind a residual)
@@ -229,10 +234,17 @@ class _VAEKernels(common._Engine):
         return dict(c=c, norm=_Norm(sd, p + ".group_norm", dev, 1e-6), q=_Dense.linear(sd, p + ".to_q", dev),
                     k=_Dense.linear(sd, p + ".to_k", dev),
                     wv=sd[p + ".to_v.weight"].to(dev, torch.float16).contiguous(),      # A operand of V^T = W_v X^T
+                    v=_Dense.linear(sd, p + ".to_v", dev) if self.attention == "fused" else None,
                     bv=_f32(sd[p + ".to_v.bias"], dev), out=_Dense.linear(sd, p + ".to_out.0", dev))
 
     def _check_tokens(self, hw):
         """The token counts the mid-block attention takes, checked before anything is launched."""
+        if self.attention == "fused":           # refuses only what the kernel refuses
+            c = self.cfg.block_out_channels[-1]
+            if c not in (128, 256, 512):
+                raise ValueError(f"mid-block attention: the fused kernel takes a width of 128, 256 or 512, not {c}; "
+                                 f"attention=\"composed\" takes every multiple of 64")
+            return
         if hw % 64:
             raise ValueError(f"mid-block attention: H*W = {hw} tokens per image must be a multiple of 64")
         if hw > self.attn_long_from and hw % 256:
@@ -248,8 +260,15 @@ class _VAEKernels(common._Engine):
         q = self._dense(p["q"], t, m).t
         k = self._dense(p["k"], t, m).t
         o = self._buf(m, c)
-        vt = self._buf(c, hw)
         scale = 1.0 / math.sqrt(c)
+        if self.attention == "fused":
+            # one kernel for all images of the chunk: V = X W_v^T + b_v as an ordinary projection, no score matrix, no
+            # row blocks, no V^T (sp_attn_wide_f16 transposes V on chip)
+            v = self._dense(p["v"], t, m).t
+            ops.attn_wide(q, k, v, o, ldq=c, ldk=c, ldv=c, ldo=c, batch=n_img, seq=hw, head_dim=c, scale=scale)
+            del v, q, k, t
+            return self._dense(p["out"], o, m, res1=x.t, r1scale=1.0, frame_rows=hw)
+        vt = self._buf(c, hw)
         if hw > self.attn_long_from:
             # Frames beyond what the register softmax holds (16,384 tokens): the same fp32-logit composition over blocks of R
             # query rows, so that the score scratch is [R][tokens] (at most attn_scratch_elems, whatever the frame) and the
@@ -299,8 +318,8 @@ class TemporalDecoderHIP(_VAEKernels):
     """``AutoencoderKLTemporalDecoder.decode`` on a HIP device.  ``state_dict``: the ``decoder.*`` entries of a diffusers
     vae checkpoint with the prefix stripped (or ``random_state_dict``)."""
 
-    def __init__(self, cfg: VAEDecoderConfig, state_dict: dict, device):
-        super().__init__(cfg, device)
+    def __init__(self, cfg: VAEDecoderConfig, state_dict: dict, device, attention=None):
+        super().__init__(cfg, device, attention)
         dev = self.device
         sd = state_dict
         ch = list(cfg.block_out_channels)
@@ -486,8 +505,8 @@ class ImageEncoderHIP(_VAEKernels):
     padded copies, no extra kernel variant.  ``quant_conv`` (1x1 on 8 channels) is composed into ``conv_out`` at load
     time (fp32, rounded once), keeping only the four mean channels that ``mode()`` returns."""
 
-    def __init__(self, cfg: VAEDecoderConfig, state_dict: dict, device):
-        super().__init__(cfg, device)
+    def __init__(self, cfg: VAEDecoderConfig, state_dict: dict, device, attention=None):
+        super().__init__(cfg, device, attention)
         dev = self.device
         sd = dict(state_dict)
         ch = list(cfg.block_out_channels)

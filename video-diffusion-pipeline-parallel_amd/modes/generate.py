@@ -110,6 +110,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--random-init", action="store_true")
     p.add_argument("--tiny", action="store_true", help="with --random-init: the narrow test configuration")
     p.add_argument("--decode-chunk-size", type=int, default=14)
+    p.add_argument("--vae-attention", type=str, default="composed", choices=["composed", "fused"],
+                   help="mid-block attention of the VAE encoder and decoder: contractions and a row softmax through a score "
+                        "matrix, or one fused kernel (no score matrix, any frame size that is a multiple of 64 px)")
     p.add_argument("--balanced", action="store_true")
     p.add_argument("--backend", type=str, default="auto", choices=["auto", "gloo", "nccl"])
     p.add_argument("--init-method", type=str, default=None)
@@ -213,15 +216,16 @@ def _build_engines(args, timesteps, device):
                                                  window_stride=args.window_stride, window_weights=args.window_weights,
                                                  eta=args.eta, s_noise=args.s_noise, **tile_arguments(args))
         clip = CLIPVisionHIP(spec, clip_random_state_dict(spec, seed=args.seed + 1, device=device), device)
-        enc = ImageEncoderHIP(vcfg, random_encoder_state_dict(vcfg, seed=args.seed + 2, device=device), device)
+        enc = ImageEncoderHIP(vcfg, random_encoder_state_dict(vcfg, seed=args.seed + 2, device=device), device,
+                              attention=args.vae_attention)
         return model, clip, enc, lambda: TemporalDecoderHIP(vcfg, random_state_dict(vcfg, seed=args.seed + 3, device=device),
-                                                            device)
+                                                            device, attention=args.vae_attention)
     from ..models.edge_stages import load_edge_engines
 
     model = StableVideoUNet.from_pretrained(args.model_id, timesteps=timesteps, device=device, sampler=args.sampler,
                                             window_stride=args.window_stride, window_weights=args.window_weights,
                                             eta=args.eta, s_noise=args.s_noise, **tile_arguments(args))
-    clip, enc, dec = load_edge_engines(args.model_id, device)
+    clip, enc, dec = load_edge_engines(args.model_id, device, vae_attention=args.vae_attention)
     return model, clip, enc, lambda: dec
 
 
