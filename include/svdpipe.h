@@ -179,6 +179,35 @@ const char *sp_gemm_last_kernel(void);
 int sp_conv_up2x_f16(const void *a, int64_t lda, int cin, int n_img, int hin, int win, const void *w, int n,
                      const float *bias, void *d, int64_t ldd, float *gn_part, const void *zero_page, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * fp8 feed-forward path (W8A8, OCP e4m3fn; csrc/gemm_f8.hip): the first projection of a GEGLU
+ * feed-forward with its LayerNorm, as an opt-in data type (BASELINE config 5; the reference has no fp8 path).  Activations
+ * carry one fp32 scale per ROW, weights one per OUTPUT CHANNEL; products are exact, sums fp32.
+ *
+ * sp_ln_quant_f8: per row, y = (x - mean) * rstd in fp32 (gamma and beta live in the weights and the bias, as with the
+ * folded LayerNorm of sp_gemm_desc.ln_stats), sa[row] = max|y| / 448, q[row][:] = e4m3(y / sa[row]) (round to nearest
+ * even, never the NaN code); a row whose y is all zero stores zeros and sa = 1.  The norm is applied BEFORE rounding: the
+ * fp16 fold rstd*(x.W' - mean*colsum) on quantised raw x would multiply the 3-bit-mantissa error by |mean|/std.
+ *   x: fp16 [rows][ldx], stats: fp32 [rows][2] (mean, rstd) as sp_ln_stats_f16 or sp_gemm_desc.ln_out leave them,
+ *   q: e4m3 bytes [rows][ldq], sa: fp32 [rows].  c: a multiple of 64 in 64 .. 1280; ldx >= c, a multiple of 8; ldq >= c, a
+ *   multiple of 16; x, q 16-byte aligned; 0 < rows < 2^31.
+ *
+ * sp_gemm_f8: D[m][:] = epilogue(sa[m] * sw[n] * sum_k A8[m][k] * W8[n][k]) on v_mfma_scale_f32_32x32x64_f8f6f4 with unit
+ * block scales.  a8: e4m3 bytes [m][lda], w8: e4m3 bytes [n][k], sa: fp32 [m], sw: fp32 [n], bias: fp32 [n].
+ *   geglu == 0: v = sa*sw*acc + bias (+ r1scale*res1, res1 fp16 [m][ldr1] or NULL), rounded to fp16 once, d fp16 [m][ldd]
+ *   geglu != 0: weight rows interleaved in blocks of 16 as for sp_gemm_desc.geglu; out[m][j] = h*gelu(gate), each after its
+ *               own scale and bias, the erf form and rounding order of sp_gemm_f16's GEGLU epilogue; n/2 stored columns;
+ *               res1 must be NULL.
+ * k: a multiple of 64 in 64 .. 1280; n: a multiple of 128; 0 < m < 2^31 (rows at or beyond m are read from row m - 1 and
+ * not stored); lda >= k, a multiple of 16; ldd, ldr1 >= the stored columns, multiples of 8; a8, w8, sw, bias, d, res1
+ * 16-byte aligned.  Everything is checked before anything is launched (SP_EINVAL, sp_last_error names the argument).
+ * Runs as "gemm_f8_kernel<256, 256, 0 | 1>" (the name sp_gemm_last_kernel reports afterwards). */
+int sp_ln_quant_f8(const void *x, int64_t ldx, const float *stats, void *q, int64_t ldq, float *sa, int64_t rows, int c,
+                   void *stream);
+int sp_gemm_f8(const void *a8, int64_t lda, const float *sa, const void *w8, const float *sw, const float *bias,
+               const void *res1, int64_t ldr1, float r1scale, void *d, int64_t ldd, int m, int n, int k, int geglu,
+               void *stream);
+
 /* Test / micro-benchmark hook (no counterpart in the reference): pins the kernel family sp_gemm_f16 picks for the
  * shapes that family supports; everything else keeps the automatic choice.  Process-wide, not thread-safe: set it
  * before the calls it should affect.  route 0 = automatic (default), 1 = small tiles only, 2 = ping-pong large tiles

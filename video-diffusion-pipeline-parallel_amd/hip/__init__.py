@@ -67,6 +67,8 @@ SIGNATURES = {
     "sp_gemm_set_route": (_I, [_I, _I, _I]),
     "sp_gemm_last_kernel": (ctypes.c_char_p, []),
     "sp_conv_up2x_f16": (_I, [_P, _L, _I, _I, _I, _I, _P, _I, _P, _P, _L, _P, _P, _P]),
+    "sp_ln_quant_f8": (_I, [_P, _L, _P, _P, _L, _P, _L, _I, _P]),
+    "sp_gemm_f8": (_I, [_P, _L, _P, _P, _P, _P, _P, _L, _F, _P, _L, _I, _I, _I, _I, _P]),
     "sp_gemv_f16": (_I, [_P, _L, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P]),
     "sp_gemv_batched_f16": (_I, [_P, _L, _L, _P, _L, _P, _L, _P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _P]),
     "sp_sinusoid_f16": (_I, [_P, _P, _I, _I, _P]),

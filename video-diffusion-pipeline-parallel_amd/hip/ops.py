@@ -293,6 +293,40 @@ def ln_stats(x, stats, *, rows, c, eps=1e-5, addvec=None, addvec_rows=0, sum_out
     return stats
 
 
+def _u8(t: torch.Tensor, name: str) -> torch.Tensor:
+    if t.dtype != torch.uint8 or not t.is_cuda or (t.dim() >= 1 and t.stride(-1) != 1 and t.shape[-1] != 1):
+        raise TypeError(f"{name} must be a row-major uint8 (e4m3 bytes) tensor on a HIP device")
+    return t
+
+
+def ln_quant_f8(x, stats, q, sa, *, rows, c, ldx=None, ldq=None):
+    """LayerNorm (no affine) of the fp16 rows ``x`` from their ``stats`` -> e4m3 bytes ``q`` and one fp32 scale per row
+    ``sa`` (``sp_ln_quant_f8``): the A operand of :func:`gemm_f8`."""
+    ldx = int(ldx if ldx is not None else x.stride(0))
+    ldq = int(ldq if ldq is not None else q.stride(0))
+    with _Timed("ln_quant_f8", 0.0, 3.0 * rows * c + 12.0 * rows):
+        _check(load().sp_ln_quant_f8(_rows(x, "x", ldx).data_ptr(), ldx, stats.data_ptr(), _u8(q, "q").data_ptr(), ldq,
+                                     sa.data_ptr(), rows, c, _stream()), "sp_ln_quant_f8")
+    return q, sa
+
+
+def gemm_f8(a8, sa, w8, sw, bias, out, *, m, n, k, geglu=False, res1=None, r1scale=1.0, lda=None, ldd=None, ldr1=None):
+    """``out[m][:] = epilogue(sa[m] * sw[n] * A8 @ W8^T + bias)`` on the 2x-rate fp8 MFMA (``sp_gemm_f8`` in
+    include/svdpipe.h): e4m3 bytes ``a8`` [m][lda] and ``w8`` [n][k], fp32 scales per row / per output channel."""
+    nout = n // 2 if geglu else n
+    lda = int(lda if lda is not None else a8.stride(0))
+    ldd = int(ldd if ldd is not None else out.stride(0))
+    ldr1 = int(ldr1 if ldr1 is not None else (res1.stride(0) if res1 is not None else nout))
+    nbytes = 1.0 * (m * k + n * k) + 2.0 * m * nout * (1 + (res1 is not None)) + 4.0 * (m + 2 * n)
+    with _Timed("gemm", 2.0 * m * n * k, nbytes, (m, n, k, A_LINEAR, bool(geglu))) as tm:
+        _check(load().sp_gemm_f8(_u8(a8, "a8").data_ptr(), lda, sa.data_ptr(), _u8(w8, "w8").data_ptr(), sw.data_ptr(),
+                                 _ptr(bias), _ptr(res1), ldr1, float(r1scale), _rows(out, "out", ldd).data_ptr(), ldd,
+                                 m, n, k, int(geglu), _stream()), "sp_gemm_f8")
+        if PROFILE is not None:
+            tm.tag = tm.tag + (load().sp_gemm_last_kernel().decode(),)
+    return out
+
+
 def attn_spatial(q, k, v, o, *, ldq, ldk, ldv, ldo, batch, seq, heads, scale=0.125):
     with _Timed("attn_spatial", 4.0 * batch * heads * seq * seq * 64):
         _check(load().sp_attn_spatial_f16(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), ldq, ldk, ldv, ldo,

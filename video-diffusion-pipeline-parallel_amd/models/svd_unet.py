@@ -265,6 +265,7 @@ class StableVideoUNet(nn.Module):
         enable_sliced_attention: bool = False,
         attention_slice_size: int | str = "auto",
         device="cuda",
+        fp8_ff: bool | None = None,
         **kwargs,
     ) -> "StableVideoUNet":
         """Load ``<model_id>/unet/diffusion_pytorch_model*.safetensors`` from a LOCAL directory.
@@ -272,7 +273,8 @@ class StableVideoUNet(nn.Module):
         The attention toggles of the reference signature are accepted and ignored: the fused HIP
         attention kernels are always on.  A hub name cannot be fetched (no network): ValueError.
         Of ``kwargs`` the step options (``STEP_OPTIONS``: ``sampler``, ``window_stride``, ``tile_size``, ...) go to
-        ``__init__``, which validates them; the reference's other keywords are accepted and ignored.
+        ``__init__``, which validates them; the reference's other keywords are accepted and ignored.  ``fp8_ff`` goes to
+        the engine (``SVDUNetHIP(fp8_ff=)``: the GEGLU first projections on fp8 MFMA; default off).
         """
         unet_dir = os.path.join(model_id, "unet")
         if not os.path.isdir(unet_dir):
@@ -315,13 +317,14 @@ class StableVideoUNet(nn.Module):
             )
         if timesteps is None:
             timesteps = cls._default_timestep_schedule(num_steps=25)
-        return cls(unet=SVDUNetHIP(cfg, sd, device), timesteps=timesteps, dtype=torch_dtype,
+        return cls(unet=SVDUNetHIP(cfg, sd, device, fp8_ff=fp8_ff), timesteps=timesteps, dtype=torch_dtype,
                    **{k: v for k, v in kwargs.items() if k in STEP_OPTIONS})
 
     @classmethod
     def from_random_init(cls, timesteps: Sequence[int], *, config: UNetConfig | None = None, seed: int = 0,
                          device="cuda", fp8_attention: bool | None = None,
-                         long_attention: bool | None = None, **step_options) -> "StableVideoUNet":
+                         long_attention: bool | None = None, fp8_ff: bool | None = None,
+                         **step_options) -> "StableVideoUNet":
         """Random weights of the exact SVD architecture (benchmarks / tests; no checkpoint needed); ``step_options``
         (``STEP_OPTIONS``) as for ``__init__``."""
         unknown = sorted(set(step_options) - set(STEP_OPTIONS))
@@ -329,7 +332,7 @@ class StableVideoUNet(nn.Module):
             raise TypeError(f"from_random_init() got an unexpected keyword argument {unknown[0]!r}")
         cfg = config or UNetConfig.svd()
         sd = random_state_dict(cfg, seed=seed, device=device, dtype=torch.float16)
-        unet = SVDUNetHIP(cfg, sd, device, fp8_attention=fp8_attention, long_attention=long_attention)
+        unet = SVDUNetHIP(cfg, sd, device, fp8_attention=fp8_attention, long_attention=long_attention, fp8_ff=fp8_ff)
         del sd
         return cls(unet=unet, timesteps=timesteps, **step_options)
 

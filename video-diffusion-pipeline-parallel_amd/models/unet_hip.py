@@ -111,8 +111,12 @@ class SVDUNetHIP(common._Engine):
     LONG_ATTENTION_MIN_SEQ = 8192
 
     def __init__(self, cfg: UNetConfig, state_dict: dict, device, *, fp8_attention: bool | None = None,
-                 long_attention: bool | None = None):
-        """``fp8_attention``: run the spatial self-attention on fp8-e4m3 MFMA (BASELINE config 5: "SVD-XT ... with
+                 long_attention: bool | None = None, fp8_ff: bool | None = None):
+        """``fp8_ff``: the first projection of every GEGLU feed-forward (spatial, temporal and ``ff_in``) as a W8A8
+        contraction on the 2x-rate fp8 MFMA -- LayerNorm + per-row e4m3 quantisation (``sp_ln_quant_f8``), then ``sp_gemm_f8``
+        with per-output-channel weight scales; the second projection stays fp16.  Default off, or ``VDPP_FP8_FF=1``; off,
+        nothing is packed and every path launches what it launched without the option.
+        ``fp8_attention``: run the spatial self-attention on fp8-e4m3 MFMA (BASELINE config 5: "SVD-XT ... with
         fp8 MFMA attention path"); default off, or ``VDPP_FP8_ATTN=1``.  Everything else stays fp16.
         ``long_attention``: level-0 rows (>= 8,192 tokens) through the frozen-reference kernel; default ON since round 4
         (``False`` or ``VDPP_LONG_ATTN=0`` selects the ordinary kernel for every row).  Same results; it is 5-9 % faster
@@ -124,6 +128,7 @@ class SVDUNetHIP(common._Engine):
         self.cfg, dev = cfg, self.device
         self.fp8_attention = (os.environ.get("VDPP_FP8_ATTN") == "1") if fp8_attention is None else bool(fp8_attention)
         self.long_attention = (os.environ.get("VDPP_LONG_ATTN", "1") != "0") if long_attention is None else bool(long_attention)
+        self.fp8_ff = (os.environ.get("VDPP_FP8_FF") == "1") if fp8_ff is None else bool(fp8_ff)
         # the 16 transformer-entry GroupNorms folded into proj_in where a frame is whole tiles (VDPP_FOLD_GN=0: never)
         self.fold_groupnorm = os.environ.get("VDPP_FOLD_GN", "1") != "0"
         # a resnet's 1x1 shortcut convolution as an extra linear tap of its second 3x3 convolution (levels with more rows
@@ -244,8 +249,22 @@ class SVDUNetHIP(common._Engine):
                     out=_Dense.linear(sd, p + ".to_out.0", dev))
 
     def _geglu_ln(self, sd, p, dev, norm):
-        return _Dense.fold_layernorm(sd[p + ".weight"], sd[p + ".bias"], sd[norm + ".weight"], sd[norm + ".bias"], dev,
-                                     eps=1e-5, geglu=True)
+        layer = _Dense.fold_layernorm(sd[p + ".weight"], sd[p + ".bias"], sd[norm + ".weight"], sd[norm + ".bias"], dev,
+                                      eps=1e-5, geglu=True)
+        return self._f8_pack(layer) if self.fp8_ff else layer
+
+    @staticmethod
+    def _f8_pack(layer: _Dense) -> _Dense:
+        """The e4m3 pack of a GEGLU projection beside its fp16 one (a quarter of its bytes more), made once: from the
+        gamma-folded, interleaved fp16 weights the fp16 route multiplies with, one scale per output channel; the folded bias
+        is shared.  At construction with ``fp8_ff``, or at the first forward after the attribute was switched on."""
+        if getattr(layer, "w8", None) is None:
+            n, k = layer.w.shape
+            if k % 64 or k > 1280 or n % 128:
+                raise ValueError(f"fp8_ff: a {n} x {k} projection; sp_gemm_f8 takes K a multiple of 64 up to 1280 and N a "
+                                 "multiple of 128")
+            layer.w8, layer.sw8 = W.pack_linear_f8(layer.w.float(), geglu=False)       # (the rows are interleaved already)
+        return layer
 
     def _xattn(self, sd, p, dev):
         return dict(v=W.pack_linear(sd[p + ".to_v.weight"]).to(dev), o=W.pack_linear(sd[p + ".to_out.0.weight"]).to(dev),
@@ -469,13 +488,27 @@ class SVDUNetHIP(common._Engine):
     FF_CHUNK_BYTES = int(os.environ.get("VDPP_FF_CHUNK_MB", "0")) << 20
     FF_CHUNK_ROUND = None            # tests: rows a chunk is rounded to (default: one full round of FF2 workgroups)
 
+    def _ff1(self, r: _Run, ff1: _Dense, x, st):
+        """``geglu(ff1(LN(x)))`` of the rows ``x`` with statistics ``st`` -> the fp16 hidden tensor.  fp16 route: the
+        LayerNorm folded into the contraction.  ``fp8_ff``: the normalised rows as e4m3 bytes with one scale per row (in the
+        stream's scratch pool: they live from one launch to the next), then the W8A8 contraction."""
+        m, c = x.shape
+        if not self.fp8_ff:
+            return self._gemm(r, ff1, x, m=m, ln_stats=st).t
+        self._f8_pack(ff1)
+        ws = self._scratch.get("ff8", m * c + 4 * m)
+        q, sa = ws[:m * c].view(m, c), ws[m * c:m * c + 4 * m].view(torch.float32)
+        ops.ln_quant_f8(x, st, q, sa, rows=m, c=c)
+        g = self._buf(m, ff1.n_true)
+        return ops.gemm_f8(q, sa, ff1.w8, ff1.sw8, ff1.bias, g, m=m, n=ff1.n, k=c, geglu=True)
+
     def _ff_pair(self, r: _Run, ff1: _Dense, ff2: _Dense, x, st, *, ln_next=None, **epi) -> _Act:
         """``ff2(geglu(ff1(LN(x))))`` on the plain tensor ``x`` with row statistics ``st``; ``epi``: ff2's epilogue
         arguments (residuals are row-sliced along), ``ln_next`` as in _gemm."""
         m, hid = x.shape[0], ff1.n_true
         budget = self.FF_CHUNK_BYTES
         if not budget or m * hid * 2 <= budget:
-            g = self._gemm(r, ff1, x, ln_stats=st).t
+            g = self._ff1(r, ff1, x, st)
             return self._gemm(r, ff2, g, ln_next=ln_next, **epi)
         tiles_n = max(1, ff2.n // 320 if ff2.n % 320 == 0 else ff2.n // 256)
         rows_round = self.FF_CHUNK_ROUND or 256 * max(1, 256 // tiles_n)   # rows of one full round of FF2 workgroups
@@ -493,7 +526,7 @@ class SVDUNetHIP(common._Engine):
             kw = {k: (v[r0:r1] if k in ("res1", "res2") and v is not None else v) for k, v in epi.items()}
             if st_next is not None:
                 kw.update(ln_next=ln_next, ln_out=st_next[r0:r1])
-            g = self._gemm(r, ff1, x[r0:r1], m=r1 - r0, ln_stats=st[r0:r1]).t
+            g = self._ff1(r, ff1, x[r0:r1], st[r0:r1])
             self._gemm(r, ff2, g, m=r1 - r0, out=out[r0:r1], **kw)
             del g
         return _Act(out, ln_stats=st_next, ln_eps=ln_next.ln_eps if st_next is not None else None)

@@ -78,3 +78,19 @@ def interleave_geglu(w: torch.Tensor, b: torch.Tensor | None):
     wi = w[order].to(torch.float16).contiguous()
     bi = None if b is None else b[order].float().contiguous()
     return wi, bi
+
+
+def pack_linear_f8(w_folded: torch.Tensor, geglu: bool = False):
+    """(N, K) weights in fp32 (a folded LayerNorm's gamma already multiplied in) -> (e4m3 bytes uint8 ``[N][K]``, fp32 scale
+    ``[N]``) for ``sp_gemm_f8``: one scale per output channel, ``amax/448`` of its row (1 for an all-zero row), the row
+    divided by it and rounded to OCP e4m3fn once.  ``geglu``: rows reordered as :func:`interleave_geglu` does."""
+    w = w_folded.reshape(w_folded.shape[0], -1).float()
+    if geglu:
+        inner = w.shape[0] // 2
+        assert inner % 16 == 0
+        idx = torch.arange(inner, device=w.device).reshape(-1, 16)
+        w = w[torch.cat([idx, idx + inner], dim=1).reshape(-1)]
+    amax = w.abs().amax(dim=1)
+    sw = torch.where(amax > 0, amax / 448.0, torch.ones_like(amax))
+    w8 = (w / sw[:, None]).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).view(torch.uint8)
+    return w8.contiguous(), sw.contiguous()

@@ -109,6 +109,8 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--model-id", type=str, default=None, help="LOCAL checkpoint directory in the hub layout")
     p.add_argument("--random-init", action="store_true")
     p.add_argument("--tiny", action="store_true", help="with --random-init: the narrow test configuration")
+    p.add_argument("--fp8-ff", action="store_true",
+                   help="first projection of every GEGLU feed-forward as a W8A8 (e4m3) contraction; default fp16")
     p.add_argument("--decode-chunk-size", type=int, default=14)
     p.add_argument("--vae-attention", type=str, default="composed", choices=["composed", "fused"],
                    help="mid-block attention of the VAE encoder and decoder: contractions and a row softmax through a score "
@@ -214,7 +216,8 @@ def _build_engines(args, timesteps, device):
         vcfg = VAEDecoderConfig.tiny(64) if args.tiny else VAEDecoderConfig.svd()
         model = StableVideoUNet.from_random_init(timesteps, config=ucfg, seed=args.seed, device=device, sampler=args.sampler,
                                                  window_stride=args.window_stride, window_weights=args.window_weights,
-                                                 eta=args.eta, s_noise=args.s_noise, **tile_arguments(args))
+                                                 eta=args.eta, s_noise=args.s_noise, fp8_ff=args.fp8_ff or None,
+                                                 **tile_arguments(args))
         clip = CLIPVisionHIP(spec, clip_random_state_dict(spec, seed=args.seed + 1, device=device), device)
         enc = ImageEncoderHIP(vcfg, random_encoder_state_dict(vcfg, seed=args.seed + 2, device=device), device,
                               attention=args.vae_attention)
@@ -224,7 +227,8 @@ def _build_engines(args, timesteps, device):
 
     model = StableVideoUNet.from_pretrained(args.model_id, timesteps=timesteps, device=device, sampler=args.sampler,
                                             window_stride=args.window_stride, window_weights=args.window_weights,
-                                            eta=args.eta, s_noise=args.s_noise, **tile_arguments(args))
+                                            eta=args.eta, s_noise=args.s_noise, fp8_ff=args.fp8_ff or None,
+                                            **tile_arguments(args))
     clip, enc, dec = load_edge_engines(args.model_id, device, vae_attention=args.vae_attention)
     return model, clip, enc, lambda: dec
 

@@ -44,6 +44,8 @@ def parse_args(argv=None) -> argparse.Namespace:
                         "with motion bucket B[i %% len(B)]")
     p.add_argument("--model-id", type=str, default="stabilityai/stable-video-diffusion-img2vid-xt")
     p.add_argument("--random-init", action="store_true")
+    p.add_argument("--fp8-ff", action="store_true",
+                   help="first projection of every GEGLU feed-forward as a W8A8 (e4m3) contraction; default fp16")
     p.add_argument("--balanced", action="store_true")
     p.add_argument("--backend", type=str, default="auto", choices=["auto", "gloo", "nccl"])
     p.add_argument("--init-method", type=str, default=None)
@@ -66,10 +68,10 @@ def main(argv=None) -> None:
     init_distributed(backend=backend, rank=rank, world_size=world, init_method=args.init_method)
 
     timesteps = StableVideoUNet._default_timestep_schedule(args.total_steps)
-    noise = dict(eta=args.eta, s_noise=args.s_noise)
-    model = (StableVideoUNet.from_random_init(timesteps, device=device, sampler=args.sampler, **noise) if args.random_init
+    options = dict(eta=args.eta, s_noise=args.s_noise, fp8_ff=args.fp8_ff or None)
+    model = (StableVideoUNet.from_random_init(timesteps, device=device, sampler=args.sampler, **options) if args.random_init
              else StableVideoUNet.from_pretrained(args.model_id, timesteps=timesteps, device=device, sampler=args.sampler,
-                                                  **noise))
+                                                  **options))
     torch.manual_seed(args.seed)
     model.set_dummy_conditioning(1, args.latent_frames, args.latent_height, args.latent_width, device,
                                  fps=args.fps, motion_bucket_id=args.motion_bucket_id,
