@@ -367,6 +367,33 @@ int sp_attn_spatial_fp8(const void *q, const void *k, const void *v, void *o, in
 int sp_attn_wide_f16(const void *q, const void *k, const void *v, void *o, int64_t ldq, int64_t ldk, int64_t ldv,
                      int64_t ldo, const float *bias, int batch, int seq, int head_dim, float scale, void *stream);
 
+/* Spatial self-attention over POOLED keys and values (csrc/attention_kv.hip; no counterpart in the reference: token
+ * downsampling of K/V, an approximation, opt-in).  Every query token of a frame is kept; K and V are averaged over
+ * factor x factor cells of the frame's h x w token grid and the attention runs seq_q queries against seq_kv keys.
+ *
+ * sp_kv_pool_f16: k, v fp16 rows [n_img*h*w][c] with row pitches ldk, ldv (in the engine: columns of the fused QKV
+ * buffer); kp, vp fp16 rows [n_img*(h/factor)*(w/factor)][c] with pitches ldkp, ldvp; cell (y, x) of an image goes to
+ * its row y*(w/factor) + x.  fp32 sum, times 1/factor^2, one rounding to fp16 (to nearest even).  Columns at or beyond
+ * c of the outputs are not written.  No allocation, no synchronisation.
+ * Refused without a launch: null pointers, factor other than 2 or 4, counts that are not positive, c no multiple of 8,
+ * h or w that does not divide by factor, a pitch below c or no multiple of 8, pointers not 16-byte aligned.
+ *
+ * sp_attn_spatial_kv_f16: O[b] = softmax(scale * Q[b].K[b]^T).V[b] per image b and head, head_dim 64.  q, o: fp16 rows
+ * [batch*seq_q][heads*64]; k, v: [batch*seq_kv][heads*64]; pitches ldq, ldk, ldv, ldo in elements (>= heads*64,
+ * multiples of 8), 16-byte aligned.  seq_q and seq_kv: any positive counts, independent of each other.
+ * Numerical contract (that of sp_attn_wide_f16): logits are fp32 MFMA sums, never rounded to fp16 or clamped; running
+ * maximum and sum per row are fp32, exp2 with scale*log2(e) folded in; probabilities are rounded to fp16 only as the
+ * operand of P.V; outputs accumulate in fp32 and are divided by the row sum once.  Finite inputs give finite outputs.
+ * Tails: a key row at or beyond seq_kv is read from row seq_kv-1 of its image and contributes exactly 0; a query row at
+ * or beyond seq_q is not stored.  No read or write touches a row outside its image or a column outside [0, heads*64).
+ * Refused without a launch: null pointers, counts that are not positive, a pitch below heads*64, no multiple of 8 or
+ * (ldk, ldv) of 2^24 or more, misaligned pointers, a scale that is not positive and finite. */
+int sp_kv_pool_f16(const void *k, const void *v, int64_t ldk, int64_t ldv, void *kp, void *vp, int64_t ldkp,
+                   int64_t ldvp, int n_img, int h, int w, int c, int factor, void *stream);
+int sp_attn_spatial_kv_f16(const void *q, const void *k, const void *v, void *o, int64_t ldq, int64_t ldk,
+                           int64_t ldv, int64_t ldo, int batch, int seq_q, int seq_kv, int heads, float scale,
+                           void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Layout / elementwise glue around the UNet (svd_unet.py:382-439).
  * ------------------------------------------------------------------------------------------- */

@@ -344,6 +344,25 @@ def attn_wide(q, k, v, o, *, ldq, ldk, ldv, ldo, batch, seq, head_dim, scale, bi
     return o
 
 
+def kv_pool(k, v, kp, vp, *, ldk, ldv, ldkp, ldvp, n_img, h, w, c, factor):
+    """K and V rows [n_img*h*w][c] averaged over ``factor x factor`` cells of the h x w token grid into ``kp``, ``vp``
+    [n_img*(h/factor)*(w/factor)][c] (csrc/attention_kv.hip): fp32 sum, one rounding."""
+    rows = n_img * h * w
+    with _Timed("kv_pool", 0.0, 4.0 * rows * c * (1.0 + 1.0 / (factor * factor))):
+        _check(load().sp_kv_pool_f16(k.data_ptr(), v.data_ptr(), ldk, ldv, kp.data_ptr(), vp.data_ptr(), ldkp, ldvp,
+                                     n_img, h, w, c, factor, _stream()), "sp_kv_pool_f16")
+    return kp, vp
+
+
+def attn_spatial_kv(q, k, v, o, *, ldq, ldk, ldv, ldo, batch, seq_q, seq_kv, heads, scale=0.125):
+    """Rectangular spatial attention, ``seq_q`` queries against ``seq_kv`` (pooled) keys per image and head
+    (csrc/attention_kv.hip): the numerical contract of ``attn_wide`` at head_dim 64."""
+    with _Timed("attn_spatial_kv", 4.0 * batch * heads * seq_q * seq_kv * 64):
+        _check(load().sp_attn_spatial_kv_f16(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), ldq, ldk, ldv, ldo,
+                                             batch, seq_q, seq_kv, heads, scale, _stream()), "sp_attn_spatial_kv_f16")
+    return o
+
+
 def attn_long_ws_bytes(batch, seq, heads) -> int:
     return int(load().sp_attn_long_ws_bytes(batch, seq, heads))
 

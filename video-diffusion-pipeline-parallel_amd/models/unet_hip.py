@@ -111,8 +111,14 @@ class SVDUNetHIP(common._Engine):
     LONG_ATTENTION_MIN_SEQ = 8192
 
     def __init__(self, cfg: UNetConfig, state_dict: dict, device, *, fp8_attention: bool | None = None,
-                 long_attention: bool | None = None, fp8_ff: bool | None = None):
-        """``fp8_ff``: the first projection of every GEGLU feed-forward (spatial, temporal and ``ff_in``) as a W8A8
+                 long_attention: bool | None = None, fp8_ff: bool | None = None, kv_downsample: int | None = None,
+                 kv_downsample_min_tokens: int = 4096):
+        """``kv_downsample``: 2 or 4 runs the SPATIAL self-attention of every level with at least
+        ``kv_downsample_min_tokens`` tokens per frame (and a token grid that divides) over keys and values averaged over
+        2 x 2 / 4 x 4 cells of the grid: every query is kept, a quarter / a sixteenth of the keys (``sp_kv_pool_f16``, then
+        ``sp_attn_spatial_kv_f16``; there it takes precedence over the fp8 and long routes).  An approximation; default 1 =
+        off, or ``VDPP_KV_DOWNSAMPLE``; off, every path launches what it launched without the option.
+        ``fp8_ff``: the first projection of every GEGLU feed-forward (spatial, temporal and ``ff_in``) as a W8A8
         contraction on the 2x-rate fp8 MFMA -- LayerNorm + per-row e4m3 quantisation (``sp_ln_quant_f8``), then ``sp_gemm_f8``
         with per-output-channel weight scales; the second projection stays fp16.  Default off, or ``VDPP_FP8_FF=1``; off,
         nothing is packed and every path launches what it launched without the option.
@@ -129,6 +135,10 @@ class SVDUNetHIP(common._Engine):
         self.fp8_attention = (os.environ.get("VDPP_FP8_ATTN") == "1") if fp8_attention is None else bool(fp8_attention)
         self.long_attention = (os.environ.get("VDPP_LONG_ATTN", "1") != "0") if long_attention is None else bool(long_attention)
         self.fp8_ff = (os.environ.get("VDPP_FP8_FF") == "1") if fp8_ff is None else bool(fp8_ff)
+        self.kv_downsample = int(os.environ.get("VDPP_KV_DOWNSAMPLE", "1")) if kv_downsample is None else kv_downsample
+        if self.kv_downsample not in (1, 2, 4) or isinstance(self.kv_downsample, bool):
+            raise ValueError(f"kv_downsample: {self.kv_downsample!r} (1 = off, 2 or 4)")
+        self.kv_downsample_min_tokens = int(kv_downsample_min_tokens)
         # the 16 transformer-entry GroupNorms folded into proj_in where a frame is whole tiles (VDPP_FOLD_GN=0: never)
         self.fold_groupnorm = os.environ.get("VDPP_FOLD_GN", "1") != "0"
         # a resnet's 1x1 shortcut convolution as an extra linear tap of its second 3x3 convolution (levels with more rows
@@ -430,6 +440,11 @@ class SVDUNetHIP(common._Engine):
         c, g = x["grp"]
         return r.cross[c][g]
 
+    def _kv_pooled(self, r: _Run) -> bool:
+        """Does this level's spatial self-attention run over pooled keys and values (``kv_downsample``)?"""
+        f = self.kv_downsample
+        return f > 1 and r.hw >= self.kv_downsample_min_tokens and r.h % f == 0 and r.w % f == 0
+
     def _self_attn(self, r: _Run, att, xvec, resid: _Act, *, temporal: bool, **epi) -> _Act:
         """LayerNorm (folded into the fused Q/K/V projection) -> self-attention -> output projection + residual."""
         c = att["out"].n
@@ -440,6 +455,14 @@ class SVDUNetHIP(common._Engine):
         if temporal:
             ops.attn_temporal(q, k, v, o, ldq=3 * c, ldk=3 * c, ldv=3 * c, ldo=c, batch=r.b, frames=r.f, hw=r.hw,
                               heads=heads)
+        elif self._kv_pooled(r):
+            f, inst = self.kv_downsample, r.b * r.f
+            rows_kv = inst * (r.hw // (f * f))
+            pooled = self._scratch.get("kvpool", 4 * rows_kv * c)[:4 * rows_kv * c].view(torch.float16)
+            kp, vp = pooled[:rows_kv * c].view(rows_kv, c), pooled[rows_kv * c:2 * rows_kv * c].view(rows_kv, c)
+            ops.kv_pool(k, v, kp, vp, ldk=3 * c, ldv=3 * c, ldkp=c, ldvp=c, n_img=inst, h=r.h, w=r.w, c=c, factor=f)
+            ops.attn_spatial_kv(q, kp, vp, o, ldq=3 * c, ldk=c, ldv=c, ldo=c, batch=inst, seq_q=r.hw, seq_kv=r.hw // (f * f),
+                                heads=heads)
         elif self.fp8_attention and r.hw >= self.FP8_MIN_SEQ:
             ws = self._scratch.get("fp8", ops.attn_fp8_ws_bytes(r.b * r.f, r.hw, heads))
             ops.attn_spatial_fp8(q, k, v, o, ws, ldq=3 * c, ldk=3 * c, ldv=3 * c, ldo=c, batch=r.b * r.f, seq=r.hw,

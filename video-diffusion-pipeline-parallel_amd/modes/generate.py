@@ -111,6 +111,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--tiny", action="store_true", help="with --random-init: the narrow test configuration")
     p.add_argument("--fp8-ff", action="store_true",
                    help="first projection of every GEGLU feed-forward as a W8A8 (e4m3) contraction; default fp16")
+    p.add_argument("--kv-downsample", type=int, default=None, choices=[1, 2, 4],
+                   help="spatial self-attention over keys and values pooled over 2x2 / 4x4 token cells (levels of at least "
+                        "4,096 tokens per frame); an approximation, default 1 = off")
     p.add_argument("--decode-chunk-size", type=int, default=14)
     p.add_argument("--vae-attention", type=str, default="composed", choices=["composed", "fused"],
                    help="mid-block attention of the VAE encoder and decoder: contractions and a row softmax through a score "
@@ -217,6 +220,7 @@ def _build_engines(args, timesteps, device):
         model = StableVideoUNet.from_random_init(timesteps, config=ucfg, seed=args.seed, device=device, sampler=args.sampler,
                                                  window_stride=args.window_stride, window_weights=args.window_weights,
                                                  eta=args.eta, s_noise=args.s_noise, fp8_ff=args.fp8_ff or None,
+                                                 kv_downsample=args.kv_downsample,
                                                  **tile_arguments(args))
         clip = CLIPVisionHIP(spec, clip_random_state_dict(spec, seed=args.seed + 1, device=device), device)
         enc = ImageEncoderHIP(vcfg, random_encoder_state_dict(vcfg, seed=args.seed + 2, device=device), device,
@@ -228,6 +232,7 @@ def _build_engines(args, timesteps, device):
     model = StableVideoUNet.from_pretrained(args.model_id, timesteps=timesteps, device=device, sampler=args.sampler,
                                             window_stride=args.window_stride, window_weights=args.window_weights,
                                             eta=args.eta, s_noise=args.s_noise, fp8_ff=args.fp8_ff or None,
+                                            kv_downsample=args.kv_downsample,
                                             **tile_arguments(args))
     clip, enc, dec = load_edge_engines(args.model_id, device, vae_attention=args.vae_attention)
     return model, clip, enc, lambda: dec

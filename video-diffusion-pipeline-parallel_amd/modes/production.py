@@ -46,6 +46,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--random-init", action="store_true")
     p.add_argument("--fp8-ff", action="store_true",
                    help="first projection of every GEGLU feed-forward as a W8A8 (e4m3) contraction; default fp16")
+    p.add_argument("--kv-downsample", type=int, default=None, choices=[1, 2, 4],
+                   help="spatial self-attention over keys and values pooled over 2x2 / 4x4 token cells (levels of at least "
+                        "4,096 tokens per frame); an approximation, default 1 = off")
     p.add_argument("--balanced", action="store_true")
     p.add_argument("--backend", type=str, default="auto", choices=["auto", "gloo", "nccl"])
     p.add_argument("--init-method", type=str, default=None)
@@ -68,7 +71,7 @@ def main(argv=None) -> None:
     init_distributed(backend=backend, rank=rank, world_size=world, init_method=args.init_method)
 
     timesteps = StableVideoUNet._default_timestep_schedule(args.total_steps)
-    options = dict(eta=args.eta, s_noise=args.s_noise, fp8_ff=args.fp8_ff or None)
+    options = dict(eta=args.eta, s_noise=args.s_noise, fp8_ff=args.fp8_ff or None, kv_downsample=args.kv_downsample)
     model = (StableVideoUNet.from_random_init(timesteps, device=device, sampler=args.sampler, **options) if args.random_init
              else StableVideoUNet.from_pretrained(args.model_id, timesteps=timesteps, device=device, sampler=args.sampler,
                                                   **options))
