@@ -17,7 +17,9 @@ softmax of csrc/attention.hip rescales what it summed before the selected key ar
 tile without a selected key are of order 64 x 7), and ``attn_small_kernel`` (csrc/clip.hip) keeps P in fp32 throughout.  So G
 is chosen for GAP = 160: 2^-160 is below fp32's smallest subnormal, and a product of order 2^-160 x 2^15 added to a sum
 >= 1 leaves it as it was.  ``check_selection`` asserts the gap from the scores as the kernel forms them (for the spatial
-kernels from the fp16-rounded, pre-scaled query, csrc/attention.hip:73).
+kernels from the fp16-rounded, pre-scaled query, csrc/attention.hip:73; kind "unscaled" for csrc/attention_kv.hip and
+csrc/attention_wide.hip, which form fp32 logits from the unscaled fp16 operands and scale them in front of the exponential:
+p = exp2(s c - m c)).  ``make_rect`` builds the patterns for seq_q queries against seq_kv keys; ``make`` is its square case.
 
 Criterion (``violations``): x = S / count in fp64.
 * where x is representable in fp16 the output equals it bit for bit (every one-hot row; uniform and strided rows with a
@@ -73,28 +75,38 @@ def power_of_two_at_least(x):
     return 2.0 ** math.ceil(math.log2(x))
 
 
-def make(pattern, n, hd, scale, *, stride=None, pi=None, seed=0):
-    """(q [n][hd], k [n][hd], sel [n queries][n keys] bool) for one sequence of n tokens; the same q and k serve every
-    batch item and head (V differs).  G is a power of two, so q is exact in fp16."""
+def make_rect(pattern, nq, nkv, hd, scale, *, stride=None, pi=None, seed=0):
+    """(q [nq][hd], k [nkv][hd], sel [nq queries][nkv keys] bool) for nq queries against nkv keys; the same q and k serve
+    every batch item and head (V differs).  G is a power of two, so q is exact in fp16.
+    * ``onehot``: query i selects key pi(i) mod nkv, pi the first nq entries of a seeded permutation of max(nq, nkv)
+      indices, and query 0 the last key.
+    * ``strided``: query i selects the keys j = i (mod s), s = min(stride, nkv), so that every query has a key."""
     if pattern == "uniform":
         g = torch.Generator().manual_seed(5 + seed)
-        k = torch.randint(-3, 4, (n, hd), generator=g).float()           # any keys: q = 0 makes every score zero
-        return torch.zeros(n, hd), k, torch.ones(n, n, dtype=torch.bool)
+        k = torch.randint(-3, 4, (nkv, hd), generator=g).float()         # any keys: q = 0 makes every score zero
+        return torch.zeros(nq, hd), k, torch.ones(nq, nkv, dtype=torch.bool)
     if pattern == "onehot":
-        code, r = index_code(n, hd)
-        pi = permutation(n, seed) if pi is None else pi
+        code, r = index_code(nkv, hd)
+        if pi is None:
+            pi = permutation(max(nq, nkv), seed)[:nq] % nkv
+            pi[0] = nkv - 1
         gain = power_of_two_at_least(GAP / (2 * r * scale * LOG2E) * 1.01)
-        sel = torch.zeros(n, n, dtype=torch.bool)
-        sel[torch.arange(n), pi] = True
+        sel = torch.zeros(nq, nkv, dtype=torch.bool)
+        sel[torch.arange(nq), pi] = True
         return gain * code[pi], code, sel
     if pattern == "strided":
         stride = hd if stride is None else stride
         assert stride <= hd
-        eye = torch.eye(hd)[torch.arange(n) % stride]
+        stride = min(stride, nkv)
         gain = power_of_two_at_least(GAP / (scale * LOG2E) * 1.01)
-        sel = (torch.arange(n)[:, None] % stride) == (torch.arange(n)[None, :] % stride)
-        return gain * eye, eye, sel
+        sel = (torch.arange(nq)[:, None] % stride) == (torch.arange(nkv)[None, :] % stride)
+        return gain * torch.eye(hd)[torch.arange(nq) % stride], torch.eye(hd)[torch.arange(nkv) % stride], sel
     raise ValueError(pattern)
+
+
+def make(pattern, n, hd, scale, *, stride=None, pi=None, seed=0):
+    """The square case of ``make_rect``: one sequence of n tokens."""
+    return make_rect(pattern, n, n, hd, scale, stride=stride, pi=pi, seed=seed)
 
 
 def scores_log2(q, k, scale, kind):
@@ -103,7 +115,8 @@ def scores_log2(q, k, scale, kind):
     q, k = q.half().float(), k.half().float()
     if kind == "spatial":                 # Q pre-multiplied by scale * log2 e, one rounding to fp16
         return (q * sl).half().float() @ k.t()
-    if kind == "temporal":                # scaled after the product
+    if kind in ("temporal", "unscaled"):  # scaled after the product: sp_attn_temporal_f16, and the fp32 logits of the
+        #                                   unscaled fp16 operands of csrc/attention_kv.hip and attention_wide.hip
         return (q @ k.t()) * sl
     if kind == "small":                   # q * scale in fp32, log2 e at the exponential
         return ((q * torch.tensor(scale, dtype=torch.float32)) @ k.t()) * torch.tensor(LOG2E, dtype=torch.float32)
@@ -171,6 +184,12 @@ SPATIAL_LONG = [4096, 4608]                        # sp_attn_spatial_long_f16's 
 TEMPORAL_FRAMES = [1, 14, 16, 17, 25, 32]
 TEMPORAL_HW = [9, 37]
 SMALL = [(1, 8), (65, 40), (257, 80), (280, 128), (512, 40)]
+# sp_attn_spatial_kv_f16 (seq_q != seq_kv): the edges of its 256-row workgroup and of its 64-key tile
+RECT_Q = [1, 33, 255, 256, 257, 320]
+RECT_KV = [1, 63, 64, 65, 128, 129, 200]
+# sp_attn_wide_f16: the edges of its 64-key tile and of its 128-row workgroup
+WIDE_D = [128, 256, 512]
+WIDE_SEQ = [1, 63, 64, 65, 127, 128, 129, 200]
 
 
 def temporal_stride(frames):
@@ -310,3 +329,62 @@ def model(kind, qq, kk, vv, batch, hw, heads, n, hd, scale, mutant=None):
         for i in {n - 1, min(n, 128) - 1}:
             out[:, i] = out[:, i - 1]
     return out.reshape(batch, hw, heads, n, hd)
+
+
+# ------------------------------------------------------------------------------------------------ rectangular statement
+# csrc/attention_kv.hip (and, with head_dim 128 / 256 / 512 and seq_q = seq_kv, csrc/attention_wide.hip): seq_q queries
+# against seq_kv keys.  A lane holds 32 of the 64 scores a query has in a tile -- the keys with bit 2 of the index equal
+# to the lane half -- and, of the output row, the channels with bit 2 equal to the lane half.
+KV_MUTANTS = ("last key dropped", "ragged tile's mask one key early", "clamped copy of the last key counted",
+              "score halves not exchanged before the maximum", "accumulator not rescaled when the maximum rises")
+
+
+def kv_applies(mutant, nkv):
+    """Where a rectangular mutant has something to act on: the mask exists only in a ragged last tile, the accumulator is
+    rescaled only from the second tile on."""
+    return {"last key dropped": nkv >= 2, "ragged tile's mask one key early": nkv % 64 != 0,
+            "clamped copy of the last key counted": nkv % 64 != 0, "score halves not exchanged before the maximum": True,
+            "accumulator not rescaled when the maximum rises": nkv > 64}[mutant]
+
+
+def _kv_halves_apart(s, v, c):
+    """The tiled loop of ``kv_statement`` with the row maximum taken per lane half: each half keeps its own m and l and
+    rescales the channels it holds; the P.V product sums over both halves' keys, as the MFMA does."""
+    nk, hd = s.shape[-1], v.shape[-1]
+    khalf, chalf = (torch.arange(nk) >> 2) & 1, (torch.arange(hd) >> 2) & 1
+    m = torch.full(s.shape[:-1] + (2,), float("-inf"))
+    l, o = torch.zeros_like(m), torch.zeros(s.shape[:-1] + (hd,))
+    for t0 in range(0, nk, 64):
+        st, ht = s[..., t0:t0 + 64], khalf[t0:t0 + 64]
+        mt = torch.stack([torch.where(ht == h, st, torch.full_like(st, float("-inf"))).amax(-1) for h in (0, 1)], -1)
+        m_new = torch.maximum(m, mt)
+        alpha = torch.exp2((m - m_new) * c)
+        p = torch.exp2(st * c - m_new[..., ht] * c)
+        l = l * alpha + torch.stack([(p * (ht == h)).sum(-1) for h in (0, 1)], -1)
+        m, o = m_new, o * alpha[..., chalf] + p.half().float() @ v[..., t0:t0 + 64, :]
+    return (o / l.sum(-1, keepdim=True)).half()
+
+
+def kv_statement(q, k, v, scale=0.125, mutant=None):
+    """attn_kv_kernel's rounding points, from the head of csrc/attention_kv.hip: fp32 scores of the unscaled fp16 operands,
+    tiles of 64 keys with a plain running maximum, p = exp2(s c - m c), row sums of the fp32 p, p rounded to fp16 for P.V,
+    fp32 sums, one division, fp16 output.  q [...][nq][hd], k, v [...][nkv][hd]; ``mutant``: one of KV_MUTANTS planted."""
+    c = torch.tensor(scale * LOG2E, dtype=torch.float32)
+    if mutant == "clamped copy of the last key counted":
+        k, v = [torch.cat([t, t[..., -1:, :]], dim=-2) for t in (k, v)]
+    s = q @ k.transpose(-1, -2)
+    if mutant in ("last key dropped", "ragged tile's mask one key early"):      # (a masked logit is -inf: p is exactly 0)
+        s = s.clone()
+        s[..., -1] = float("-inf")
+    if mutant == "score halves not exchanged before the maximum":
+        return _kv_halves_apart(s, v, c)
+    m = torch.full_like(s[..., :1], float("-inf"))
+    l, o = torch.zeros_like(m), torch.zeros(s.shape[:-1] + v.shape[-1:])
+    for t0 in range(0, s.shape[-1], 64):
+        st = s[..., t0:t0 + 64]
+        m_new = torch.maximum(m, st.amax(-1, keepdim=True))
+        alpha = torch.exp2((m - m_new) * c)
+        p = torch.exp2(st * c - m_new * c)
+        keep = mutant == "accumulator not rescaled when the maximum rises" and t0 > 0
+        m, l, o = m_new, l * alpha + p.sum(-1, keepdim=True), (o if keep else o * alpha) + p.half().float() @ v[..., t0:t0 + 64, :]
+    return (o / l).half()

@@ -28,7 +28,8 @@ def install(setattr_):
     def recorder(name):
         def f(*a, **k):
             launches.append(Launch(name, a, k))
-            return 1024 if name.endswith("_bytes") else a[2] if name == "gemm" else None
+            # (the two contraction wrappers return their destination: ``out`` is argument 2 of gemm, 5 of gemm_f8)
+            return 1024 if name.endswith("_bytes") else a[2] if name == "gemm" else a[5] if name == "gemm_f8" else None
         return f
 
     for name in wrapper_names():

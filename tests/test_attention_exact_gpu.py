@@ -10,6 +10,10 @@ sp_attn_spatial_long_f16 runs at both sp_attn_long_set_occupancy settings.  Patt
 in the query's own 256-block or in K/V tile 0 must leave every flag word zero (the frozen-reference kernel produced the
 bytes); the one-hot pattern with far keys must flag exactly the blocks whose queries look far, and still be exact.
 
+sp_attn_spatial_kv_f16 (seq_q != seq_kv) and sp_attn_wide_f16 (head_dim 128 / 256 / 512) take ``make_rect`` patterns through
+``run_rect``: q, k and v in three buffers of three pitches.  Both form fp32 logits from the unscaled fp16 operands
+(``check_selection`` kind "unscaled").
+
 Held to one ulp instead of bit-equality: sp_attn_temporal_f16 where the number of selected keys is no power of two (it
 rounds P / l to fp16 before the P.V product: ``v_cvt_f16_f32`` of ``pv * inv``, csrc/attention.hip:360)."""
 import functools
@@ -121,6 +125,75 @@ def test_attention_spatial_long_exact(ops, seq, pattern, occ):
     assert torch.equal(flags, expect), f"flagged blocks {flags.nonzero().tolist()} expected {expect.nonzero().tolist()}"
     assert (waves > 0) == bool(far) and waves <= 4 * int(expect.sum())
     print(f"long {pattern} seq {seq} occupancy {occ}: {share:.0%} of the outputs held bit-equal, {int(flags.sum())} blocks flagged")
+
+
+def run_rect(call, q, k, v):
+    """The rectangular counterpart of ``run``: q [nq][hd], k [nkv][hd], v [batch][1][heads][nkv][hd].  q, k and v are column
+    slices of three buffers of three different pitches whose other columns are NaN; the output slice lies between NaN guard
+    rows and guard columns.  Calls ``call(qs, ks, vs, out, ldq, ldk, ldv, ldo)``; returns [batch][1][heads][nq][hd]."""
+    batch, _, heads, nkv, hd = v.shape
+    nq, c = q.shape[0], heads * hd
+    rows = [q[None, :, None, :].expand(batch, nq, heads, hd).reshape(batch * nq, c),
+            k[None, :, None, :].expand(batch, nkv, heads, hd).reshape(batch * nkv, c), v[:, 0].permute(0, 2, 1, 3).reshape(batch * nkv, c)]
+    views, lds = [], []
+    for t, (front, back) in zip(rows, ((8, 8), (16, 24), (24, 48))):
+        buf = torch.full((t.shape[0], front + c + back), float("nan"), dtype=torch.float16)
+        buf[:, front:front + c] = t.half()
+        views.append(buf.to(DEV)[:, front:front + c])
+        lds.append(front + c + back)
+    assert len(set(lds)) == 3
+    obuf = torch.full((batch * nq + 2 * GUARD, c + 2 * P.SLACK), float("nan"), dtype=torch.float16, device=DEV)
+    call(*views, obuf[GUARD:GUARD + batch * nq, P.SLACK:P.SLACK + c], *lds, obuf.stride(0))
+    torch.cuda.synchronize()
+    got = obuf.cpu()
+    assert torch.isnan(got[:GUARD]).all() and torch.isnan(got[GUARD + batch * nq:]).all(), "guard rows written"
+    assert torch.isnan(got[:, :P.SLACK]).all() and torch.isnan(got[:, P.SLACK + c:]).all(), "guard columns written"
+    return got[GUARD:GUARD + batch * nq, P.SLACK:P.SLACK + c].float().reshape(batch, nq, 1, heads, hd).permute(0, 2, 3, 1, 4)
+
+
+@pytest.mark.parametrize("pattern", P.PATTERNS)
+@pytest.mark.parametrize("seq_kv", P.RECT_KV)
+@pytest.mark.parametrize("seq_q", P.RECT_Q)
+def test_attention_spatial_kv_exact(ops, seq_q, seq_kv, pattern):
+    """sp_attn_spatial_kv_f16 on the whole cross product of the edges of its 256-row workgroup and of its 64-key tile
+    (tests/test_exact_patterns_cpu.py: what each pattern sees there)."""
+    batch, heads = 2, 2
+    q, k, sel = P.make_rect(pattern, seq_q, seq_kv, 64, 0.125)
+    P.check_selection(q, k, sel, 0.125, "unscaled")
+    v = P.values(batch, 1, heads, seq_kv, 64, seed=seq_q + seq_kv)
+    got = run_rect(lambda qs, ks, vs, o, ldq, ldk, ldv, ldo: ops.attn_spatial_kv(qs, ks, vs, o, ldq=ldq, ldk=ldk, ldv=ldv, ldo=ldo, batch=batch,
+                                                                                seq_q=seq_q, seq_kv=seq_kv, heads=heads), q, k, v)
+    share = judge(got, sel, v, f"sp_attn_spatial_kv_f16 {pattern} {seq_q} x {seq_kv}")
+    print(f"spatial_kv {pattern} {seq_q} x {seq_kv}: {share:.0%} of the outputs held bit-equal")
+    if pattern == "onehot" or (seq_kv & (seq_kv - 1)) == 0 and pattern == "uniform":
+        assert share == 1.0
+
+
+@pytest.mark.parametrize("with_bias", [False, True])
+@pytest.mark.parametrize("pattern", P.PATTERNS)
+@pytest.mark.parametrize("seq", P.WIDE_SEQ)
+@pytest.mark.parametrize("d", P.WIDE_D)
+def test_attention_wide_exact(ops, d, seq, pattern, with_bias):
+    """sp_attn_wide_f16 (one head of 128 / 256 / 512 channels, scale 1 / sqrt(d)) at the edges of its 64-key tile and of its
+    128-row workgroup.  The fp32 bias holds integers in [-3, 3]: the expected sum is S + bias x count, i.e. the bias is
+    added to the expected mean before the criterion is applied."""
+    batch, scale = 2, d ** -0.5
+    q, k, sel = P.make_rect(pattern, seq, seq, d, scale, stride=64)
+    P.check_selection(q, k, sel, scale, "unscaled")
+    v = P.values(batch, 1, 1, seq, d, seed=seq + d)
+    bias = (torch.arange(d) % 7 - 3).float() if with_bias else None
+    dev_bias = None if bias is None else bias.to(DEV)
+    got = run_rect(lambda qs, ks, vs, o, ldq, ldk, ldv, ldo: ops.attn_wide(qs, ks, vs, o, ldq=ldq, ldk=ldk, ldv=ldv, ldo=ldo, batch=batch, seq=seq,
+                                                                          head_dim=d, scale=scale, bias=dev_bias), q, k, v)
+    s, count = P.expected(sel, v)
+    if with_bias:
+        s = s + bias.double() * count.double()[:, None]
+    bad = P.violations(got, s, count)
+    assert not bad, f"sp_attn_wide_f16 {pattern} d {d} seq {seq} bias {with_bias}: {bad}"
+    share = P.must_be_bit_equal(s, count)
+    print(f"wide {pattern} d {d} seq {seq} bias {with_bias}: {share:.0%} of the outputs held bit-equal")
+    if pattern == "onehot" or (seq & (seq - 1)) == 0 and pattern == "uniform":
+        assert share == 1.0
 
 
 @pytest.mark.parametrize("pattern", P.PATTERNS)

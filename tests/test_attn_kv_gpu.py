@@ -4,7 +4,8 @@ maximum rises in every key tile, and the refusals."""
 import pytest
 import torch
 
-from tests.test_kernels_gpu import LOG2E, _attn_fp64, _per_row_err, check, h, rel_l2
+from tests.attention_patterns import kv_statement as _kv_statement      # (the kernel's rounding points; shared with the CPU mutants)
+from tests.test_kernels_gpu import _attn_fp64, _per_row_err, check, h, rel_l2
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -60,23 +61,6 @@ def test_attn_spatial_kv_matches_fp64_softmax(batch, seq_q, seq_kv, heads):
     check(got, ref, l2=3e-3, mx=2e-2)
     if seq_kv == 1:
         assert torch.equal(got, v.expand_as(got)), "one key: every output row is that V row"
-
-
-def _kv_statement(q, k, v, scale=0.125):
-    """attn_kv_kernel's rounding points, from the head of csrc/attention_kv.hip: fp32 scores of the unscaled fp16 operands,
-    tiles of 64 keys with a plain running maximum, p = exp2(s c - m c), row sums of the fp32 p, p rounded to fp16 for P.V,
-    fp32 sums, one division, fp16 output."""
-    c = torch.tensor(scale * LOG2E, dtype=torch.float32)
-    s = q @ k.transpose(-1, -2)
-    m = torch.full_like(s[..., :1], float("-inf"))
-    l, o = torch.zeros_like(m), torch.zeros_like(q)
-    for t0 in range(0, s.shape[-1], 64):
-        st = s[..., t0:t0 + 64]
-        m_new = torch.maximum(m, st.amax(-1, keepdim=True))
-        alpha = torch.exp2((m - m_new) * c)
-        p = torch.exp2(st * c - m_new * c)
-        m, l, o = m_new, l * alpha + p.sum(-1, keepdim=True), o * alpha + p.half().float() @ v[..., t0:t0 + 64, :]
-    return (o / l).half()
 
 
 def test_attn_spatial_kv_peaked_rows_judged_per_row():

@@ -8,7 +8,10 @@ The first two are ALSO run with the fuzz's Gaussian operands at the shapes where
 fuzz's 3e-3 on the global and the worst-block error: the reason for the exact tests.
 
 Attention.  fp32 statements of the three kernels' rounding points pass every pattern at every size of the GPU tests, and
-each of eight indexing bugs breaks the criterion in at least one pattern at every size where it applies."""
+each of eight indexing bugs breaks the criterion in at least one pattern at every size where it applies.
+
+Rectangular attention (``attention_patterns.make_rect``; csrc/attention_kv.hip, csrc/attention_wide.hip): see
+``test_rectangular_statement_passes_and_every_mutant_breaks_a_pattern`` for what the patterns see and what they cannot."""
 import os
 import random
 import sys
@@ -246,3 +249,107 @@ def test_attention_models_pass_and_every_mutant_breaks_a_pattern(kind, n, hw, hd
                 caught[mutant] = pattern
     print(f"{kind} n={n} hw={hw} head_dim={hd}: {caught}")
     assert all(caught.values()), f"invisible at this size: {[m for m, p in caught.items() if p is None]}"
+
+
+# ------------------------------------------------------------------------------------------------ rectangular attention
+def _make_before(pattern, n, hd, scale, *, stride=None, pi=None, seed=0):
+    """``attention_patterns.make`` as it was before ``make_rect`` existed, kept verbatim: the square patterns of the older
+    kernels' GPU tests must not move."""
+    if pattern == "uniform":
+        g = torch.Generator().manual_seed(5 + seed)
+        k = torch.randint(-3, 4, (n, hd), generator=g).float()
+        return torch.zeros(n, hd), k, torch.ones(n, n, dtype=torch.bool)
+    if pattern == "onehot":
+        code, r = P.index_code(n, hd)
+        pi = P.permutation(n, seed) if pi is None else pi
+        gain = P.power_of_two_at_least(P.GAP / (2 * r * scale * P.LOG2E) * 1.01)
+        sel = torch.zeros(n, n, dtype=torch.bool)
+        sel[torch.arange(n), pi] = True
+        return gain * code[pi], code, sel
+    if pattern == "strided":
+        stride = hd if stride is None else stride
+        assert stride <= hd
+        eye = torch.eye(hd)[torch.arange(n) % stride]
+        gain = P.power_of_two_at_least(P.GAP / (scale * P.LOG2E) * 1.01)
+        sel = (torch.arange(n)[:, None] % stride) == (torch.arange(n)[None, :] % stride)
+        return gain * eye, eye, sel
+    raise ValueError(pattern)
+
+
+def test_make_returns_what_it_returned_before_make_rect():
+    """Bit comparison at every size and stride the square GPU tests use (the long kernel's maps included)."""
+    cases = [(n, 64, 0.125, None, None) for n in P.SPATIAL_SHORT + P.SPATIAL_MID + P.SPATIAL_LONG]
+    cases += [(f, 64, 0.125, P.temporal_stride(f), None) for f in P.TEMPORAL_FRAMES]
+    cases += [(n, hd, hd ** -0.5, min(hd, 64), None) for n, hd in P.SMALL]
+    cases += [(n, 64, 0.125, None, P.far_map(n, (1, n // 256 - 2))) for n in P.SPATIAL_LONG]
+    for n, hd, scale, stride, pi in cases:
+        for pattern in P.PATTERNS:
+            now, before = P.make(pattern, n, hd, scale, stride=stride, pi=pi), _make_before(pattern, n, hd, scale, stride=stride, pi=pi)
+            for a, b in zip(now, before):
+                assert a.dtype == b.dtype and a.shape == b.shape
+                assert torch.equal(a.view(torch.int32) if a.dtype == torch.float32 else a, b.view(torch.int32) if b.dtype == torch.float32 else b), \
+                    f"make({pattern!r}, {n}, {hd}) moved"
+
+
+@pytest.mark.parametrize("nq", P.RECT_Q)
+def test_rectangular_statement_passes_and_every_mutant_breaks_a_pattern(nq):
+    """Every (seq_q, seq_kv) of the GPU test of sp_attn_spatial_kv_f16: the patterns are selections for scores formed the
+    way the kernel forms them, the clean statement of its rounding points (``attention_patterns.kv_statement``) meets the
+    criterion, and each planted mistake breaks it in at least one pattern wherever it has something to act on.
+
+    What the patterns cannot see (asserted below, so that this list stays true):
+    * the clamped copy of the last key counted as key seq_kv: invisible to ``onehot`` at every shape (query 0 selects the
+      last key; the copy doubles S and count alike) and to EVERY pattern at seq_kv = 1, where the copy of the only key
+      changes no mean.  ``uniform`` sees it at every other ragged seq_kv, ``strided`` where a query of the shape selects
+      the last key.
+    * the two 32-key halves not exchanged: invisible to ``uniform`` from seq_kv = 5 (both halves hold a key and every score
+      is zero, so both maxima are equal); seen by ``onehot`` and ``strided`` at every shape.
+    * the accumulator not rescaled: seen by ``onehot`` only (under ``uniform`` and ``strided`` the first tile already holds
+      a selected key and the maximum never rises); it needs a second tile, seq_kv > 64.
+    * a dropped or masked last key: ``uniform`` and ``onehot`` at every shape; ``strided`` only where a query selects it.
+    In the statement a masked key and a dropped key are the same thing (p is exactly 0); the two mutants differ in where
+    they apply: the mask exists only in a ragged last tile."""
+    batch, heads = 2, 2
+    for nkv in P.RECT_KV:
+        v = P.values(batch, 1, heads, nkv, 64, seed=nq + nkv)
+        caught = {m: [] for m in P.KV_MUTANTS if P.kv_applies(m, nkv)}
+        for pattern in P.PATTERNS:
+            q, k, sel = P.make_rect(pattern, nq, nkv, 64, 0.125)
+            P.check_selection(q, k, sel, 0.125, "unscaled")
+            s, count = P.expected(sel, v)
+            if pattern == "onehot":
+                assert P.must_be_bit_equal(s, count) == 1.0
+                assert bool(sel[0, nkv - 1]), "query 0 selects the last key"
+            bad = P.violations(P.kv_statement(q, k, v[:, 0]).float().unsqueeze(1), s, count)
+            assert not bad, f"the clean statement, {pattern} {nq} x {nkv}: {bad}"
+            for mutant in caught:
+                if P.violations(P.kv_statement(q, k, v[:, 0], mutant=mutant).float().unsqueeze(1), s, count):
+                    caught[mutant].append(pattern)
+        for mutant, seen in caught.items():
+            if mutant == "clamped copy of the last key counted":
+                assert "onehot" not in seen and (seen == [] if nkv == 1 else "uniform" in seen), (nq, nkv, mutant, seen)
+            elif mutant == "score halves not exchanged before the maximum":
+                assert {"onehot", "strided"} <= set(seen) and (("uniform" in seen) == (nkv < 5)), (nq, nkv, mutant, seen)
+            elif mutant == "accumulator not rescaled when the maximum rises":
+                assert seen == ["onehot"], (nq, nkv, mutant, seen)
+            else:
+                assert {"uniform", "onehot"} <= set(seen), (nq, nkv, mutant, seen)
+
+
+@pytest.mark.parametrize("d", P.WIDE_D)
+def test_wide_patterns_are_selections_and_the_statement_passes(d):
+    """sp_attn_wide_f16's shapes (square, head_dim 128 / 256 / 512, scale 1 / sqrt(d)): same score formation (fp32 logits of
+    the unscaled operands), same statement; with an integer bias the expected sum is S + bias x count."""
+    scale = d ** -0.5
+    bias = (torch.arange(d) % 7 - 3).double()
+    for seq in P.WIDE_SEQ:
+        v = P.values(2, 1, 1, seq, d, seed=seq + d)
+        for pattern in P.PATTERNS:
+            q, k, sel = P.make_rect(pattern, seq, seq, d, scale, stride=64)
+            P.check_selection(q, k, sel, scale, "unscaled")
+            s, count = P.expected(sel, v)
+            got = P.kv_statement(q, k, v[:, 0], scale).float().unsqueeze(1)
+            bad = P.violations(got, s, count)
+            assert not bad, f"the clean statement, {pattern} d {d} seq {seq}: {bad}"
+            biased = ((s / count.double()[:, None]).float() + bias.float()).half().float()     # the epilogue: fp32 add, one rounding
+            assert not P.violations(biased, s + bias * count.double()[:, None], count)

@@ -37,3 +37,31 @@ def test_attention_and_norm_fuzz():
     rng, g = random.Random(77), torch.Generator().manual_seed(77)
     for _ in range(90):
         fuzz_misc.one(rng, g)
+
+
+def test_new_kernel_fuzz():
+    """tools/fuzz_misc.py ``one_new``: sp_kv_pool_f16, sp_attn_spatial_kv_f16, sp_attn_wide_f16, sp_ln_quant_f8 and
+    sp_gemm_f8 in turn, a series of its own (the 90 draws above keep their shapes).  Every operand is a column slice of a
+    wider NaN-filled buffer, every pitch of a call differs, every output lies between guard rows and guard columns, no NaN
+    comes out and a second call into fresh buffers gives the same bits.  kv_pool and the plain / residual sp_gemm_f8 draws
+    are held EQUAL to their references; the attention kinds to 3e-3 relative L2 against an fp64 softmax of the same fp16
+    operands; GEGLU draws to 2e-3 / 1e-2 of max; sp_ln_quant_f8 to half an e4m3 step.
+    The series was run on the CPU first, references only (tests/test_fuzz_draws_cpu.py does so again): every reference is
+    finite and every integer-operand reference exactly representable in fp16."""
+    import collections
+    import fuzz_misc
+    rng, g = random.Random(fuzz_misc.NEW_SEED), torch.Generator().manual_seed(fuzz_misc.NEW_SEED)
+    worst, seen, gemms = collections.defaultdict(float), collections.Counter(), []
+    for i in range(fuzz_misc.NEW_DRAWS):
+        case, err = fuzz_misc.one_new(rng, g, i)
+        seen[case["kind"]] += 1
+        worst[case["kind"]] = max(worst[case["kind"]], err)
+        if case["kind"] == "gemm_f8":
+            gemms.append(case)
+    for kind in fuzz_misc.NEW_KINDS:
+        print(f"new kernel fuzz {kind}: {seen[kind]} draws, worst {worst[kind]:.3e}")
+    grid = [fuzz_misc.gemm_f8_tiles(c) for c in gemms]
+    print(f"new kernel fuzz gemm_f8 grids (row tiles, column tiles, K): {[(tm, tn, c['k']) for (tm, tn), c in zip(grid, gemms)]}")
+    assert all(seen[kind] >= 5 for kind in fuzz_misc.NEW_KINDS)
+    assert sum(tm >= 3 and tn >= 3 for tm, tn in grid) >= 5
+    assert sum(c["k"] == 640 for c in gemms) >= 3

@@ -108,9 +108,9 @@ def check_row_statistics_belong_to_the_operand(log):
     return from_epilogue
 
 
-def run_unet(log, c, shape, *, chunks=None, euler=False):
+def run_unet(log, c, shape, *, chunks=None, euler=False, **switches):
     cfg = UNetConfig.tiny(c)
-    hip = unet_hip.SVDUNetHIP(cfg, random_state_dict(cfg, seed=47, dtype=torch.float16), "cpu")
+    hip = unet_hip.SVDUNetHIP(cfg, random_state_dict(cfg, seed=47, dtype=torch.float16), "cpu", **switches)
     if chunks:
         hip.FF_CHUNK_BYTES, hip.FF_CHUNK_ROUND = chunks
     log.clear()
@@ -182,6 +182,86 @@ def test_unet_launch_plan_with_a_switch_off(log, monkeypatch, switch, want):
     assert counts(log) == want
     assert check_tile_sums_come_from_the_producer(log) == want[2] + want[4]
     assert check_row_statistics_belong_to_the_operand(log) == 40
+
+
+SPATIAL_ATTENTION = ("attn_spatial", "attn_spatial_fp8", "attn_spatial_long", "attn_spatial_kv")
+BENCH_LATENT = (1, 14, 8, 72, 128)                     # the benchmark's latent: levels of 9,216 / 2,304 / 576 / 144 tokens
+
+
+def expected_route(h, w, kv, min_tokens, fp8, long):
+    """``SVDUNetHIP._self_attn``'s stated precedence, restated from its docstring."""
+    hw = h * w
+    if kv > 1 and hw >= min_tokens and h % kv == 0 and w % kv == 0:
+        return "attn_spatial_kv"
+    if fp8 and hw >= 1024:
+        return "attn_spatial_fp8"
+    if long and hw >= 8192 and hw % 256 == 0:
+        return "attn_spatial_long"
+    return "attn_spatial"
+
+
+@pytest.mark.parametrize("long_attention", [False, True])
+@pytest.mark.parametrize("fp8_attention", [False, True])
+@pytest.mark.parametrize("kv,min_tokens", [(1, 4096), (2, 4096), (4, 4096), (2, 1), (4, 1)])
+def test_spatial_attention_route_per_level(log, kv, min_tokens, fp8_attention, long_attention):
+    """Which spatial-attention wrapper every level of the benchmark latent records, for the cross product of the three
+    switches (and, beyond the default threshold of 4,096 tokens, with the threshold at 1: 18 x 32 divides by 2 and not by
+    4, 9 x 16 by neither).  Every pooled attention is preceded by exactly one kv_pool of that level's grid -- h and w in
+    this order, which only a non-square grid can tell -- whose outputs are the attention's K and V."""
+    b, f, _, h0, w0 = BENCH_LATENT
+    run_unet(log, 64, BENCH_LATENT, kv_downsample=kv, kv_downsample_min_tokens=min_tokens, fp8_attention=fp8_attention,
+             long_attention=long_attention, fp8_ff=False)
+    grids = {(h0 >> i) * (w0 >> i): (h0 >> i, w0 >> i) for i in range(4)}
+    seen = {hw: collections.Counter() for hw in grids}
+    for i, l in enumerate(log):
+        if l.name in SPATIAL_ATTENTION:
+            hw = l.kw["seq_q"] if l.name == "attn_spatial_kv" else l.kw["seq"]
+            seen[hw][l.name] += 1
+            assert l.kw["batch"] == b * f
+        if l.name == "attn_spatial_kv":
+            gh, gw = grids[l.kw["seq_q"]]
+            pool = log[i - 1]
+            assert pool.name == "kv_pool" and l.kw["seq_kv"] == gh * gw // (kv * kv)
+            assert (pool.kw["h"], pool.kw["w"], pool.kw["n_img"], pool.kw["factor"]) == (gh, gw, b * f, kv) and gh != gw
+            assert pool.kw["c"] == 64 * l.kw["heads"]
+            assert l.args[1] is pool.args[2] and l.args[2] is pool.args[3], "the attention does not read what the pool wrote"
+            assert l.args[0].data_ptr() + 2 * pool.kw["c"] == pool.args[0].data_ptr(), "the pool's K is not the K of this Q"
+    want = {hw: expected_route(gh, gw, kv, min_tokens, fp8_attention, long_attention) for hw, (gh, gw) in grids.items()}
+    assert {hw: set(n) for hw, n in seen.items()} == {hw: {name} for hw, name in want.items()}, (seen, want)
+    # 16 spatial transformers: two per level going down (three levels), one in the middle, three per level going up
+    assert {hw: sum(n.values()) for hw, n in seen.items()} == {9216: 5, 2304: 5, 576: 5, 144: 1}
+    assert sum(l.name == "kv_pool" for l in log) == sum(l.name == "attn_spatial_kv" for l in log)
+
+
+def test_fp8_ff_replaces_every_first_projection_and_no_second(log):
+    """``fp8_ff=True``: every GEGLU first projection (80 in the first plan above) is sp_ln_quant_f8 followed by sp_gemm_f8 on
+    the bytes and scales it wrote; no fp16 GEGLU contraction is left and no other contraction moved.  Together with
+    ``kv_downsample`` the pooled attention is recorded beside it."""
+    c, shape, _, base = UNET_PLANS[0]
+    run_unet(log, c, shape, fp8_ff=False)
+    plain = [l for l in log if l.name == "gemm"]
+    n_geglu = sum(bool(l.kw["geglu"]) for l in plain)
+    assert n_geglu > 0 and not any(l.name in ("gemm_f8", "ln_quant_f8") for l in log)
+    run_unet(log, c, shape, fp8_ff=True, kv_downsample=2, kv_downsample_min_tokens=1)
+    f8 = [i for i, l in enumerate(log) if l.name == "gemm_f8"]
+    assert len(f8) == n_geglu == sum(l.name == "ln_quant_f8" for l in log)
+    assert sum(l.name == "gemm" for l in log) == len(plain) - n_geglu and not any(l.name == "gemm" and l.kw["geglu"] for l in log)
+    for i in f8:
+        quant, l = log[i - 1], log[i]
+        assert quant.name == "ln_quant_f8" and l.kw["geglu"] and l.kw.get("res1") is None
+        assert l.args[0] is quant.args[2] and l.args[1] is quant.args[3] and l.kw["m"] == quant.kw["rows"] and l.kw["k"] == quant.kw["c"]
+        nxt = next(x for x in log[i + 1:] if x.name in ("gemm", "gemm_f8"))
+        assert nxt.name == "gemm" and nxt.args[0] is l.args[5], "the second projection is the fp16 contraction on the hidden tensor"
+    assert sum(l.name == "attn_spatial_kv" for l in log) == 16            # 16 x 16 down to 2 x 2: every level's grid divides by 2
+
+
+def test_every_switch_off_is_the_recorded_plan(log):
+    """kv_downsample=1, fp8_ff=False, fp8_attention=False given explicitly: the counts of UNET_PLANS, and none of the newer
+    wrappers."""
+    for c, shape, chunks, want in UNET_PLANS:
+        run_unet(log, c, shape, chunks=chunks, kv_downsample=1, fp8_ff=False, fp8_attention=False)
+        assert counts(log) == want
+        assert not any(l.name in ("kv_pool", "attn_spatial_kv", "ln_quant_f8", "gemm_f8", "attn_spatial_fp8") for l in log)
 
 
 def test_chunked_feed_forward_leaves_row_statistics_for_all_rows_or_none(log):

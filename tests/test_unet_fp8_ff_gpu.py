@@ -75,6 +75,48 @@ def test_fp8_ff_unet_matches_fake_quantised_oracle(b, frames, h, w):
     assert e8 <= FACTOR * floor
 
 
+def test_fp8_ff_with_kv_downsample_matches_the_doubly_patched_oracle(monkeypatch):
+    """``fp8_ff=True, kv_downsample=2`` in one engine: ``_ff1``'s e4m3 bytes and ``_self_attn``'s pooled K / V live in the same
+    stream scratch pool in the same forward.  Reference: the oracle under BOTH patches (fake-quantised first projections,
+    K and V pooled over 2 x 2 cells on the three levels whose grid divides).  Bound as in the test above: measured on that
+    oracle alone (FF1 inputs rounded to fp16 first, against not), times FACTOR; nothing from the engine enters it.  The
+    result differs from either single-switch engine's, and is the same bytes on a second call and with the feed-forward
+    pairs in row chunks (1,152 rows x 256 hidden in five chunks at level 0)."""
+    from tests.test_unet_kv_downsample_gpu import _pool_patch
+    from vdpp_amd.models.unet_hip import SVDUNetHIP
+    b, frames, h, w = 1, 3, 16, 24
+    kv = dict(kv_downsample=2, kv_downsample_min_tokens=1)
+    cfg, sd, ref, both = _build(3, fp8_ff=True, **kv)
+    g = torch.Generator().manual_seed(11 + b)
+    sample = torch.randn(b, frames, 8, h, w, generator=g).half()
+    ctx = torch.randn(b, 1, cfg.cross_attention_dim, generator=g).half()
+    ids = torch.tensor([[5.0, 127.0, 0.02]]).half()
+    t = 1.63777
+    with torch.no_grad(), monkeypatch.context() as mp:
+        assert sorted(_pool_patch(mp, h, w).values()) == [(4, 6), (8, 12), (16, 24)]
+        outs = []
+        for half in (False, True):
+            hooks = _fake_quantise(ref, half_inputs=half)
+            outs.append(ref(sample.float(), t, ctx.float(), ids.float())[0])
+            [hd.remove() for hd in hooks]
+    want, floor = outs[0], rel_l2(outs[1], outs[0])
+    args = (sample.to(DEV), t, ctx.to(DEV), ids.to(DEV))
+    got = both(*args)[0].clone()
+    assert torch.isfinite(got).all()
+    assert not torch.equal(got, SVDUNetHIP(cfg, sd, DEV, fp8_ff=True)(*args)[0]), "the same bytes as fp8_ff alone: nothing was pooled"
+    assert not torch.equal(got, SVDUNetHIP(cfg, sd, DEV, **kv)(*args)[0]), "the same bytes as kv_downsample alone: no fp8 projection"
+    assert torch.equal(both(*args)[0], got), "second call"
+    both.FF_CHUNK_BYTES, both.FF_CHUNK_ROUND = 1 << 17, 256
+    try:
+        assert torch.equal(both(*args)[0], got), "feed-forward pairs in row chunks"
+    finally:
+        both.FF_CHUNK_BYTES, both.FF_CHUNK_ROUND = 0, None
+    err = rel_l2(got.float(), want)
+    print(f"fp8_ff + kv_downsample=2 b={b} frames={frames} {h}x{w}: floor {floor:.3e}, engine vs doubly patched oracle {err:.3e} "
+          f"(bound {FACTOR * floor:.3e})")
+    assert err <= FACTOR * floor
+
+
 def test_fp8_ff_off_is_the_default_forward():
     """Flag absent (environment unset) and flag False: two engines from one state dict, the same bytes, no e4m3 pack."""
     from vdpp_amd.models.unet_hip import SVDUNetHIP
