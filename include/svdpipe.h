@@ -314,6 +314,24 @@ int sp_attn_spatial_f16(const void *q, const void *k, const void *v, void *o, in
 int sp_attn_temporal_f16(const void *q, const void *k, const void *v, void *o, int64_t ldq,
                          int64_t ldk, int64_t ldv, int64_t ldo, int batch, int frames, int64_t hw,
                          int heads, float scale, const void *zero_page, void *stream);
+/* Temporal self-attention for LONG clips (csrc/attention_temporal_long.hip): sp_attn_temporal_f16's layout and arithmetic
+ * for frames in 33 .. 128, the range that call refuses.  Token (f, p) of video b is row (b*frames + f)*hw + p; head hd is
+ * columns hd*64 .. hd*64+63; q, k, v, o: fp16 rows with pitches ldq, ldk, ldv, ldo in elements (>= heads*64, multiples of
+ * 8; q, k, v are normally column slices of one fused QKV buffer), 16-byte aligned.  One wave per (video, pixel, head): K
+ * and V of the sequence are staged in LDS once (2 * 16*ceil(frames/16) * 128 bytes) and the wave walks query blocks of 32
+ * frames against all keys; 64 / 96 / 128-key instantiations.
+ * Numerical contract (that of sp_attn_temporal_f16): scores are fp32 MFMA sums of the unscaled fp16 operands; two-pass
+ * softmax, p = exp2((s - max) * scale * log2 e) in fp32, fp32 row sum; P / l is rounded to fp16 BEFORE the P.V product;
+ * outputs accumulate in fp32 and are rounded to fp16 once.
+ * Tails: rows of Q, K and V at or beyond `frames` are read from zero_page (SP_ZERO_PAGE_BYTES of zeros) and such keys are
+ * masked; a query frame at or beyond `frames` is never stored.  No read or write touches a row outside its video or a
+ * column outside [0, heads*64).  No allocation, no synchronisation.
+ * Refused without a launch: null pointers (zero_page included), frames outside [33,128] (sp_attn_temporal_f16 serves 1 ..
+ * 32; more than 128 needs an online softmax this kernel does not have), counts that are not positive, a pitch below
+ * heads*64 or no multiple of 8, pointers not 16-byte aligned, a scale that is not positive and finite. */
+int sp_attn_temporal_long_f16(const void *q, const void *k, const void *v, void *o, int64_t ldq, int64_t ldk,
+                              int64_t ldv, int64_t ldo, int batch, int frames, int64_t hw, int heads, float scale,
+                              const void *zero_page, void *stream);
 /* sp_attn_spatial_f16 for LONG rows (csrc/attention_long.hip): same arguments, same results to fp16 rounding.
  * Two query blocks per wave, one or two waves per SIMD (sp_attn_long_set_occupancy below); after a warm-up over the
  * workgroup's own tokens and tile 0 (ordinary online softmax) each row's reference is frozen at the maximum seen so far and the remaining K/V tiles run without

@@ -89,6 +89,7 @@ SIGNATURES = {
     "sp_attn_fp8_ws_bytes": (_L, [_I, _I, _I]),
     "sp_attn_spatial_fp8": (_I, [_P, _P, _P, _P, _L, _L, _L, _L, _I, _I, _I, _F, _P, _L, _P, _P]),
     "sp_attn_temporal_f16": (_I, [_P, _P, _P, _P, _L, _L, _L, _L, _I, _I, _L, _I, _F, _P, _P]),
+    "sp_attn_temporal_long_f16": (_I, [_P, _P, _P, _P, _L, _L, _L, _L, _I, _I, _L, _I, _F, _P, _P]),
     "sp_attn_wide_f16": (_I, [_P, _P, _P, _P, _L, _L, _L, _L, _P, _I, _I, _I, _F, _P]),
     "sp_kv_pool_f16": (_I, [_P, _P, _L, _L, _P, _P, _L, _L, _I, _I, _I, _I, _I, _P]),
     "sp_attn_spatial_kv_f16": (_I, [_P, _P, _P, _P, _L, _L, _L, _L, _I, _I, _I, _I, _F, _P]),

@@ -413,6 +413,16 @@ def attn_temporal(q, k, v, o, *, ldq, ldk, ldv, ldo, batch, frames, hw, heads, s
     return o
 
 
+def attn_temporal_long(q, k, v, o, *, ldq, ldk, ldv, ldo, batch, frames, hw, heads, scale=0.125):
+    """``attn_temporal`` for 33 .. 128 frames (csrc/attention_temporal_long.hip): K and V of a sequence staged in LDS, query
+    blocks of 32 frames against all keys; the arithmetic contract of ``attn_temporal``."""
+    with _Timed("attn_temporal_long", 4.0 * batch * hw * heads * frames * frames * 64, 4 * 2.0 * batch * frames * hw * heads * 64):
+        _check(load().sp_attn_temporal_long_f16(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), ldq, ldk, ldv, ldo,
+                                                batch, frames, hw, heads, scale, zero_page(o.device).data_ptr(), _stream()),
+               "sp_attn_temporal_long_f16")
+    return o
+
+
 def pack_input(latent, image_latents, out, *, in_scale, b, frames, h, w, cpad):
     _check(load().sp_pack_input_f16(_f16(latent, "latent").data_ptr(), _f16(image_latents, "image_latents").data_ptr(),
                                     out.data_ptr(), in_scale, b, frames, h, w, cpad, _stream()), "sp_pack_input_f16")

@@ -557,6 +557,10 @@ class StableVideoUNet(nn.Module):
         sample_shape = (latent.shape[0], 4) + tuple(latent.shape[2:])
         # with window_stride a long latent against a conditioning prepared for one window of W = num_frames frames
         frames = latent.shape[2] if self.window_stride is None else cond.num_frames
+        most = getattr(self.unet, "MAX_FRAMES", None)          # (before anything is launched; the engine checks again)
+        if most is not None and frames > most:
+            raise ValueError(f"{frames} frames in one UNet call: the engine takes at most {most}; run longer clips as "
+                             f"overlapping frame windows (window_stride=, with num_frames = the window length <= {most})")
         # ValueError naming (total, tile, stride) of the axis, or (frames_total, window, stride); the plan's tables reach the device here
         self._step_plan(latent.shape[2], frames, latent.shape[3], latent.shape[4])
         if self.window_stride is not None:

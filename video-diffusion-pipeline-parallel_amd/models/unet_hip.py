@@ -452,7 +452,10 @@ class SVDUNetHIP(common._Engine):
         qkv = self._gemm(r, att["qkv"], resid.t, ln_stats=self._ln_stats(att["qkv"], resid)).t
         o = self._buf(r.m, c)
         q, k, v = qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:]
-        if temporal:
+        if temporal and r.f > 32:       # long clips: K/V of a sequence staged in LDS, query blocks of 32 frames
+            ops.attn_temporal_long(q, k, v, o, ldq=3 * c, ldk=3 * c, ldv=3 * c, ldo=c, batch=r.b, frames=r.f, hw=r.hw,
+                                   heads=heads)
+        elif temporal:
             ops.attn_temporal(q, k, v, o, ldq=3 * c, ldk=3 * c, ldv=3 * c, ldo=c, batch=r.b, frames=r.f, hw=r.hw,
                               heads=heads)
         elif self._kv_pooled(r):
@@ -576,6 +579,8 @@ class SVDUNetHIP(common._Engine):
         return self._gemm(r, p["pout"], mix, res1=x.t, r1scale=1.0, out=out, gn_next=gn_next)
 
     # ------------------------------------------------------------------ forward
+    MAX_FRAMES = 128      # frames per call: sp_attn_temporal_f16 up to 32, sp_attn_temporal_long_f16 up to 128
+
     def forward_rows(self, x_rows, *, b, frames, h, w, t_value, ctx16, added_ids32, euler=None, eps_out=None):
         """x_rows: fp16 [B*F*H*W][cin_pad] (see ``sp_pack_input_f16``); ``t_value``: fp32 device tensor [1]
         (continuous timestep) or [B] (one per video); ``ctx16``: fp16 [B][cross_dim]; ``added_ids32``: fp32 device [3]
@@ -590,6 +595,10 @@ class SVDUNetHIP(common._Engine):
         cfg, dev = self.cfg, self.device
         if h % 8 or w % 8:
             raise ValueError("latent height/width must be multiples of 8 (three stride-2 levels)")
+        if frames > self.MAX_FRAMES:
+            raise ValueError(f"{frames} frames in one UNet call: the temporal attention kernels take at most {self.MAX_FRAMES} "
+                             "(33 .. 128 through sp_attn_temporal_long_f16); longer clips run as overlapping frame windows "
+                             "(window_stride)")
         temb_dim, c0 = cfg.time_embed_dim, cfg.block_out_channels[0]
         # GroupNorm partial-sum scratch for the widest norm of the net (an up resnet's concatenation buffer)
         max_c = 2 * max(cfg.block_out_channels)
