@@ -412,6 +412,30 @@ int sp_attn_spatial_kv_f16(const void *q, const void *k, const void *v, void *o,
                            int64_t ldv, int64_t ldo, int batch, int seq_q, int seq_kv, int heads, float scale,
                            void *stream);
 
+/* FreeU (Si et al., "FreeU: Free Lunch in Diffusion U-Net"; no counterpart in the reference, opt-in) on the concatenation
+ * buffer an up resnet reads, IN PLACE (csrc/freeu.hip).  cat: fp16 rows [n_img*h*w][c_left + c_right] with pitch ld in
+ * elements: columns [0, c_left) the running tensor, [c_left, c_left + c_right) the skip; image i owns rows i*h*w ..
+ * (i+1)*h*w - 1 (row y*w + x of an image is pixel (y, x)).
+ * Backbone scale, columns [0, c_left/2): version 1 multiplies by b; version 2 by (b - 1)*mhat[p] + 1, m[p] the fp32 mean
+ * of pixel p over all c_left channels before any scaling, mhat = (m - lo)/(hi - lo) with lo, hi the minimum and maximum
+ * of m over the image; hi == lo gives mhat = 0, factor 1 (the widespread implementation returns NaN there).
+ * Skip filter, columns [c_left, c_left + c_right): ifftn(ifftshift(fftshift(fftn(x)) * mask)).real per image and channel,
+ * mask = s on rows h/2-1 .. h/2 and columns w/2-1 .. w/2 of the shifted spectrum (threshold 1: the frequencies {-1, 0} x
+ * {-1, 0}) and 1 elsewhere, evaluated as x + (s - 1)/(h w) * sum_j phi_j coef_j over the seven real functions 1, cos ay,
+ * sin ay, cos ax, sin ax, cos(ay + ax), sin(ay + ax): fp32 sums in a fixed order, no atomics, one rounding to fp16.  The
+ * same input gives the same bytes on every run.  s == 1 leaves the skip columns, b == 1 the backbone columns untouched.
+ * Nothing outside columns [0, c_left/2) and [c_left, c_left + c_right) of rows [0, n_img*h*w) is written.
+ * ws: at least the workspace size reported for the same (n_img, h, w, c_left, c_right), 4-byte aligned, owned by the
+ * caller and private to the call until it completes on `stream`; that size is 0 for a shape the call refuses.  No
+ * allocation, no synchronisation.
+ * Refused without a launch: null cat or ws, counts that are not positive, h or w below 2, c_left no multiple of 16, c_right
+ * no multiple of 8, ld below c_left + c_right or no multiple of 8, cat not 16-byte aligned, a version other than 1 or 2,
+ * b or s not finite and positive, ws_bytes below the reported size, h + w above 4096, a channel count above 2^30, 2^31 rows and
+ * more, or more workgroups than one grid holds. */
+size_t sp_freeu_ws_bytes(int n_img, int h, int w, int c_left, int c_right);
+int sp_freeu_f16(void *cat, int64_t ld, int n_img, int h, int w, int c_left, int c_right, float b, float s, int version,
+                 void *ws, size_t ws_bytes, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Layout / elementwise glue around the UNet (svd_unet.py:382-439).
  * ------------------------------------------------------------------------------------------- */

@@ -363,6 +363,24 @@ def attn_spatial_kv(q, k, v, o, *, ldq, ldk, ldv, ldo, batch, seq_q, seq_kv, hea
     return o
 
 
+def freeu_ws_bytes(n_img, h, w, c_left, c_right) -> int:
+    return int(load().sp_freeu_ws_bytes(n_img, h, w, c_left, c_right))
+
+
+def freeu(cat, ws, *, n_img, h, w, c_left, c_right, b, s, version=2):
+    """FreeU in place on a concatenation buffer ``cat`` [n_img*h*w][c_left + c_right] (csrc/freeu.hip): the first
+    ``c_left/2`` columns times the backbone factor (version 1: ``b``; version 2: ``(b - 1)*mhat + 1``), the last ``c_right``
+    through the Fourier filter that scales the frequencies {-1, 0} x {-1, 0} by ``s``.  ``ws``: tensor of at least
+    ``freeu_ws_bytes()`` bytes."""
+    rows = n_img * h * w
+    # algorithmic bytes: the mean pass reads the left half, the coefficient pass the right half, the apply pass reads and
+    # writes the right half and half of the left
+    with _Timed("freeu", 0.0, 2.0 * rows * ((c_left if version == 2 else 0) + 3 * c_right + c_left)):
+        _check(load().sp_freeu_f16(_f16(cat, "cat").data_ptr(), cat.stride(0), n_img, h, w, c_left, c_right, b, s, version,
+                                   ws.data_ptr(), ws.numel() * ws.element_size(), _stream()), "sp_freeu_f16")
+    return cat
+
+
 def attn_long_ws_bytes(batch, seq, heads) -> int:
     return int(load().sp_attn_long_ws_bytes(batch, seq, heads))
 

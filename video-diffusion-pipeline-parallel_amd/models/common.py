@@ -96,7 +96,8 @@ class StreamScratch:
     """Every per-stream scratch buffer of an engine: one uint8 tensor per (raw handle of the current HIP stream, name).
     Forwards on different streams may overlap in time, and two names never share an allocation.  Names in use: ``"gn"``
     GroupNorm partials, ``"splitk"`` split-K slabs, ``"fp8"`` fp8 attention operands, ``"long"`` flag words of the
-    long-row attention, ``"ff8"`` e4m3 feed-forward rows, ``"kvpool"`` pooled keys and values (``kv_downsample``)."""
+    long-row attention, ``"ff8"`` e4m3 feed-forward rows, ``"kvpool"`` pooled keys and values (``kv_downsample``), ``"freeu"`` FreeU's
+    pixel means and coefficient partials."""
 
     def __init__(self, device):
         self.device, self._bufs = device, {}

@@ -29,6 +29,7 @@ Fusions baked into the kernel calls:
 
 from __future__ import annotations
 
+import math
 import os
 from dataclasses import dataclass
 
@@ -39,6 +40,27 @@ from . import common
 from . import weights as W
 from .common import _Act, _Dense, _Norm, _f32
 from .unet_spec import UNetConfig, up_block_plan
+
+
+def parse_freeu(freeu, version):
+    """``SVDUNetHIP``'s ``freeu`` / ``freeu_version``, from the environment (``VDPP_FREEU="b1,b2,s1,s2"``,
+    ``VDPP_FREEU_VERSION``) where they are ``None`` -> ((b1, b2, s1, s2) or None, 1 or 2).  ValueError for anything but four
+    positive values that are finite in fp32 and a version of 1 or 2."""
+    if freeu is None and os.environ.get("VDPP_FREEU"):
+        freeu = os.environ["VDPP_FREEU"].split(",")
+    if version is None:
+        version = os.environ.get("VDPP_FREEU_VERSION", "2")
+    if isinstance(version, bool) or str(version).strip() not in ("1", "2"):
+        raise ValueError(f"freeu_version: {version!r} (1 or 2)")
+    if freeu is None:
+        return None, int(version)
+    try:
+        vals = tuple(float(v) for v in freeu)
+    except (TypeError, ValueError):
+        vals = ()
+    if len(vals) != 4 or not all(math.isfinite(v) and 0.0 < v <= 3.0e38 for v in vals):
+        raise ValueError(f"freeu: {freeu!r} (four finite positive values b1, b2, s1, s2)")
+    return vals, int(version)
 
 
 @dataclass
@@ -112,8 +134,15 @@ class SVDUNetHIP(common._Engine):
 
     def __init__(self, cfg: UNetConfig, state_dict: dict, device, *, fp8_attention: bool | None = None,
                  long_attention: bool | None = None, fp8_ff: bool | None = None, kv_downsample: int | None = None,
-                 kv_downsample_min_tokens: int = 4096):
-        """``kv_downsample``: 2 or 4 runs the SPATIAL self-attention of every level with at least
+                 kv_downsample_min_tokens: int = 4096, freeu=None, freeu_version: int | None = None):
+        """``freeu``: ``(b1, b2, s1, s2)`` applies FreeU (Si et al.) in front of every up resnet whose running tensor has
+        ``4*c0`` channels (``b1, s1``) or ``2*c0`` (``b2, s2``), ``c0 = block_out_channels[0]``: ``sp_freeu_f16`` in place on
+        the concatenation buffer, backbone scale on the first half of the running tensor's channels (``freeu_version`` 1: the
+        constant; 2, the default: weighted by the normalised channel mean) and the Fourier filter on the skip.  A buffer it
+        has modified reaches the resnet without its producers' column sums: that norm takes its statistics pass.  Default
+        ``None`` = off, or ``VDPP_FREEU="b1,b2,s1,s2"`` and ``VDPP_FREEU_VERSION``; off, every path launches what it
+        launched without the option.
+        ``kv_downsample``: 2 or 4 runs the SPATIAL self-attention of every level with at least
         ``kv_downsample_min_tokens`` tokens per frame (and a token grid that divides) over keys and values averaged over
         2 x 2 / 4 x 4 cells of the grid: every query is kept, a quarter / a sixteenth of the keys (``sp_kv_pool_f16``, then
         ``sp_attn_spatial_kv_f16``; there it takes precedence over the fp8 and long routes).  An approximation; default 1 =
@@ -139,6 +168,7 @@ class SVDUNetHIP(common._Engine):
         if self.kv_downsample not in (1, 2, 4) or isinstance(self.kv_downsample, bool):
             raise ValueError(f"kv_downsample: {self.kv_downsample!r} (1 = off, 2 or 4)")
         self.kv_downsample_min_tokens = int(kv_downsample_min_tokens)
+        self.freeu, self.freeu_version = parse_freeu(freeu, freeu_version)
         # the 16 transformer-entry GroupNorms folded into proj_in where a frame is whole tiles (VDPP_FOLD_GN=0: never)
         self.fold_groupnorm = os.environ.get("VDPP_FOLD_GN", "1") != "0"
         # a resnet's 1x1 shortcut convolution as an extra linear tap of its second 3x3 convolution (levels with more rows
@@ -445,6 +475,24 @@ class SVDUNetHIP(common._Engine):
         f = self.kv_downsample
         return f > 1 and r.hw >= self.kv_downsample_min_tokens and r.h % f == 0 and r.w % f == 0
 
+    def _freeu_pairs(self) -> dict:
+        """Channels of the running tensor -> FreeU's (b, s) in front of an up resnet: ``4*c0`` takes (b1, s1), ``2*c0``
+        (b2, s2), any other width nothing (the rule keys on the channel count, not on the level)."""
+        b1, b2, s1, s2 = self.freeu
+        c0 = self.cfg.block_out_channels[0]
+        return {4 * c0: (b1, s1), 2 * c0: (b2, s2)}
+
+    def _freeu_sites(self, h, w):
+        """(c_left, c_right, h, w) of every concatenation buffer FreeU works on in a forward over ``h`` x ``w`` latents."""
+        shift = len(self.down) - 1
+        sh, sw = h >> shift, w >> shift
+        for res, _, us in self.up:
+            for p in res:
+                if p["cx"] in self._freeu_pairs():
+                    yield p["cx"], p["cin"] - p["cx"], sh, sw
+            if us is not None:
+                sh, sw = 2 * sh, 2 * sw
+
     def _self_attn(self, r: _Run, att, xvec, resid: _Act, *, temporal: bool, **epi) -> _Act:
         """LayerNorm (folded into the fused Q/K/V projection) -> self-attention -> output projection + residual."""
         c = att["out"].n
@@ -608,6 +656,14 @@ class SVDUNetHIP(common._Engine):
         sk_bytes = max([8 * rows * c * 4 for rows, c in zip(level_rows, cfg.block_out_channels)
                         if rows <= self.SPLITK_MAX_ROWS], default=0)
         sk_ws = self._scratch.get("splitk", sk_bytes) if sk_bytes else None
+        # FreeU's workspace (pixel means, coefficient partials), sized once for the largest of its sites
+        fu_ws = None
+        if self.freeu is not None:
+            sites = list(self._freeu_sites(h, w))
+            if any(sh < 2 or sw < 2 for _, _, sh, sw in sites):
+                raise ValueError(f"freeu: a {h} x {w} latent leaves a level below 2 x 2, which has no frequency -1 to filter")
+            fu_ws = self._scratch.get("freeu", max([ops.freeu_ws_bytes(b * frames, sh, sw, ca, cb) for ca, cb, sh, sw in sites],
+                                                   default=0))
 
         # ---- embeddings: M = 1 GEMVs when the batch shares timestep and ids, else one row per video
         nt, nids = t_value.numel(), added_ids32.numel()
@@ -662,6 +718,11 @@ class SVDUNetHIP(common._Engine):
         for res, att, us in self.up:
             for j, p in enumerate(res):
                 cat = skips.pop()              # both halves are in place
+                if self.freeu is not None and p["cx"] in self._freeu_pairs():
+                    bb, ss = self._freeu_pairs()[p["cx"]]
+                    ops.freeu(cat.t, fu_ws, n_img=r.b * r.f, h=r.h, w=r.w, c_left=p["cx"], c_right=cat.t.shape[1] - p["cx"],
+                              b=bb, s=ss, version=self.freeu_version)
+                    cat = _Act(cat.t)          # the bare record: the producers' column sums describe the old values
                 last = j == len(res) - 1 and us is not None
                 if att:
                     x = self._run_resblock(r, p, cat, gn_next=True)                     # -> the transformer's entry norm

@@ -49,6 +49,11 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--kv-downsample", type=int, default=None, choices=[1, 2, 4],
                    help="spatial self-attention over keys and values pooled over 2x2 / 4x4 token cells (levels of at least "
                         "4,096 tokens per frame); an approximation, default 1 = off")
+    p.add_argument("--freeu", type=float, nargs=4, default=None, metavar=("B1", "B2", "S1", "S2"),
+                   help="FreeU in the UNet's up path: backbone scales b1, b2 and skip-filter scales s1, s2 (e.g. 1.3 1.4 0.9 0.2); "
+                        "default off")
+    p.add_argument("--freeu-version", type=int, default=None, choices=[1, 2],
+                   help="1: constant backbone scale; 2 (default): weighted by the normalised channel mean")
     p.add_argument("--balanced", action="store_true")
     p.add_argument("--backend", type=str, default="auto", choices=["auto", "gloo", "nccl"])
     p.add_argument("--init-method", type=str, default=None)
@@ -71,7 +76,8 @@ def main(argv=None) -> None:
     init_distributed(backend=backend, rank=rank, world_size=world, init_method=args.init_method)
 
     timesteps = StableVideoUNet._default_timestep_schedule(args.total_steps)
-    options = dict(eta=args.eta, s_noise=args.s_noise, fp8_ff=args.fp8_ff or None, kv_downsample=args.kv_downsample)
+    options = dict(eta=args.eta, s_noise=args.s_noise, fp8_ff=args.fp8_ff or None, kv_downsample=args.kv_downsample,
+                   freeu=args.freeu, freeu_version=args.freeu_version)
     model = (StableVideoUNet.from_random_init(timesteps, device=device, sampler=args.sampler, **options) if args.random_init
              else StableVideoUNet.from_pretrained(args.model_id, timesteps=timesteps, device=device, sampler=args.sampler,
                                                   **options))
