@@ -412,6 +412,30 @@ int sp_attn_spatial_kv_f16(const void *q, const void *k, const void *v, void *o,
                            int64_t ldv, int64_t ldo, int batch, int seq_q, int seq_kv, int heads, float scale,
                            void *stream);
 
+/* Spatial self-attention over a SLIDING WINDOW OF 8 x 8 TOKEN TILES (csrc/attention_window.hip; no counterpart in the
+ * reference: local attention, an approximation, opt-in).  A frame's tokens form an h x w grid, token (y, x) is row
+ * y*w + x of its image; tiles are 8 x 8 tokens, gh = h/8, gw = w/8.  The window (wh, ww) is counted in tiles, both odd;
+ * eh = min(wh, gh), ew = min(ww, gw).  A query of tile (ty, tx) attends to exactly the keys of tile rows [y0, y0 + eh)
+ * and tile columns [x0, x0 + ew), y0 = min(max(ty - wh/2, 0), gh - eh) (integer division) and x0 likewise: the window is
+ * shifted inwards at the borders, never cut, so every query has 64*eh*ew keys; wh >= gh and ww >= gw is full attention.
+ * O = softmax(scale * Q.K^T restricted to that key set).V per image and head, head_dim 64.
+ * q, k, v, o: fp16 rows [batch*h*w][heads*64]; pitches ldq, ldk, ldv, ldo in elements (>= heads*64, multiples of 8),
+ * 16-byte aligned (in the engine q, k, v are columns of the fused QKV buffer).
+ * Numerical contract (that of sp_attn_spatial_kv_f16): logits are fp32 MFMA sums, never rounded to fp16 or clamped;
+ * running maximum and sum per row are fp32, exp2 with scale*log2(e) folded in; probabilities are rounded to fp16 only as
+ * the operand of P.V; outputs accumulate in fp32 and are divided by the row sum once.  Finite inputs give finite outputs.
+ * Tails: none.  Every key tile a query meets is whole and inside its window (no mask, no -inf); where gw is no multiple of
+ * 4 the last workgroup of a tile row has waves without a query tile, which store nothing.  No read or write touches a row
+ * outside [b*h*w, (b+1)*h*w) of its image or a column outside [64 head, 64 head + 64).  No allocation, no
+ * synchronisation.
+ * Refused without a launch: null pointers, batch or heads not positive, h or w not a positive multiple of 8, wh or ww not
+ * positive and odd, a pitch below heads*64 or no multiple of 8, ldk or ldv of 2^24 or more or w*ldk, w*ldv of 2^28 or
+ * more (32-bit lane offsets over a tile's 8 token rows), misaligned pointers, a scale that is not positive and finite,
+ * more workgroups (batch*heads*gh*ceil(gw/4)) than a grid holds. */
+int sp_attn_spatial_window_f16(const void *q, const void *k, const void *v, void *o, int64_t ldq, int64_t ldk,
+                               int64_t ldv, int64_t ldo, int batch, int h, int w, int heads, int wh, int ww, float scale,
+                               void *stream);
+
 /* FreeU (Si et al., "FreeU: Free Lunch in Diffusion U-Net"; no counterpart in the reference, opt-in) on the concatenation
  * buffer an up resnet reads, IN PLACE (csrc/freeu.hip).  cat: fp16 rows [n_img*h*w][c_left + c_right] with pitch ld in
  * elements: columns [0, c_left) the running tensor, [c_left, c_left + c_right) the skip; image i owns rows i*h*w ..

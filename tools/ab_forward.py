@@ -4,7 +4,7 @@ them in flight on two HIP streams): the arms alternate for ROUNDS rounds, best a
 usage: ab_forward.py [--lib exp] [--rounds 5] [--steps 6] ARM ARM ...
 ARM = comma-separated settings: env:NAME=VALUE (process environment, e.g. env:SP_GEMM_DBG=256 with --lib exp) or
       unet:ATTR=0|1|INT|F/F/.. (attribute of the SVDUNetHIP engine, e.g. unet:fold_groupnorm=0, unet:FF_CHUNK_BYTES=176160768,
-      unet:freeu=1.3/1.4/0.9/0.2: a tuple of floats) or
+      unet:freeu=1.3/1.4/0.9/0.2: a tuple of floats, unet:spatial_window=5/7: all digits, a tuple of ints) or
       route:R=BM (sp_gemm_set_route(R, BM, 0) for the whole forward, e.g. route:2=0 = ping-pong kernels only) or
       occ:long=N (sp_attn_long_set_occupancy(N): the long-row attention kernel with one or two workgroups per CU); "base" = nothing."""
 import argparse, os, statistics, sys, time
@@ -54,8 +54,9 @@ def apply(arm):
             hip.load().sp_attn_long_set_occupancy(int(val))
         elif kind == "unet":
             defaults.setdefault(name, getattr(model.unet, name))
-            setattr(model.unet, name, tuple(map(float, val.split("/"))) if "/" in val else bool(int(val)) if val in ("0", "1")
-                    else int(val))
+            parts = val.split("/")
+            setattr(model.unet, name, tuple(map(int if all(p.isdigit() for p in parts) else float, parts)) if "/" in val
+                    else bool(int(val)) if val in ("0", "1") else int(val))
         else:
             raise SystemExit(f"unknown setting {item}")
 

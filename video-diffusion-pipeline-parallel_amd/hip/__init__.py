@@ -93,6 +93,7 @@ SIGNATURES = {
     "sp_attn_wide_f16": (_I, [_P, _P, _P, _P, _L, _L, _L, _L, _P, _I, _I, _I, _F, _P]),
     "sp_kv_pool_f16": (_I, [_P, _P, _L, _L, _P, _P, _L, _L, _I, _I, _I, _I, _I, _P]),
     "sp_attn_spatial_kv_f16": (_I, [_P, _P, _P, _P, _L, _L, _L, _L, _I, _I, _I, _I, _F, _P]),
+    "sp_attn_spatial_window_f16": (_I, [_P, _P, _P, _P, _L, _L, _L, _L, _I, _I, _I, _I, _I, _I, _F, _P]),
     "sp_freeu_ws_bytes": (_Z, [_I, _I, _I, _I, _I]),
     "sp_freeu_f16": (_I, [_P, _L, _I, _I, _I, _I, _I, _F, _F, _I, _P, _Z, _P]),
     "sp_pack_input_f16": (_I, [_P, _P, _P, _F, _I, _I, _I, _I, _I, _P]),

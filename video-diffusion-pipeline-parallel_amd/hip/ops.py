@@ -363,6 +363,18 @@ def attn_spatial_kv(q, k, v, o, *, ldq, ldk, ldv, ldo, batch, seq_q, seq_kv, hea
     return o
 
 
+def attn_spatial_window(q, k, v, o, *, ldq, ldk, ldv, ldo, batch, h, w, heads, wh, ww, scale=0.125):
+    """Spatial attention over a sliding window of 8 x 8 token tiles (csrc/attention_window.hip): a query of tile (ty, tx)
+    of the ``h x w`` token grid attends to the keys of ``min(wh, h/8) x min(ww, w/8)`` whole tiles around its own, the
+    window shifted inwards at the borders; the numerical contract of ``attn_spatial_kv``.  A window that covers the grid
+    is full attention."""
+    keys = 64 * min(wh, h // 8) * min(ww, w // 8)
+    with _Timed("attn_spatial_window", 4.0 * batch * heads * h * w * keys * 64):
+        _check(load().sp_attn_spatial_window_f16(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), ldq, ldk, ldv, ldo,
+                                                 batch, h, w, heads, wh, ww, scale, _stream()), "sp_attn_spatial_window_f16")
+    return o
+
+
 def freeu_ws_bytes(n_img, h, w, c_left, c_right) -> int:
     return int(load().sp_freeu_ws_bytes(n_img, h, w, c_left, c_right))
 

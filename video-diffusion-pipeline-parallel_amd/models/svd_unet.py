@@ -269,6 +269,7 @@ class StableVideoUNet(nn.Module):
         kv_downsample: int | None = None,
         freeu=None,
         freeu_version: int | None = None,
+        spatial_window=None,
         **kwargs,
     ) -> "StableVideoUNet":
         """Load ``<model_id>/unet/diffusion_pytorch_model*.safetensors`` from a LOCAL directory.
@@ -279,7 +280,9 @@ class StableVideoUNet(nn.Module):
         ``__init__``, which validates them; the reference's other keywords are accepted and ignored.  ``fp8_ff`` goes to
         the engine (``SVDUNetHIP(fp8_ff=)``: the GEGLU first projections on fp8 MFMA; default off), and so does ``kv_downsample``
         (``SVDUNetHIP(kv_downsample=)``: spatial self-attention over 2 x 2 / 4 x 4 pooled keys and values; default off)
-        and ``freeu`` / ``freeu_version`` (``SVDUNetHIP(freeu=(b1, b2, s1, s2))``: FreeU in the up path; default off).
+        and ``freeu`` / ``freeu_version`` (``SVDUNetHIP(freeu=(b1, b2, s1, s2))``: FreeU in the up path; default off) and
+        ``spatial_window`` (``SVDUNetHIP(spatial_window=(wh, ww))``: spatial self-attention over a sliding window of 8 x 8
+        token tiles; default off).
         """
         unet_dir = os.path.join(model_id, "unet")
         if not os.path.isdir(unet_dir):
@@ -323,7 +326,7 @@ class StableVideoUNet(nn.Module):
         if timesteps is None:
             timesteps = cls._default_timestep_schedule(num_steps=25)
         return cls(unet=SVDUNetHIP(cfg, sd, device, fp8_ff=fp8_ff, kv_downsample=kv_downsample, freeu=freeu,
-                                   freeu_version=freeu_version), timesteps=timesteps, dtype=torch_dtype,
+                                   freeu_version=freeu_version, spatial_window=spatial_window), timesteps=timesteps, dtype=torch_dtype,
                    **{k: v for k, v in kwargs.items() if k in STEP_OPTIONS})
 
     @classmethod
@@ -331,7 +334,7 @@ class StableVideoUNet(nn.Module):
                          device="cuda", fp8_attention: bool | None = None,
                          long_attention: bool | None = None, fp8_ff: bool | None = None,
                          kv_downsample: int | None = None, freeu=None, freeu_version: int | None = None,
-                         **step_options) -> "StableVideoUNet":
+                         spatial_window=None, **step_options) -> "StableVideoUNet":
         """Random weights of the exact SVD architecture (benchmarks / tests; no checkpoint needed); ``step_options``
         (``STEP_OPTIONS``) as for ``__init__``."""
         unknown = sorted(set(step_options) - set(STEP_OPTIONS))
@@ -340,7 +343,8 @@ class StableVideoUNet(nn.Module):
         cfg = config or UNetConfig.svd()
         sd = random_state_dict(cfg, seed=seed, device=device, dtype=torch.float16)
         unet = SVDUNetHIP(cfg, sd, device, fp8_attention=fp8_attention, long_attention=long_attention, fp8_ff=fp8_ff,
-                          kv_downsample=kv_downsample, freeu=freeu, freeu_version=freeu_version)
+                          kv_downsample=kv_downsample, freeu=freeu, freeu_version=freeu_version,
+                          spatial_window=spatial_window)
         del sd
         return cls(unet=unet, timesteps=timesteps, **step_options)
 

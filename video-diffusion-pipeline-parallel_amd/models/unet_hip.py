@@ -63,6 +63,27 @@ def parse_freeu(freeu, version):
     return vals, int(version)
 
 
+def parse_spatial_window(window):
+    """``SVDUNetHIP``'s ``spatial_window``, from the environment (``VDPP_SPATIAL_WINDOW="wh,ww"``) where it is ``None`` ->
+    (wh, ww) or None.  ValueError for anything but two odd positive integers (counted in 8 x 8 token tiles)."""
+    given = window
+    if window is None and os.environ.get("VDPP_SPATIAL_WINDOW"):
+        given = os.environ["VDPP_SPATIAL_WINDOW"]
+        try:
+            window = [int(v) for v in given.split(",")]
+        except ValueError:
+            window = ()
+    if window is None:
+        return None
+    try:
+        vals = tuple(window)
+    except TypeError:
+        vals = ()
+    if len(vals) != 2 or not all(isinstance(v, int) and not isinstance(v, bool) and v > 0 and v % 2 == 1 for v in vals):
+        raise ValueError(f"spatial_window: {given!r} (two odd positive integers wh, ww, in 8 x 8 token tiles)")
+    return vals
+
+
 @dataclass
 class _Run:
     """Per-forward state handed down the module tree."""
@@ -134,7 +155,8 @@ class SVDUNetHIP(common._Engine):
 
     def __init__(self, cfg: UNetConfig, state_dict: dict, device, *, fp8_attention: bool | None = None,
                  long_attention: bool | None = None, fp8_ff: bool | None = None, kv_downsample: int | None = None,
-                 kv_downsample_min_tokens: int = 4096, freeu=None, freeu_version: int | None = None):
+                 kv_downsample_min_tokens: int = 4096, freeu=None, freeu_version: int | None = None,
+                 spatial_window=None, spatial_window_min_tokens: int = 4096):
         """``freeu``: ``(b1, b2, s1, s2)`` applies FreeU (Si et al.) in front of every up resnet whose running tensor has
         ``4*c0`` channels (``b1, s1``) or ``2*c0`` (``b2, s2``), ``c0 = block_out_channels[0]``: ``sp_freeu_f16`` in place on
         the concatenation buffer, backbone scale on the first half of the running tensor's channels (``freeu_version`` 1: the
@@ -147,6 +169,13 @@ class SVDUNetHIP(common._Engine):
         2 x 2 / 4 x 4 cells of the grid: every query is kept, a quarter / a sixteenth of the keys (``sp_kv_pool_f16``, then
         ``sp_attn_spatial_kv_f16``; there it takes precedence over the fp8 and long routes).  An approximation; default 1 =
         off, or ``VDPP_KV_DOWNSAMPLE``; off, every path launches what it launched without the option.
+        ``spatial_window``: ``(wh, ww)``, two odd positive tile counts, runs the SPATIAL self-attention of every level with
+        at least ``spatial_window_min_tokens`` tokens per frame and a token grid that divides by 8 over a sliding window of
+        8 x 8 token tiles: a query sees the unblurred keys of ``wh x ww`` whole tiles around its own, the window shifted
+        inwards at the borders (``sp_attn_spatial_window_f16``; there it takes precedence over the fp8 and long routes, as
+        the pooled route does; a window that covers the grid is full attention).  An approximation; default ``None`` =
+        off, or ``VDPP_SPATIAL_WINDOW="wh,ww"``; off, every path launches what it launched without the option; not combined
+        with ``kv_downsample``.
         ``fp8_ff``: the first projection of every GEGLU feed-forward (spatial, temporal and ``ff_in``) as a W8A8
         contraction on the 2x-rate fp8 MFMA -- LayerNorm + per-row e4m3 quantisation (``sp_ln_quant_f8``), then ``sp_gemm_f8``
         with per-output-channel weight scales; the second projection stays fp16.  Default off, or ``VDPP_FP8_FF=1``; off,
@@ -168,6 +197,11 @@ class SVDUNetHIP(common._Engine):
         if self.kv_downsample not in (1, 2, 4) or isinstance(self.kv_downsample, bool):
             raise ValueError(f"kv_downsample: {self.kv_downsample!r} (1 = off, 2 or 4)")
         self.kv_downsample_min_tokens = int(kv_downsample_min_tokens)
+        self.spatial_window = parse_spatial_window(spatial_window)
+        if self.spatial_window is not None and self.kv_downsample > 1:
+            raise ValueError(f"spatial_window {self.spatial_window} and kv_downsample {self.kv_downsample}: the two approximations "
+                             "are not composed")
+        self.spatial_window_min_tokens = int(spatial_window_min_tokens)
         self.freeu, self.freeu_version = parse_freeu(freeu, freeu_version)
         # the 16 transformer-entry GroupNorms folded into proj_in where a frame is whole tiles (VDPP_FOLD_GN=0: never)
         self.fold_groupnorm = os.environ.get("VDPP_FOLD_GN", "1") != "0"
@@ -475,6 +509,10 @@ class SVDUNetHIP(common._Engine):
         f = self.kv_downsample
         return f > 1 and r.hw >= self.kv_downsample_min_tokens and r.h % f == 0 and r.w % f == 0
 
+    def _windowed(self, r: _Run) -> bool:
+        """Does this level's spatial self-attention run over a sliding window of 8 x 8 token tiles (``spatial_window``)?"""
+        return (self.spatial_window is not None and r.hw >= self.spatial_window_min_tokens and r.h % 8 == 0 and r.w % 8 == 0)
+
     def _freeu_pairs(self) -> dict:
         """Channels of the running tensor -> FreeU's (b, s) in front of an up resnet: ``4*c0`` takes (b1, s1), ``2*c0``
         (b2, s2), any other width nothing (the rule keys on the channel count, not on the level)."""
@@ -514,6 +552,10 @@ class SVDUNetHIP(common._Engine):
             ops.kv_pool(k, v, kp, vp, ldk=3 * c, ldv=3 * c, ldkp=c, ldvp=c, n_img=inst, h=r.h, w=r.w, c=c, factor=f)
             ops.attn_spatial_kv(q, kp, vp, o, ldq=3 * c, ldk=c, ldv=c, ldo=c, batch=inst, seq_q=r.hw, seq_kv=r.hw // (f * f),
                                 heads=heads)
+        elif self._windowed(r):
+            wh, ww = self.spatial_window
+            ops.attn_spatial_window(q, k, v, o, ldq=3 * c, ldk=3 * c, ldv=3 * c, ldo=c, batch=r.b * r.f, h=r.h, w=r.w,
+                                    heads=heads, wh=wh, ww=ww)
         elif self.fp8_attention and r.hw >= self.FP8_MIN_SEQ:
             ws = self._scratch.get("fp8", ops.attn_fp8_ws_bytes(r.b * r.f, r.hw, heads))
             ops.attn_spatial_fp8(q, k, v, o, ws, ldq=3 * c, ldk=3 * c, ldv=3 * c, ldo=c, batch=r.b * r.f, seq=r.hw,

@@ -114,6 +114,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--kv-downsample", type=int, default=None, choices=[1, 2, 4],
                    help="spatial self-attention over keys and values pooled over 2x2 / 4x4 token cells (levels of at least "
                         "4,096 tokens per frame); an approximation, default 1 = off")
+    p.add_argument("--spatial-window", type=int, nargs=2, default=None, metavar=("WH", "WW"),
+                   help="spatial self-attention over a sliding window of WH x WW tiles of 8x8 tokens (both odd; levels of at "
+                        "least 4,096 tokens per frame whose grid divides by 8); an approximation, default off")
     p.add_argument("--freeu", type=float, nargs=4, default=None, metavar=("B1", "B2", "S1", "S2"),
                    help="FreeU in the UNet's up path: backbone scales b1, b2 and skip-filter scales s1, s2 (e.g. 1.3 1.4 0.9 0.2); "
                         "default off")
@@ -226,7 +229,7 @@ def _build_engines(args, timesteps, device):
                                                  window_stride=args.window_stride, window_weights=args.window_weights,
                                                  eta=args.eta, s_noise=args.s_noise, fp8_ff=args.fp8_ff or None,
                                                  kv_downsample=args.kv_downsample, freeu=args.freeu, freeu_version=args.freeu_version,
-                                                 **tile_arguments(args))
+                                                 spatial_window=args.spatial_window, **tile_arguments(args))
         clip = CLIPVisionHIP(spec, clip_random_state_dict(spec, seed=args.seed + 1, device=device), device)
         enc = ImageEncoderHIP(vcfg, random_encoder_state_dict(vcfg, seed=args.seed + 2, device=device), device,
                               attention=args.vae_attention)
@@ -238,7 +241,7 @@ def _build_engines(args, timesteps, device):
                                             window_stride=args.window_stride, window_weights=args.window_weights,
                                             eta=args.eta, s_noise=args.s_noise, fp8_ff=args.fp8_ff or None,
                                             kv_downsample=args.kv_downsample, freeu=args.freeu, freeu_version=args.freeu_version,
-                                            **tile_arguments(args))
+                                            spatial_window=args.spatial_window, **tile_arguments(args))
     clip, enc, dec = load_edge_engines(args.model_id, device, vae_attention=args.vae_attention)
     return model, clip, enc, lambda: dec
 
